@@ -26,7 +26,7 @@ for wl in wls:
             env["BFC_BENCH_DEVICES"] = ",".join(["0"] * n)
         for tr in ((0,) if n == 1 else (0, 2)):  # default (push kernel: exact bytes) and whole-block peer copies
             env["BFC_BENCH_TRANSPORT"] = str(tr)
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--workload", wl, "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--workload", wl, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                                 "--no-boundary", "--no-secondary"] + (["--scaling", "weak"] if WEAK and n > 1 else []) + EXTRA.get(wl, []), capture_output=True, text=True, env=env)
             try:
                 d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -100,6 +100,34 @@ def test_c2_full_read_set(gpu_lib, batch_reads, layout):
     g.close()
 
 
+def test_bench_plain_run_dumps_c2_outputs(gpu_lib, tmp_path):
+    """bench.py without --full on config c2: ONE result line with the headline fields and none of what --full adds, and what
+    --dump-outputs writes (float arrays, at most 64 MB in all) is what the reference computed for the same reads."""
+    import subprocess
+    import sys
+    root = os.path.dirname(HERE)
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=900, cwd=root)
+    assert r.returncode == 0, r.stderr[-1500:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-500:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0, d
+    assert d["unit"] == "M k-mers/s" and d["higher_is_better"] is True and d["dtype"] == "u64"
+    assert not {"verified", "cpu_baseline", "secondary", "e2e", "pcie"} & set(d), sorted(d)
+    arrs = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    e = BASE["c2"]
+    assert arrs["counts"].tolist() == [e["n_kmers"], e["n_high"], e["n_seen"], e["distinct"]]
+    assert arrs["bloom_popcount"].tolist() == [e["bf_popcount"]]
+    assert np.array_equal(arrs["table_hist_cnt"], np.array(e["cnt"], dtype=np.float64))
+    assert np.array_equal(arrs["table_hist_high"], np.array(e["high"], dtype=np.float64))
+    assert len(arrs["table_sizes"]) == 1 << e["l_pre"] and arrs["table_sizes"].sum() == e["distinct"]  # (2^20 sub-tables: not sampled)
+    assert arrs["table_slots"].shape[1] == 2 and 0 < len(arrs["table_slots"]) <= e["distinct"] and arrs["table_slots"].max() < 2 ** 32
+    assert 0 < len(arrs["bloom_words"]) <= 1 << 20
+
+
 def test_c3_full_read_set(gpu_lib):
     """Config c3 as bench.py runs it (k=33, -b35 table mode, 49.6 M reads: 9+9 scatter levels, 16-byte records, the batches'
     k-mers hardly repeat so the context switches to STREAM mode, the table grows to 300 M keys): equals the reference."""

@@ -396,7 +396,7 @@ def test_bench_through_the_group_path_is_verified(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BFC_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29533",
-                        os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--no-boundary"],
+                        os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary", "--no-boundary"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-1500:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -418,7 +418,7 @@ def _bench_inproc(n, devices, workload, extra=()):
     if devices is not None:
         env["BFC_BENCH_DEVICES"] = devices
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--workload", workload, "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--no-secondary", "--no-boundary"] + list(extra), capture_output=True, text=True, timeout=1500, env=env, cwd=root)
+                        "--full", "--no-cpu-baseline", "--no-secondary", "--no-boundary"] + list(extra), capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, (r.stdout[-500:], r.stderr[-1500:])
     return r.returncode, json.loads(lines[0]), r.stderr
