@@ -552,3 +552,94 @@ class GpuKcov:
 
     def dev_seq(self):
         return self.L.bfcg_kcov_dev_seq(self.t)
+
+
+class GpuCorrector:
+    """BFC's error correction (bfc_ec1, correct.c:388-476) for whole batches of reads on the GPU (bfcg_ec_*), with the host instance of the
+    same code as a twin (bfcg_ec1_host).  `table` is a HostTable (bfc_count / bfc_ch_restore); it must outlive this object.  `opt` is a
+    table-mode bfc_opt_t (bfc_opt_init, k = the table's k).  Results are the reference's worker_ec: corrected bytes, aux, aux2."""
+
+    def __init__(self, table, opt, device=0, max_pos=1 << 24, max_reads=1 << 18, gpu=True):
+        self.L = _lib.load()
+        self.table, self.opt = table, opt
+        cnt, high = np.zeros(256, dtype=np.uint64), np.zeros(64, dtype=np.uint64)
+        self.mode = int(self.L.bfc_ch_hist(table.ptr, cnt.ctypes.data_as(u64p), high.ctypes.data_as(u64p)))
+        self.e = None
+        if gpu:
+            self.e = self.L.bfcg_ec_create(table.ptr, C.byref(opt), device, int(max_pos), int(max_reads))
+            if not self.e:
+                raise BfcGpuError("bfcg_ec_create failed: " + self.L.bfcg_last_error().decode())
+
+    def close(self):
+        if self.e:
+            self.L.bfcg_ec_destroy(self.e)
+            self.e = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def correct(self, seqs, quals=None):
+        """seqs: list of bytes (one read each); quals: list of bytes or None (FASTA).  Returns (seqs, quals or None, aux uint32[n], aux2 uint32[n])."""
+        n = len(seqs)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(s) + 1 for s in seqs])
+        s = np.frombuffer(b"".join(x + b"\n" for x in seqs), dtype=np.uint8).copy()
+        q = np.frombuffer(b"".join(x + b"!" for x in quals), dtype=np.uint8).copy() if quals is not None else None
+        aux, aux2 = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        rc = self.L.bfcg_ec_batch(self.e, s.ctypes.data, q.ctypes.data if q is not None else None, len(s), off.ctypes.data_as(u64p), n,
+                                  aux.ctypes.data_as(u32p), aux2.ctypes.data_as(u32p))
+        if rc != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        sb = s.tobytes()
+        out_s = [sb[int(off[i]):int(off[i + 1]) - 1] for i in range(n)]
+        out_q = None
+        if q is not None:
+            qb = q.tobytes()
+            out_q = [qb[int(off[i]):int(off[i + 1]) - 1] for i in range(n)]
+        return out_s, out_q, aux, aux2
+
+    def host_correct(self, seqs, quals=None):
+        """The same through the host instance, read by read."""
+        n = len(seqs)
+        out_s, out_q = [], [] if quals is not None else None
+        aux, aux2 = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        a, a2 = C.c_uint32(), C.c_uint32()
+        for i in range(n):
+            sb = C.create_string_buffer(seqs[i], len(seqs[i]) + 1)
+            qb = C.create_string_buffer(quals[i], len(quals[i]) + 1) if quals is not None else None
+            if self.L.bfcg_ec1_host(self.table.ptr, C.byref(self.opt), self.mode, sb, qb, C.byref(a), C.byref(a2)) != 0:
+                raise BfcGpuError(self.L.bfcg_last_error().decode())
+            out_s.append(sb.raw[:len(seqs[i])])
+            if qb is not None:
+                out_q.append(qb.raw[:len(quals[i])])
+            aux[i], aux2[i] = a.value, a2.value
+        return out_s, out_q, aux, aux2
+
+    def last_ms(self):
+        return float(self.L.bfcg_ec_last_ms(self.e))
+
+    def last_lookups(self):
+        return int(self.L.bfcg_ec_last_lookups(self.e))
+
+    def host_reads(self):
+        return int(self.L.bfcg_ec_host_reads(self.e))
+
+
+def format_ec(names, seqs, quals, aux, aux2, opt):
+    """bfc_ec_cb's output step (correct.c:592-612) in table mode for reads without comments: bytes of the corrected FASTA/FASTQ."""
+    out = []
+    for i, name in enumerate(names):
+        a, a2 = int(aux[i]), int(aux2[i])
+        if opt.discard and a & 7:
+            continue
+        is_fq = quals is not None and quals[i] is not None and not opt.no_qual
+        h = (b"@" if is_fq else b">") + name + b"\tec:Z:%d" % (a & 7)
+        if a & 7 == 0:
+            h += b"_%d:%d_%d_%d:%d_%d" % (a2 >> 10, a2 & 0xff, a >> 3 & 1, a >> 18 & 0x3fff, a >> 4 & 0x3fff, a2 >> 8 & 3)
+        out.append(h + b"\n" + seqs[i] + b"\n")
+        if is_fq:
+            out.append(b"+\n" + quals[i] + b"\n")
+    return b"".join(out)

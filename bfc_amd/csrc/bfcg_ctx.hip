@@ -1987,5 +1987,9 @@ extern "C" int bfcg_kcov_batch(bfcg_kcov_t *t, const uint8_t *h_seq, const uint8
 	return 0;
 }
 extern "C" float bfcg_kcov_last_ms(bfcg_kcov_t *t) { return t->last_ms; }
+// the corrector (bfcg_ec.hip) runs behind a coverage context: its table in HBM, the probe parameters, the device it lives on
+namespace bfcg {
+const unsigned long long *kcov_table(bfcg_kcov_t *t, KParams *P, int *device) { *P = t->P; *device = t->device; return t->table; }
+}
 extern "C" void *bfcg_kcov_dev_seq(bfcg_kcov_t *t) { return t->d_seq; }
 extern "C" void *bfcg_kcov_dev_out(bfcg_kcov_t *t) { return t->d_out; }

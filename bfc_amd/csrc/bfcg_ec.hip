@@ -1,0 +1,240 @@
+// bfcg_ec.hip -- BFC's error correction (bfc_ec1, correct.c:388-476) for whole batches of reads on gfx950, and its host instance.
+//
+// A batch: the k-mer coverage of every position first (k_occ / k_cov behind a bfcg_kcov_t, which also holds the uploaded table), then
+// k_ec: a persistent grid in which every lane corrects one read at a time with bfcg_ec1.h and takes the next read from a global
+// counter when it is done, so a slow read holds up only its own lane.  The search's heap (hcap entries) and stack (scap entries) and
+// the two directions' results (lmax bytes each) live in a per-lane slice of a global workspace.  A read that would overflow either
+// array, or is longer than lmax, is left untouched with aux2 = BFCG_EC_FALLBACK and corrected after the batch by the host instance of
+// the same code (bfcg_ec1_host): the results do not depend on hcap / scap / lmax (BFCG_EC_HEAP / BFCG_EC_STACK / BFCG_EC_LMAX).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <stdarg.h>
+#include "bfc_gpu.h"
+#include "bfcg_internal.h"
+#include "kmer_dev.h"
+#include "bfcg_ec1.h"
+
+using namespace ec1k;
+
+extern "C" void bfcg_set_error(const char *msg);
+namespace bfcg { const unsigned long long *kcov_table(bfcg_kcov_t *t, KParams *P, int *device); }
+
+static int ec_err(const char *fmt, ...)
+{
+	char buf[512];
+	va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
+	bfcg_set_error(buf);
+	return -1;
+}
+#define ECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return ec_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+static Opt ec_opt(const bfc_opt_t *opt, int mode)
+{
+	Opt o;
+	o.k = opt->k; o.q = opt->q; o.max_end_ext = opt->max_end_ext; o.win_multi_ec = opt->win_multi_ec; o.min_cov = opt->min_cov;
+	o.w_ec = opt->w_ec; o.w_ec_high = opt->w_ec_high; o.w_absent = opt->w_absent; o.w_absent_high = opt->w_absent_high;
+	o.max_path_diff = opt->max_path_diff; o.max_heap = opt->max_heap; o.mode = mode;
+	return o;
+}
+
+// ------------------------------------------------------------------------------------------------ host instance
+
+struct HostLookup {
+	const bfc_ch_t *ch;
+	int operator()(uint64_t y0, uint64_t y1) const { const uint64_t y[2] = {y0, y1}; return bfc_ch_get(ch, y); }
+};
+
+// one read of n bases; the heap and stack grow until the read fits
+static void host_ec1(const bfc_ch_t *ch, const Opt &o, uint8_t *seq, uint8_t *qual, int n, uint32_t *aux, uint32_t *aux2)
+{
+	const HostLookup lk = {ch};
+	uint16_t *cov = (uint16_t *)malloc((size_t)(n > 0 ? n : 1) * 2);
+	uint8_t *ecb = (uint8_t *)malloc((size_t)(n > 0 ? n : 1) * 2);
+	kcov(o, seq, n, lk, cov);
+	Result res;
+	for (int hcap = 64, scap = 4 * n + 256;; hcap *= 4, scap *= 4) {
+		Work w;
+		w.hcap = hcap; w.scap = scap;
+		w.heap = (Heap1 *)malloc(sizeof(Heap1) * (size_t)hcap); w.stack = (Stack1 *)malloc(sizeof(Stack1) * (size_t)scap);
+		if (!w.heap || !w.stack) { fprintf(stderr, "[E::bfcg_ec1_host] out of memory\n"); abort(); }
+		const int rc = ec1(o, seq, qual, cov, n, lk, w, ecb, ecb + n, &res);
+		free(w.heap); free(w.stack);
+		if (rc == EC_OK) break;
+	}
+	free(cov); free(ecb);
+	*aux = res.aux; *aux2 = res.aux2;
+}
+
+extern "C" int bfcg_ec1_host(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t *aux, uint32_t *aux2)
+{
+	if (!ch || !opt || !seq || opt->k != bfc_ch_get_k(ch)) return ec_err("bad arguments to bfcg_ec1_host");
+	const Opt o = ec_opt(opt, mode);
+	host_ec1(ch, o, (uint8_t *)seq, (uint8_t *)qual, (int)strlen(seq), aux, aux2);
+	return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ device
+
+struct DevLookup {
+	int k, l_pre, cshift;
+	const unsigned long long *tab;
+	unsigned *n;                                               // lookups by this lane
+	__device__ int operator()(uint64_t y0, uint64_t y1) const { ++*n; return bfcg::ch_get_dev(k, l_pre, cshift, tab, y0, y1); }
+};
+
+enum { EC_BT = 256 };
+
+// ctr[0]: next read; ctr[1]: table lookups; ctr[2]: reads left to the host
+__global__ __launch_bounds__(EC_BT) void k_ec(Opt o, int l_pre, int cshift, const unsigned long long *__restrict__ tab, uint8_t *seq, uint8_t *qual,
+                                              const uint16_t *__restrict__ cov, const uint64_t *__restrict__ off, uint64_t n_reads,
+                                              uint32_t *__restrict__ aux, uint32_t *__restrict__ aux2, Heap1 *heap_ws, Stack1 *stack_ws, uint8_t *ec_ws,
+                                              int hcap, int scap, int lmax, unsigned long long *ctr)
+{
+	const uint64_t lane = (uint64_t)blockIdx.x * EC_BT + threadIdx.x;
+	unsigned n_look = 0, n_host = 0;
+	const DevLookup lk = {o.k, l_pre, cshift, tab, &n_look};
+	Work w;
+	w.heap = heap_ws + lane * (uint64_t)hcap; w.stack = stack_ws + lane * (uint64_t)scap; w.hcap = hcap; w.scap = scap;
+	uint8_t *ec0 = ec_ws + lane * 2 * (uint64_t)lmax, *ec1b = ec0 + lmax;
+	for (;;) {
+		const uint64_t r = atomicAdd(&ctr[0], 1ULL);
+		if (r >= n_reads) break;
+		const uint64_t a = off[r];
+		const int n = (int)(off[r + 1] - a - 1);
+		Result res;
+		if (n > lmax || ec1(o, seq + a, qual ? qual + a : nullptr, cov + a, n, lk, w, ec0, ec1b, &res) != EC_OK) {
+			res.aux = 0; res.aux2 = BFCG_EC_FALLBACK; ++n_host;
+		}
+		aux[r] = res.aux; aux2[r] = res.aux2;
+	}
+	atomicAdd(&ctr[1], (unsigned long long)n_look);
+	if (n_host) atomicAdd(&ctr[2], (unsigned long long)n_host);
+}
+
+struct bfcg_ec {
+	bfcg_kcov_t *kc;
+	const bfc_ch_t *ch;
+	Opt o;
+	bfcg::KParams P;
+	const unsigned long long *tab;
+	int device, hcap, scap, lmax;
+	uint64_t lanes, max_pos, max_reads;
+	hipStream_t st;
+	hipEvent_t e0, e1;
+	uint8_t *d_qual, *d_ec;
+	uint64_t *d_off;
+	uint32_t *d_aux, *d_aux2;
+	Heap1 *d_heap;
+	Stack1 *d_stack;
+	unsigned long long *d_ctr;
+	float last_ms;
+	uint64_t host_reads, last_lookups, last_host;
+};
+
+static int env_int(const char *name, int dflt, int lo, int hi)
+{
+	const char *s = getenv(name);
+	int v = s && *s ? atoi(s) : dflt;
+	return v < lo ? lo : v > hi ? hi : v;
+}
+
+extern "C" void bfcg_ec_destroy(bfcg_ec_t *e)
+{
+	if (!e) return;
+	if (e->st) { (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->st); }
+	(void)hipFree(e->d_qual); (void)hipFree(e->d_ec); (void)hipFree(e->d_off); (void)hipFree(e->d_aux); (void)hipFree(e->d_aux2);
+	(void)hipFree(e->d_heap); (void)hipFree(e->d_stack); (void)hipFree(e->d_ctr);
+	if (e->st) { (void)hipEventDestroy(e->e0); (void)hipEventDestroy(e->e1); (void)hipStreamDestroy(e->st); }
+	bfcg_kcov_destroy(e->kc);
+	free(e);
+}
+
+#define ECN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ec_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); bfcg_ec_destroy(e); return NULL; } } while (0)
+
+extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, int device, uint64_t max_pos, uint64_t max_reads)
+{
+	if (!ch || !opt || opt->k != bfc_ch_get_k(ch) || max_pos == 0 || max_reads == 0 || opt->filter_mode || opt->refine_ec) {
+		ec_err("bad arguments to bfcg_ec_create (a table-mode bfc_opt_t whose k is the table's, without refine_ec)");
+		return NULL;
+	}
+	bfcg_ec_t *e = (bfcg_ec_t *)calloc(1, sizeof(bfcg_ec_t));
+	e->kc = bfcg_kcov_create(ch, device, max_pos);                 // uploads the table once (and says so if there is no GPU)
+	if (!e->kc) { free(e); return NULL; }
+	uint64_t hist[256], hist_high[64];
+	e->ch = ch;
+	e->o = ec_opt(opt, bfc_ch_hist(ch, hist, hist_high));        // correct.c:627
+	e->tab = bfcg::kcov_table(e->kc, &e->P, &e->device);
+	e->max_pos = max_pos; e->max_reads = max_reads;
+	e->hcap = env_int("BFCG_EC_HEAP", 16, 1, 1 << 16);
+	e->scap = env_int("BFCG_EC_STACK", 1024, 1, 1 << 20);
+	e->lmax = env_int("BFCG_EC_LMAX", 512, 1, 1 << 16);
+	const uint64_t lanes_max = (uint64_t)env_int("BFCG_EC_LANES", 1 << 17, EC_BT, 1 << 20);
+	e->lanes = (max_reads + EC_BT - 1) / EC_BT * EC_BT;
+	if (e->lanes > lanes_max) e->lanes = lanes_max / EC_BT * EC_BT;
+	ECN(hipSetDevice(e->device));
+	ECN(hipStreamCreate(&e->st));
+	ECN(hipEventCreate(&e->e0)); ECN(hipEventCreate(&e->e1));
+	ECN(hipMalloc(&e->d_qual, max_pos));
+	ECN(hipMalloc(&e->d_off, (max_reads + 1) * 8));
+	ECN(hipMalloc(&e->d_aux, max_reads * 4)); ECN(hipMalloc(&e->d_aux2, max_reads * 4));
+	ECN(hipMalloc(&e->d_heap, sizeof(Heap1) * e->lanes * (uint64_t)e->hcap));
+	ECN(hipMalloc(&e->d_stack, sizeof(Stack1) * e->lanes * (uint64_t)e->scap));
+	ECN(hipMalloc(&e->d_ec, e->lanes * 2 * (uint64_t)e->lmax));
+	ECN(hipMalloc(&e->d_ctr, 3 * sizeof(unsigned long long)));
+	return e;
+}
+
+// seq / qual: host streams of n_pos positions in the batch format of PART 2 (qual NULL: no read has a quality string); rewritten in place
+extern "C" int bfcg_ec_batch(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, uint32_t *aux, uint32_t *aux2)
+{
+	if (!e || !seq || !off || !aux || !aux2) return ec_err("bad arguments to bfcg_ec_batch");
+	if (n_pos > e->max_pos || n_reads > e->max_reads) return ec_err("correction batch exceeds the capacity given to bfcg_ec_create");
+	if (n_reads && off[n_reads] != n_pos) return ec_err("bfcg_ec_batch: off[n_reads] must be n_pos");
+	e->last_ms = 0; e->last_lookups = 0; e->last_host = 0;
+	if (n_reads == 0) return 0;
+	for (uint64_t r = 0; r < n_reads; ++r)                       // every read ends in its separator inside the batch
+		if (off[r + 1] <= off[r]) return ec_err("bfcg_ec_batch: read %llu has no separator", (unsigned long long)r);
+	uint8_t *d_seq = (uint8_t *)bfcg_kcov_dev_seq(e->kc);
+	const uint16_t *d_cov = (const uint16_t *)bfcg_kcov_dev_out(e->kc);
+	ECK(hipSetDevice(e->device));
+	ECK(hipMemcpy(d_seq, seq, n_pos, hipMemcpyHostToDevice));
+	if (bfcg_kcov_batch(e->kc, nullptr, d_seq, n_pos, e->o.min_cov, nullptr) != 0) return -1;
+	const float ms_cov = bfcg_kcov_last_ms(e->kc);
+	if (qual) ECK(hipMemcpyAsync(e->d_qual, qual, n_pos, hipMemcpyHostToDevice, e->st));
+	ECK(hipMemcpyAsync(e->d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice, e->st));
+	ECK(hipMemsetAsync(e->d_ctr, 0, 3 * sizeof(unsigned long long), e->st));
+	uint64_t lanes = (n_reads + EC_BT - 1) / EC_BT * EC_BT;
+	if (lanes > e->lanes) lanes = e->lanes;
+	ECK(hipEventRecord(e->e0, e->st));
+	hipLaunchKernelGGL(k_ec, dim3((unsigned)(lanes / EC_BT)), dim3(EC_BT), 0, e->st, e->o, e->P.l_pre, e->P.tab_cshift, e->tab, d_seq,
+	                   qual ? e->d_qual : nullptr, d_cov, (const uint64_t *)e->d_off, n_reads, e->d_aux, e->d_aux2, e->d_heap, e->d_stack, e->d_ec,
+	                   e->hcap, e->scap, e->lmax, e->d_ctr);
+	ECK(hipGetLastError());
+	ECK(hipEventRecord(e->e1, e->st));
+	unsigned long long ctr[3];
+	ECK(hipMemcpyAsync(seq, d_seq, n_pos, hipMemcpyDeviceToHost, e->st));
+	if (qual) ECK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
+	ECK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+	ECK(hipMemcpyAsync(aux2, e->d_aux2, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+	ECK(hipMemcpyAsync(ctr, e->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->st));
+	ECK(hipStreamSynchronize(e->st));
+	float ms = 0;
+	ECK(hipEventElapsedTime(&ms, e->e0, e->e1));
+	e->last_ms = ms_cov + ms;
+	e->last_lookups = ctr[1];
+	for (uint64_t r = 0; r < n_reads; ++r) {                     // the reads the device left to the host instance
+		if (aux2[r] != BFCG_EC_FALLBACK) continue;
+		const uint64_t a = off[r];
+		host_ec1(e->ch, e->o, seq + a, qual ? qual + a : nullptr, (int)(off[r + 1] - a - 1), &aux[r], &aux2[r]);
+		++e->last_host;
+	}
+	e->host_reads += e->last_host;
+	return 0;
+}
+
+extern "C" float bfcg_ec_last_ms(bfcg_ec_t *e) { return e->last_ms; }
+extern "C" uint64_t bfcg_ec_host_reads(bfcg_ec_t *e) { return e->host_reads; }
+extern "C" uint64_t bfcg_ec_last_lookups(bfcg_ec_t *e) { return e->last_lookups; }

@@ -2083,20 +2083,10 @@ __global__ __launch_bounds__(256) void k_streak(int k, float min_frac, const uns
 //   k_cov : lcov / hcov of every base = number of solid (solid and high) k-mers covering it = the k flags that follow it;
 //           packed like ecbase_t's bit-fields (correct.c:14-19): lcov | hcov<<6 | solid_end<<12 | high_end<<13
 
-// bfc_ch_get on the device layout: probe the sub-table's region from the key's home slot until the key or an empty slot
+// bfc_ch_get on the device layout (kmer_dev.h: ch_get_dev)
 __device__ __forceinline__ int table_get(const KParams &P, const unsigned long long *__restrict__ tab, uint64_t y0, uint64_t y1)
 {
-	uint64_t key;
-	const uint32_t sub = ch_subkey(P.k, P.l_pre, y0, y1, key);
-	const uint32_t cmask = (1u << P.tab_cshift) - 1;
-	const unsigned long long *reg = tab + ((uint64_t)sub << P.tab_cshift);
-	uint32_t pos = (uint32_t)(key >> 14) & cmask;
-	for (uint32_t probe = 0; probe <= cmask; ++probe, pos = (pos + 1) & cmask) {
-		const unsigned long long cur = reg[pos];
-		if (cur == 0) return -1;
-		if ((cur >> 14) == (key >> 14)) return (int)(cur & 0x3fff);
-	}
-	return -1;
+	return ch_get_dev(P.k, P.l_pre, P.tab_cshift, tab, y0, y1);
 }
 
 template <typename W, int TILE, int BT>

@@ -149,6 +149,23 @@ __device__ __forceinline__ uint32_t ch_subkey(int k, int l_pre, uint64_t y0, uin
 	}
 }
 
+// bfc_ch_get (htab.c:84-92) on the host's table layout in HBM: probe the sub-table's region from the key's home slot until the key or an
+// empty slot.  -1 | high << 8 | count.  (k_occ's table_get; the corrector, bfcg_ec.hip)
+__device__ __forceinline__ int ch_get_dev(int k, int l_pre, int cshift, const unsigned long long *__restrict__ tab, uint64_t y0, uint64_t y1)
+{
+	uint64_t key;
+	const uint32_t sub = ch_subkey(k, l_pre, y0, y1, key);
+	const uint32_t cmask = (1u << cshift) - 1;
+	const unsigned long long *reg = tab + ((uint64_t)sub << cshift);
+	uint32_t pos = (uint32_t)(key >> 14) & cmask;
+	for (uint32_t probe = 0; probe <= cmask; ++probe, pos = (pos + 1) & cmask) {
+		const unsigned long long cur = reg[pos];
+		if (cur == 0) return -1;
+		if ((cur >> 14) == (key >> 14)) return (int)(cur & 0x3fff);
+	}
+	return -1;
+}
+
 // ---- region-owned table segments ----
 // Every occurrence of a k-mer falls into the same bloom region f = block id >> R, and block id = the low bf_shift-9 bits of
 // hash = (h0^h1)<<k | y0 (kmer.h:87): bits [lo, hi) of y0, lo = min(R, k), hi = max(lo, min(k, bf_shift-9)), ARE the low hi-lo bits of f.

@@ -80,7 +80,8 @@ void *bfc_count(const char *fn, const bfc_opt_t *opt);
  * (opt->filter_mode, ptr = the bfc_bf_t* bfc_count returned): bloom queries (bbf.c:47-63), longest streak
  * (correct.c:478-497) and the keep/trim rule (correct.c:557-569) run on the GPU, output as correct.c:595-611.
  * With filter_mode off it forwards to bfc_correct_cpu(), i.e. the reference's correct.c compiled with
- * -Dbfc_correct=bfc_correct_cpu; error correction itself is not part of this library. */
+ * -Dbfc_correct=bfc_correct_cpu.  Error correction (table mode, no refine_ec) runs on the GPU (bfcg_ec_*, PART 2)
+ * when BFC_GPU_EC=1 is set or bfc_correct_cpu is not linked; otherwise it is bfc_correct_cpu's. */
 void bfc_correct(const char *fn, const bfc_opt_t *opt, const void *ptr);
 
 /* ============================================================ PART 2: device-level API */
@@ -292,6 +293,24 @@ int bfcg_kcov_batch(bfcg_kcov_t *t, const uint8_t *h_seq, const uint8_t *d_seq, 
 float bfcg_kcov_last_ms(bfcg_kcov_t *t);   /* GPU time of the last batch's two kernels (HIP events) */
 void *bfcg_kcov_dev_seq(bfcg_kcov_t *t);   /* device staging buffer for the stream (max_pos bytes) */
 void *bfcg_kcov_dev_out(bfcg_kcov_t *t);   /* device result of the last batch (max_pos u16) */
+
+/* BFC's error correction (bfc_ec1, correct.c:388-476) for whole batches of reads (bfcg_ec.hip): the k-mer coverage pass above, then one
+ * read per lane of a persistent grid (bfcg_ec1.h: the per-read search, shared with the host).  Output is byte-identical to the reference's
+ * worker_ec / bfc_ec_cb in table mode (opt->filter_mode and opt->refine_ec off) for any other option.  The table is uploaded once from
+ * the host bfc_ch_t, which must outlive the object: reads the device cannot hold (heap or stack full, longer than its bound) are corrected
+ * after the batch by the host instance, bfcg_ec1_host, on that table.  BFCG_EC_HEAP / BFCG_EC_STACK / BFCG_EC_LMAX set the device's heap
+ * and stack entries and read length per lane (results do not depend on them).
+ *   bfcg_ec_batch: the stream and off[] as bfcg_trim_batch (off[n_reads] = n_pos); qual NULL: no quality strings.  seq / qual are
+ *   rewritten in place as bfc_ec1 does (reads with ec_code != 0 untouched); aux / aux2 as worker_ec packs them (correct.c:552-553).
+ *   bfcg_ec1_host: one NUL-terminated read on the host; mode = bfc_ch_hist(ch, ...). */
+typedef struct bfcg_ec bfcg_ec_t;
+bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, int device, uint64_t max_pos, uint64_t max_reads);
+int   bfcg_ec_batch(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, uint32_t *aux, uint32_t *aux2);
+void  bfcg_ec_destroy(bfcg_ec_t *e);
+float bfcg_ec_last_ms(bfcg_ec_t *e);          /* GPU time of the last batch: coverage + correction kernels (HIP events) */
+uint64_t bfcg_ec_host_reads(bfcg_ec_t *e);    /* reads the host fallback corrected, since creation */
+uint64_t bfcg_ec_last_lookups(bfcg_ec_t *e);  /* table lookups of the last batch's correction kernel (the coverage pass adds one per k-mer) */
+int   bfcg_ec1_host(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t *aux, uint32_t *aux2);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);

@@ -1,0 +1,78 @@
+"""Rate of error correction on the GPU (bfcg_ec_batch: coverage pass + k_ec) against the reference's correction phase on the same host.
+
+    python scripts/ec_rate.py --set ecoli   # E. coli 30x: gen.ReadSet(2, 4_600_000, 30.0), -k31 -b30, every read
+    python scripts/ec_rate.py --set c3      # c3's read set (seed 3, 248 Mbp, 30x) with c3's table (-k33 -b35), a sample of its reads
+
+The table is counted on the GPU and exported to the host (bfcg_ec_create uploads it once).  GPU time is bfcg_ec_last_ms summed over
+batches (HIP events around the two kernels of a batch; inputs already staged); lookups are counted on the device.  The reference:
+`bfc-ref -t16 -r <dump>` on the first --ref-reads reads, timed from its `bfc_correct ... Starting...` stamp to its exit.
+Prints one JSON line."""
+import argparse, json, os, re, subprocess, sys, tempfile, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ctypes as C
+import numpy as np
+import bfc_amd
+from bfc_amd import gen, _lib
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--set", default="ecoli", choices=["ecoli", "c3"])
+ap.add_argument("--reads", type=int, default=0, help="reads to correct on the GPU (0: ecoli all, c3 4M)")
+ap.add_argument("--ref-reads", type=int, default=200_000, help="reads the reference corrects (0: skip)")
+ap.add_argument("--batch", type=int, default=1 << 20, help="reads per bfcg_ec_batch")
+args = ap.parse_args()
+S = {"ecoli": dict(seed=2, G=4_600_000, cov=30.0, k=31, b=30, reads=0), "c3": dict(seed=3, G=248_000_000, cov=30.0, k=33, b=35, reads=4_000_000)}[args.set]
+t0 = time.time()
+rs = gen.ReadSet(seed=S["seed"], G=S["G"], cov=S["cov"])
+stride = rs.L + 1
+n_ec = args.reads or S["reads"] or rs.n_reads
+CH = 2_000_000
+g = bfc_amd.GpuCounter(S["k"], S["b"], max_batch_pos=CH * stride)
+for r0 in range(0, rs.n_reads, CH):
+    r1 = min(rs.n_reads, r0 + CH)
+    seq, qual, off = rs.reads(r0, r1)
+    g.count_host(bfc_amd.to_stream(seq, off), bfc_amd.to_stream(qual, off))
+t = g.export_table()
+g.close()
+print("[ec_rate] %s: %d reads counted, table exported (%.1fs)" % (args.set, rs.n_reads, time.time() - t0), file=sys.stderr, flush=True)
+
+opt = bfc_amd.bfc_opt_init(); opt.k = S["k"]
+B = args.batch
+c = bfc_amd.GpuCorrector(t, opt, max_pos=B * stride, max_reads=B)
+L = _lib.load()
+ms = 0.0; lookups = 0; n_done = 0; codes = np.zeros(8, dtype=np.int64); n_changed = 0
+for r0 in range(0, n_ec, B):
+    r1 = min(n_ec, r0 + B)
+    seq, qual, off = rs.reads(r0, r1)
+    s, q = bfc_amd.to_stream(seq, off), bfc_amd.to_stream(qual, off)
+    o = np.arange(r1 - r0 + 1, dtype=np.uint64) * np.uint64(stride)
+    aux = np.zeros(r1 - r0, dtype=np.uint32); aux2 = np.zeros(r1 - r0, dtype=np.uint32)
+    rc = L.bfcg_ec_batch(c.e, s.ctypes.data, q.ctypes.data, len(s), o.ctypes.data_as(_lib.u64p), r1 - r0,
+                         aux.ctypes.data_as(_lib.u32p), aux2.ctypes.data_as(_lib.u32p))
+    assert rc == 0, L.bfcg_last_error()
+    ms += c.last_ms(); lookups += c.last_lookups(); n_done += r1 - r0
+    codes += np.bincount(aux & 7, minlength=8); n_changed += int((aux >> 18).sum())
+n_kmers = n_done * (rs.L - S["k"] + 1)
+res = dict(set=args.set, k=S["k"], b=S["b"], reads=n_done, gpu_ms=round(ms, 2), gpu_reads_per_s=round(n_done / ms * 1e3),
+           ec_lookups=lookups, lookups_per_read=round((lookups + n_kmers) / n_done, 1),
+           lookups_per_s=round((lookups + n_kmers) / ms * 1e3), host_fallback_reads=c.host_reads(),
+           host_fallback_share=c.host_reads() / n_done, ec_codes=[int(v) for v in codes[:6]], bases_changed=n_changed)
+c.close()
+
+ref = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "bfc-ref")
+if args.ref_reads and os.path.exists(ref):
+    with tempfile.TemporaryDirectory() as d:
+        fq, dump = os.path.join(d, "s.fq"), os.path.join(d, "t.hash")
+        rs.fastq(fq, 0, args.ref_reads)
+        t.dump(dump)
+        t1 = time.time()
+        r = subprocess.run([ref, "-t16", "-k", str(S["k"]), "-r", dump, fq], capture_output=True, timeout=560)
+        wall = time.time() - t1
+        err = r.stderr.decode()
+        m = re.search(r"\[M::bfc_correct @([0-9.]+)\*", err)
+        m_end = re.findall(r"\[M::bfc_ec_cb @([0-9.]+)\*", err)
+        assert r.returncode == 0 and m and m_end, err[-1000:]
+        ec_s = float(m_end[-1]) - float(m.group(1))
+        res.update(ref_reads=args.ref_reads, ref_threads=16, ref_correct_s=round(ec_s, 2), ref_reads_per_s=round(args.ref_reads / ec_s),
+                   ref_wall_s=round(wall, 1), speedup_vs_ref_t16=round((n_done / ms * 1e3) / (args.ref_reads / ec_s), 1))
+t.close()
+print(json.dumps(res))
