@@ -137,6 +137,9 @@ SYMBOLS = {
     "bfcg_ec_host_reads": (C.c_uint64, [C.c_void_p]),
     "bfcg_ec_last_lookups": (C.c_uint64, [C.c_void_p]),
     "bfcg_ec1_host": (C.c_int, [C.c_void_p, C.POINTER(BfcOpt), C.c_int, C.c_void_p, C.c_void_p, u32p, u32p]),
+    "bfcg_ec_batch_refine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, u32p, u32p, u32p, u32p]),
+    "bfcg_ec1_host_refine": (C.c_int, [C.c_void_p, C.POINTER(BfcOpt), C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, u32p, u32p]),
+    "bfcg_ec_parse_stats": (C.c_int, [C.c_char_p, u32p, u32p]),
     "bfcg_hash_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_seen_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
 }

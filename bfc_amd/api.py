@@ -557,7 +557,11 @@ class GpuKcov:
 class GpuCorrector:
     """BFC's error correction (bfc_ec1, correct.c:388-476) for whole batches of reads on the GPU (bfcg_ec_*), with the host instance of the
     same code as a twin (bfcg_ec1_host).  `table` is a HostTable (bfc_count / bfc_ch_restore); it must outlive this object.  `opt` is a
-    table-mode bfc_opt_t (bfc_opt_init, k = the table's k).  Results are the reference's worker_ec: corrected bytes, aux, aux2."""
+    table-mode bfc_opt_t (bfc_opt_init, k = the table's k).  Results are the reference's worker_ec: corrected bytes, aux, aux2.
+
+    With opt.refine_ec (`bfc -R`) every read given is refined: correct / host_correct take `ori`, the reads' earlier stats as two uint32
+    arrays packed like aux / aux2 (parse_ec_stats; all zero where there were none).  Which reads to skip is the caller's choice, as in
+    worker_ec (correct.c:542-546)."""
 
     def __init__(self, table, opt, device=0, max_pos=1 << 24, max_reads=1 << 18, gpu=True):
         self.L = _lib.load()
@@ -581,16 +585,34 @@ class GpuCorrector:
         except Exception:
             pass
 
-    def correct(self, seqs, quals=None):
-        """seqs: list of bytes (one read each); quals: list of bytes or None (FASTA).  Returns (seqs, quals or None, aux uint32[n], aux2 uint32[n])."""
+    def _ori(self, n, ori):
+        if not self.opt.refine_ec:
+            if ori is not None:
+                raise BfcGpuError("earlier stats (ori) are for a corrector made with refine_ec")
+            return None
+        if ori is None:
+            return np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        a, a2 = (np.ascontiguousarray(x, dtype=np.uint32) for x in ori)
+        if len(a) != n or len(a2) != n:
+            raise BfcGpuError("ori: two arrays of one entry per read")
+        return a, a2
+
+    def correct(self, seqs, quals=None, ori=None):
+        """seqs: list of bytes (one read each); quals: list of bytes or None (FASTA); ori: (aux, aux2) earlier stats, refine_ec only.
+        Returns (seqs, quals or None, aux uint32[n], aux2 uint32[n])."""
         n = len(seqs)
+        ori = self._ori(n, ori)
         off = np.zeros(n + 1, dtype=np.uint64)
         off[1:] = np.cumsum([len(s) + 1 for s in seqs])
         s = np.frombuffer(b"".join(x + b"\n" for x in seqs), dtype=np.uint8).copy()
         q = np.frombuffer(b"".join(x + b"!" for x in quals), dtype=np.uint8).copy() if quals is not None else None
         aux, aux2 = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
-        rc = self.L.bfcg_ec_batch(self.e, s.ctypes.data, q.ctypes.data if q is not None else None, len(s), off.ctypes.data_as(u64p), n,
-                                  aux.ctypes.data_as(u32p), aux2.ctypes.data_as(u32p))
+        if ori is None:
+            rc = self.L.bfcg_ec_batch(self.e, s.ctypes.data, q.ctypes.data if q is not None else None, len(s), off.ctypes.data_as(u64p), n,
+                                      aux.ctypes.data_as(u32p), aux2.ctypes.data_as(u32p))
+        else:
+            rc = self.L.bfcg_ec_batch_refine(self.e, s.ctypes.data, q.ctypes.data if q is not None else None, len(s), off.ctypes.data_as(u64p), n,
+                                             ori[0].ctypes.data_as(u32p), ori[1].ctypes.data_as(u32p), aux.ctypes.data_as(u32p), aux2.ctypes.data_as(u32p))
         if rc != 0:
             raise BfcGpuError(self.L.bfcg_last_error().decode())
         sb = s.tobytes()
@@ -601,16 +623,21 @@ class GpuCorrector:
             out_q = [qb[int(off[i]):int(off[i + 1]) - 1] for i in range(n)]
         return out_s, out_q, aux, aux2
 
-    def host_correct(self, seqs, quals=None):
+    def host_correct(self, seqs, quals=None, ori=None):
         """The same through the host instance, read by read."""
         n = len(seqs)
+        ori = self._ori(n, ori)
         out_s, out_q = [], [] if quals is not None else None
         aux, aux2 = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
         a, a2 = C.c_uint32(), C.c_uint32()
         for i in range(n):
             sb = C.create_string_buffer(seqs[i], len(seqs[i]) + 1)
             qb = C.create_string_buffer(quals[i], len(quals[i]) + 1) if quals is not None else None
-            if self.L.bfcg_ec1_host(self.table.ptr, C.byref(self.opt), self.mode, sb, qb, C.byref(a), C.byref(a2)) != 0:
+            if ori is None:
+                rc = self.L.bfcg_ec1_host(self.table.ptr, C.byref(self.opt), self.mode, sb, qb, C.byref(a), C.byref(a2))
+            else:
+                rc = self.L.bfcg_ec1_host_refine(self.table.ptr, C.byref(self.opt), self.mode, sb, qb, int(ori[0][i]), int(ori[1][i]), C.byref(a), C.byref(a2))
+            if rc != 0:
                 raise BfcGpuError(self.L.bfcg_last_error().decode())
             out_s.append(sb.raw[:len(seqs[i])])
             if qb is not None:
@@ -628,17 +655,33 @@ class GpuCorrector:
         return int(self.L.bfcg_ec_host_reads(self.e))
 
 
-def format_ec(names, seqs, quals, aux, aux2, opt):
-    """bfc_ec_cb's output step (correct.c:592-612) in table mode for reads without comments: bytes of the corrected FASTA/FASTQ."""
+def parse_ec_stats(comment):
+    """worker_ec's test and parse_stats (correct.c:517-531, 542-543) on a read's comment (bytes or str), through bfcg_ec_parse_stats:
+    (aux, aux2) packed as worker_ec packs them (rf_code 1, fields cut to ecstat_t's bit-field widths), or None if the comment does not
+    start with "ec:Z:".  A read is skipped by `-R` if aux & 7 == 0 and aux2 & 0xff < 50."""
+    if isinstance(comment, str):
+        comment = comment.encode()
+    a, a2 = C.c_uint32(), C.c_uint32()
+    if not _lib.load().bfcg_ec_parse_stats(comment, C.byref(a), C.byref(a2)):
+        return None
+    return a.value, a2.value
+
+
+def format_ec(names, seqs, quals, aux, aux2, opt, comments=None):
+    """bfc_ec_cb's output step (correct.c:592-612) in table mode: bytes of the corrected FASTA/FASTQ.  comments[i] (bytes), where given and
+    not None, is printed after the name instead of an ec:Z: tag (a read `-R` skipped: worker_ec kept its comment, aux = 0)."""
     out = []
     for i, name in enumerate(names):
         a, a2 = int(aux[i]), int(aux2[i])
         if opt.discard and a & 7:
             continue
         is_fq = quals is not None and quals[i] is not None and not opt.no_qual
-        h = (b"@" if is_fq else b">") + name + b"\tec:Z:%d" % (a & 7)
-        if a & 7 == 0:
-            h += b"_%d:%d_%d_%d:%d_%d" % (a2 >> 10, a2 & 0xff, a >> 3 & 1, a >> 18 & 0x3fff, a >> 4 & 0x3fff, a2 >> 8 & 3)
+        if comments is not None and comments[i] is not None:
+            h = (b"@" if is_fq else b">") + name + b"\t" + comments[i]
+        else:
+            h = (b"@" if is_fq else b">") + name + b"\tec:Z:%d" % (a & 7)
+            if a & 7 == 0:
+                h += b"_%d:%d_%d_%d:%d_%d" % (a2 >> 10, a2 & 0xff, a >> 3 & 1, a >> 18 & 0x3fff, a >> 4 & 0x3fff, a2 >> 8 & 3)
         out.append(h + b"\n" + seqs[i] + b"\n")
         if is_fq:
             out.append(b"+\n" + quals[i] + b"\n")

@@ -6,7 +6,8 @@
  *
  * An unmodified correct.c can never call a batched kernel, so this object provides `bfc_correct` itself; the reference's
  * corrector is linked under another name (compile correct.c with -Dbfc_correct=bfc_correct_cpu, source untouched, see
- * INTEGRATION.md) and is what this function forwards to when filter_mode is off.
+ * INTEGRATION.md) and is what this function forwards to when filter_mode is off -- unless BFC_GPU_EC=1 is set or bfc_correct_cpu is not
+ * linked: then table-mode correction, `-R` included, runs on the GPU (correct_gpu below).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -78,45 +79,144 @@ static uint64_t read_batch(parser_t *ps, batch_t *b, uint64_t *off, uint64_t max
 	return n;
 }
 
+/* worker_ec's test and parse_stats (correct.c:517-531, 542-543) with ecstat_t's bit-fields (correct.c:144-147) as masks, packed as
+ * worker_ec packs a result (correct.c:552-553).  Where the reference's strtol(p + 1, ...) would step over the comment's NUL, the fields
+ * left are 0. */
+int bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2)
+{
+	long v[6] = {0, 0, 0, 0, 0, 0}; /* ec_code, n_absent, max_heap, brute, n_ec, n_ec_high: the order of the ec:Z: tag */
+	char *p;
+	int i;
+	if (!comment || strncmp(comment, "ec:Z:", 5) != 0) return 0;
+	v[0] = strtol(comment + 5, &p, 10);
+	if (((uint32_t)v[0] & 7) == 0)
+		for (i = 1; i < 6 && *p; ++i) v[i] = strtol(p + 1, &p, 10);
+	*aux = ((uint32_t)v[4] & 0x3fff) << 18 | ((uint32_t)v[5] & 0x3fff) << 4 | ((uint32_t)v[3] & 1) << 3 | ((uint32_t)v[0] & 7);
+	*aux2 = ((uint32_t)v[1] & 0x3fffff) << 10 | 1u << 8 | ((uint32_t)v[2] & 0xff); /* rf_code 1 */
+	return 1;
+}
+
 /* Error correction of table mode on the GPU (bfcg_ec_*): bfc_ec_cb's pipeline (correct.c:575-612) batch by batch -- parse as
  * bseq_read(..., keep_comment = 0, ...) does, correct every read (bfc_ec1 through worker_ec, correct.c:532-553), print.  With several
- * devices (BFC_GPU_DEVICES) each batch's reads are dealt to them as in the trim pass, one host thread per device. */
-typedef struct { bfcg_ec_t *e; uint8_t *seq, *qual; uint64_t n_pos; uint64_t *off; uint64_t n; uint32_t *aux, *aux2; int rc; char err[256]; } ec_job_t;
+ * devices (BFC_GPU_DEVICES) each batch's reads are dealt to them as in the trim pass, one host thread per device.
+ * With refine_ec (`-R`) comments are kept (correct.c:578) and worker_ec's first step runs here on the host, read by read in stream order
+ * (what `-t1` does): a comment that starts with ec:Z: becomes the stats the following reads are held to (ori_st, carried across batches),
+ * and its read is printed as it came if they say ec_code 0 and max_heap < 50.  The others go to the GPU as a batch of their own, so the
+ * coverage pass sees only reads that are corrected. */
+typedef struct { bfcg_ec_t *e; uint8_t *seq, *qual; uint64_t n_pos; uint64_t *off; uint64_t n; const uint32_t *oaux, *oaux2; uint32_t *aux, *aux2; int rc; char err[256]; } ec_job_t;
+static int ec_run(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, uint64_t *off, uint64_t n, const uint32_t *oaux, const uint32_t *oaux2,
+                  uint32_t *aux, uint32_t *aux2)
+{
+	return oaux ? bfcg_ec_batch_refine(e, seq, qual, n_pos, off, n, oaux, oaux2, aux, aux2) : bfcg_ec_batch(e, seq, qual, n_pos, off, n, aux, aux2);
+}
 static void *ec_worker(void *p)
 {
 	ec_job_t *j = (ec_job_t*)p;
-	j->rc = j->n ? bfcg_ec_batch(j->e, j->seq, j->qual, j->n_pos, j->off, j->n, j->aux, j->aux2) : 0;
+	j->rc = j->n ? ec_run(j->e, j->seq, j->qual, j->n_pos, j->off, j->n, j->oaux, j->oaux2, j->aux, j->aux2) : 0;
 	if (j->rc != 0) { strncpy(j->err, bfcg_last_error(), sizeof(j->err) - 1); j->err[sizeof(j->err) - 1] = 0; }
 	return 0;
+}
+
+/* one batch (n reads, off[0] = 0) corrected: by the host instance where records without a quality string meet q > 93 (below), else on the
+ * GPU(s).  ri[idx[r]] (ri[r] without idx) describes read r; oaux / oaux2: NULL, or the reads' earlier stats (refinement) */
+typedef struct {
+	const bfc_opt_t *opt;
+	const bfc_ch_t *ch;
+	bfcg_ec_t *ecs[64];
+	int devs[64], n_dev;
+	uint64_t *off2;
+	double gpu_ms;
+	uint64_t n_host;
+} ec_devs_t;
+static void ec_correct(ec_devs_t *g, uint8_t *seq, uint8_t *qual, int has_qual, int any_noq, uint64_t n_pos, uint64_t *off, uint64_t n,
+                       const rinfo_t *ri, const uint64_t *idx, const uint32_t *oaux, const uint32_t *oaux2, uint32_t *aux, uint32_t *aux2)
+{
+	const bfc_opt_t *opt = g->opt;
+	uint64_t r;
+	int d;
+	/* a record without a quality string has '~' in the stream (batch_put): q = (93 >= opt->q), which is what no quality string means
+	 * (correct.c:32) unless q > 93 -- then a batch that mixes both kinds of record takes the host instance, read by read */
+	uint8_t *q_all = has_qual ? qual : 0;
+	if (n == 0) return;
+	if (q_all && any_noq && opt->q > 93) {
+		uint64_t hist[256], high[64];
+		const int mode = bfc_ch_hist(g->ch, hist, high);
+		for (r = 0; r < n; ++r) {
+			uint8_t *s = seq + off[r], *q = qual + off[r];
+			const uint64_t l = off[r + 1] - off[r] - 1;
+			const uint8_t sep_s = s[l], sep_q = q[l];
+			char *rq = ri[idx ? idx[r] : r].has_qual ? (char*)q : 0;
+			s[l] = 0; q[l] = 0;
+			if (oaux) bfcg_ec1_host_refine(g->ch, opt, mode, (char*)s, rq, oaux[r], oaux2[r], &aux[r], &aux2[r]);
+			else bfcg_ec1_host(g->ch, opt, mode, (char*)s, rq, &aux[r], &aux2[r]);
+			s[l] = sep_s; q[l] = sep_q;
+		}
+		g->n_host += n;
+	} else if (g->n_dev == 1) {
+		if (ec_run(g->ecs[0], seq, q_all, n_pos, off, n, oaux, oaux2, aux, aux2) != 0) {
+			fprintf(stderr, "[E::%s] GPU error correction failed: %s\n", "bfc_correct", bfcg_last_error()); abort();
+		}
+		g->gpu_ms += bfcg_ec_last_ms(g->ecs[0]);
+	} else { /* as the trim pass: device d takes the reads up to the boundary nearest to d+1 N-ths of the batch's positions */
+		ec_job_t job[64];
+		pthread_t th[64];
+		uint64_t o2 = 0, r1 = 0;
+		for (d = 0; d < g->n_dev; ++d) {
+			const uint64_t r0 = r1, want = d + 1 == g->n_dev ? n_pos : n_pos / (uint64_t)g->n_dev * (uint64_t)(d + 1);
+			uint64_t q;
+			if (d + 1 == g->n_dev) r1 = n;
+			else {
+				uint64_t lo = r0, hi = n;
+				while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (off[mid] < want) lo = mid + 1; else hi = mid; }
+				r1 = lo;
+				if (r1 > r0 && off[r1] - want > want - off[r1 - 1]) --r1;
+			}
+			job[d].e = g->ecs[d]; job[d].seq = seq + off[r0]; job[d].qual = q_all ? q_all + off[r0] : 0; job[d].n_pos = off[r1] - off[r0];
+			job[d].n = r1 - r0; job[d].off = g->off2 + o2; job[d].aux = aux + r0; job[d].aux2 = aux2 + r0; job[d].rc = 0;
+			job[d].oaux = oaux ? oaux + r0 : 0; job[d].oaux2 = oaux2 ? oaux2 + r0 : 0;
+			for (q = r0; q <= r1; ++q) g->off2[o2++] = off[q] - off[r0];
+			pthread_create(&th[d], 0, ec_worker, &job[d]);
+		}
+		for (d = 0; d < g->n_dev; ++d) {
+			pthread_join(th[d], 0);
+			if (job[d].rc != 0) { fprintf(stderr, "[E::%s] GPU error correction failed on device %d: %s\n", "bfc_correct", g->devs[d], job[d].err); abort(); }
+		}
+	}
 }
 
 static void correct_gpu(const char *fn, const bfc_opt_t *opt, const bfc_ch_t *ch)
 {
 	parser_t ps;
 	batch_t b;
-	bfcg_ec_t *ecs[64];
-	int devs[64], n_dev, d, empties = 0;
-	uint64_t cap, max_reads, *off, *off2 = 0, n_total = 0, n_host = 0;
+	ec_devs_t g;
+	int d, empties = 0;
+	uint64_t cap, max_reads, *off, n_total = 0, n_refined = 0, n_kept = 0;
 	uint32_t *aux, *aux2;
 	rinfo_t *ri;
 	char *hdrs = 0; size_t m_hdrs = 0;
 	const char *env;
-	double t0 = (&bfc_real_time && bfc_real_time > 0.) ? bfc_real_time : t_real(), gpu_ms = 0.;
+	double t0 = (&bfc_real_time && bfc_real_time > 0.) ? bfc_real_time : t_real();
+	/* refinement: the sub-batch of the reads to correct (stream, offsets, their reads in the batch, earlier stats, results), kept reads */
+	uint8_t *r_seq = 0, *r_qual = 0, *kept = 0;
+	uint64_t *r_off = 0, *r_idx = 0;
+	uint32_t *r_oaux = 0, *r_oaux2 = 0, *r_aux = 0, *r_aux2 = 0, ori_aux = 0, ori_aux2 = 0; /* ori_st: calloc'd (correct.c:185) */
 
 	if (!(&bfc_verbose) || bfc_verbose >= 3)
 		fprintf(stderr, "[M::%s @%.1f*%.1f%%] Starting...\n", "bfc_correct", t_real() - t0, 100. * t_cpu() / (t_real() - t0 + 1e-6));
+	memset(&g, 0, sizeof(g));
+	g.opt = opt; g.ch = ch;
 	cap = (uint64_t)(opt->chunk_size > 0 ? opt->chunk_size : 100000000);
 	if ((env = getenv("BFC_GPU_BATCH")) != 0) cap = strtoull(env, 0, 10);
 	if (cap < (1u << 16)) cap = 1u << 16;
 	cap += cap / 64 + (1u << 20);
 	max_reads = cap / 16 + 1024;
-	n_dev = bfcg_env_devices(devs, 64);
-	if (n_dev == 0) { n_dev = 1; devs[0] = (env = getenv("BFC_GPU_DEVICE")) ? atoi(env) : 0; }
-	for (d = 0; d < n_dev; ++d) { /* a device's share of a batch: 1/N of its positions (cut at the nearest read boundary), up to all of its reads */
-		ecs[d] = bfcg_ec_create(ch, opt, devs[d], n_dev > 1 ? cap / (uint64_t)n_dev + cap / 64 + (1u << 16) : cap, max_reads);
-		if (!ecs[d]) { fprintf(stderr, "[E::%s] cannot set up error correction on the GPU: %s\n", "bfc_correct", bfcg_last_error()); abort(); }
+	g.n_dev = bfcg_env_devices(g.devs, 64);
+	if (g.n_dev == 0) { g.n_dev = 1; g.devs[0] = (env = getenv("BFC_GPU_DEVICE")) ? atoi(env) : 0; }
+	for (d = 0; d < g.n_dev; ++d) { /* a device's share of a batch: 1/N of its positions (cut at the nearest read boundary), up to all of its reads */
+		g.ecs[d] = bfcg_ec_create(ch, opt, g.devs[d], g.n_dev > 1 ? cap / (uint64_t)g.n_dev + cap / 64 + (1u << 16) : cap, max_reads);
+		if (!g.ecs[d]) { fprintf(stderr, "[E::%s] cannot set up error correction on the GPU: %s\n", "bfc_correct", bfcg_last_error()); abort(); }
 	}
-	if (n_dev > 1) off2 = (uint64_t*)malloc((max_reads + 1 + (uint64_t)n_dev) * 8);
+	if (g.n_dev > 1) g.off2 = (uint64_t*)malloc((max_reads + 1 + (uint64_t)g.n_dev) * 8);
 
 	memset(&ps, 0, sizeof(ps));
 	ps.keep_hdr = 1;
@@ -131,56 +231,43 @@ static void correct_gpu(const char *fn, const bfc_opt_t *opt, const bfc_ch_t *ch
 	off = (uint64_t*)malloc((max_reads + 1) * 8); aux = (uint32_t*)malloc(max_reads * 4); aux2 = (uint32_t*)malloc(max_reads * 4);
 	ri = (rinfo_t*)malloc(max_reads * sizeof(rinfo_t));
 	if (!b.seq || !b.qual || !off || !aux || !aux2 || !ri) { fprintf(stderr, "[E::%s] out of memory\n", "bfc_correct"); abort(); }
+	if (opt->refine_ec) {
+		r_seq = (uint8_t*)bfcg_host_alloc(cap); r_qual = (uint8_t*)bfcg_host_alloc(cap); kept = (uint8_t*)malloc(max_reads);
+		r_off = (uint64_t*)malloc((max_reads + 1) * 8); r_idx = (uint64_t*)malloc(max_reads * 8);
+		r_oaux = (uint32_t*)malloc(max_reads * 4); r_oaux2 = (uint32_t*)malloc(max_reads * 4);
+		r_aux = (uint32_t*)malloc(max_reads * 4); r_aux2 = (uint32_t*)malloc(max_reads * 4);
+		if (!r_seq || !r_qual || !kept || !r_off || !r_idx || !r_oaux || !r_oaux2 || !r_aux || !r_aux2) { fprintf(stderr, "[E::%s] out of memory\n", "bfc_correct"); abort(); }
+	}
 
-	for (;;) { /* one batch: parse (keep_comment = 0: comments are dropped, correct.c:580), correct on the GPU, print */
+	for (;;) { /* one batch: parse (keep_comment = refine_ec, correct.c:578-580), correct on the GPU, print */
 		uint64_t r, n = read_batch(&ps, &b, off, max_reads, ri, &hdrs, &m_hdrs);
 		int last = 0;
 		fprintf(stderr, "[M::%s] read %d sequences\n", "bfc_ec_cb", (int)n);
 		if (n == 0 && ++empties >= (opt->no_mt_io ? 1 : 2)) last = 1;
 		if (n) {
-			/* a record without a quality string has '~' in the stream (batch_put): q = (93 >= opt->q), which is what no quality string means
-			 * (correct.c:32) unless q > 93 -- then a batch that mixes both kinds of record takes the host instance, read by read */
-			uint8_t *qual = b.has_qual ? b.qual : 0;
-			if (qual && b.n_noq && opt->q > 93) {
-				uint64_t hist[256], high[64];
-				const int mode = bfc_ch_hist(ch, hist, high);
-				for (r = 0; r < n; ++r) {
-					uint8_t *s = b.seq + off[r], *q = b.qual + off[r];
-					const uint64_t l = off[r + 1] - off[r] - 1;
-					const uint8_t sep_s = s[l], sep_q = q[l];
-					s[l] = 0; q[l] = 0;
-					bfcg_ec1_host(ch, opt, mode, (char*)s, ri[r].has_qual ? (char*)q : 0, &aux[r], &aux2[r]);
-					s[l] = sep_s; q[l] = sep_q;
-				}
-				n_host += n;
-			} else if (n_dev == 1) {
-				if (bfcg_ec_batch(ecs[0], b.seq, qual, b.n_pos, off, n, aux, aux2) != 0) {
-					fprintf(stderr, "[E::%s] GPU error correction failed: %s\n", "bfc_correct", bfcg_last_error()); abort();
-				}
-				gpu_ms += bfcg_ec_last_ms(ecs[0]);
-			} else { /* as the trim pass: device d takes the reads up to the boundary nearest to d+1 N-ths of the batch's positions */
-				ec_job_t job[64];
-				pthread_t th[64];
-				uint64_t o2 = 0, r1 = 0;
-				for (d = 0; d < n_dev; ++d) {
-					const uint64_t r0 = r1, want = d + 1 == n_dev ? b.n_pos : b.n_pos / (uint64_t)n_dev * (uint64_t)(d + 1);
-					uint64_t q;
-					if (d + 1 == n_dev) r1 = n;
-					else {
-						uint64_t lo = r0, hi = n;
-						while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (off[mid] < want) lo = mid + 1; else hi = mid; }
-						r1 = lo;
-						if (r1 > r0 && off[r1] - want > want - off[r1 - 1]) --r1;
+			if (!opt->refine_ec) ec_correct(&g, b.seq, b.qual, b.has_qual, b.n_noq > 0, b.n_pos, off, n, ri, 0, 0, 0, aux, aux2);
+			else {
+				uint64_t m = 0, any_noq = 0;
+				r_off[0] = 0;
+				for (r = 0; r < n; ++r) { /* worker_ec, correct.c:542-550 */
+					const uint64_t l = off[r + 1] - off[r];
+					uint32_t a, a2;
+					kept[r] = 0;
+					if (ri[r].has_comment && bfcg_ec_parse_stats(hdrs + ri[r].off_cmt, &a, &a2)) {
+						ori_aux = a; ori_aux2 = a2;
+						if ((a & 7) == 0 && (a2 & 0xff) < 50) { kept[r] = 1; aux[r] = aux2[r] = 0; continue; }
 					}
-					job[d].e = ecs[d]; job[d].seq = b.seq + off[r0]; job[d].qual = qual ? qual + off[r0] : 0; job[d].n_pos = off[r1] - off[r0];
-					job[d].n = r1 - r0; job[d].off = off2 + o2; job[d].aux = aux + r0; job[d].aux2 = aux2 + r0; job[d].rc = 0;
-					for (q = r0; q <= r1; ++q) off2[o2++] = off[q] - off[r0];
-					pthread_create(&th[d], 0, ec_worker, &job[d]);
+					memcpy(r_seq + r_off[m], b.seq + off[r], l); memcpy(r_qual + r_off[m], b.qual + off[r], l);
+					r_idx[m] = r; r_oaux[m] = ori_aux; r_oaux2[m] = ori_aux2; any_noq |= !ri[r].has_qual;
+					r_off[m + 1] = r_off[m] + l; ++m;
 				}
-				for (d = 0; d < n_dev; ++d) {
-					pthread_join(th[d], 0);
-					if (job[d].rc != 0) { fprintf(stderr, "[E::%s] GPU error correction failed on device %d: %s\n", "bfc_correct", devs[d], job[d].err); abort(); }
+				ec_correct(&g, r_seq, r_qual, b.has_qual, any_noq != 0, r_off[m], r_off, m, ri, r_idx, r_oaux, r_oaux2, r_aux, r_aux2);
+				for (r = 0; r < m; ++r) { /* the results back into the batch */
+					const uint64_t i = r_idx[r], l = off[i + 1] - off[i] - 1;
+					memcpy(b.seq + off[i], r_seq + r_off[r], l); memcpy(b.qual + off[i], r_qual + r_off[r], l);
+					aux[i] = r_aux[r]; aux2[i] = r_aux2[r];
 				}
+				n_refined += m; n_kept += n - m;
 			}
 			fprintf(stderr, "[M::%s @%.1f*%.1f%%] processed %d sequences\n", "bfc_ec_cb", t_real() - t0, 100. * t_cpu() / (t_real() - t0 + 1e-6), (int)n);
 			for (r = 0; r < n; ++r) { /* correct.c:595-604, 609-611 */
@@ -189,9 +276,12 @@ static void correct_gpu(const char *fn, const bfc_opt_t *opt, const bfc_ch_t *ch
 				if (opt->discard && (aux[r] & 7)) continue;
 				putchar(is_fq ? '@' : '>');
 				fputs(hdrs + ri[r].off_hdr, stdout);
-				printf("\tec:Z:%d", aux[r] & 7);
-				if ((aux[r] & 7) == 0)
-					printf("_%d:%d_%d_%d:%d_%d", aux2[r] >> 10, aux2[r] & 0xff, aux[r] >> 3 & 1, aux[r] >> 18 & 0x3fff, aux[r] >> 4 & 0x3fff, aux2[r] >> 8 & 3);
+				if (kept && kept[r]) { putchar('\t'); fputs(hdrs + ri[r].off_cmt, stdout); } /* the comment worker_ec left (correct.c:604) */
+				else {
+					printf("\tec:Z:%d", aux[r] & 7);
+					if ((aux[r] & 7) == 0)
+						printf("_%d:%d_%d_%d:%d_%d", aux2[r] >> 10, aux2[r] & 0xff, aux[r] >> 3 & 1, aux[r] >> 18 & 0x3fff, aux[r] >> 4 & 0x3fff, aux2[r] >> 8 & 3);
+				}
 				putchar('\n');
 				fwrite(b.seq + off[r], 1, (size_t)l, stdout); putchar('\n');
 				if (is_fq) { puts("+"); fwrite(b.qual + off[r], 1, (size_t)l, stdout); putchar('\n'); }
@@ -200,13 +290,18 @@ static void correct_gpu(const char *fn, const bfc_opt_t *opt, const bfc_ch_t *ch
 		}
 		if (last) break;
 	}
-	for (d = 0; d < n_dev; ++d) { n_host += bfcg_ec_host_reads(ecs[d]); bfcg_ec_destroy(ecs[d]); }
-	fprintf(stderr, "[M::%s] error correction ran on the GPU (%d device(s), %.1f ms of kernels): %llu reads, %llu of them by the host fallback\n",
-	        "bfc_correct", n_dev, gpu_ms, (unsigned long long)n_total, (unsigned long long)n_host);
-	free(off2);
+	for (d = 0; d < g.n_dev; ++d) { g.n_host += bfcg_ec_host_reads(g.ecs[d]); bfcg_ec_destroy(g.ecs[d]); }
+	fprintf(stderr, "[M::%s] error correction ran on the GPU (%d device(s), %.1f ms of kernels): %llu reads, %llu of them by the host fallback",
+	        "bfc_correct", g.n_dev, g.gpu_ms, (unsigned long long)n_total, (unsigned long long)g.n_host);
+	if (opt->refine_ec) fprintf(stderr, "; -R: %llu reads refined, %llu skipped", (unsigned long long)n_refined, (unsigned long long)n_kept);
+	fputc('\n', stderr);
+	free(g.off2);
 	gzclose(ps.rd.fp);
 	free(ps.rd.buf); free(ps.rd.line); free(ps.seq); free(ps.qual); free(ps.hdr); free(ps.cmt);
 	bfcg_host_free(b.seq); bfcg_host_free(b.qual); free(b.kind_cut); free(off); free(aux); free(aux2); free(ri); free(hdrs);
+	if (r_seq) bfcg_host_free(r_seq);
+	if (r_qual) bfcg_host_free(r_qual);
+	free(kept); free(r_off); free(r_idx); free(r_oaux); free(r_oaux2); free(r_aux); free(r_aux2);
 }
 
 void bfc_correct(const char *fn, const bfc_opt_t *opt, const void *ptr)
@@ -224,10 +319,9 @@ void bfc_correct(const char *fn, const bfc_opt_t *opt, const void *ptr)
 	double t0 = (&bfc_real_time && bfc_real_time > 0.) ? bfc_real_time : t_real();
 
 	if (!opt->filter_mode) {
-		if (!opt->refine_ec && (((env = getenv("BFC_GPU_EC")) != 0 && strcmp(env, "1") == 0) || !bfc_correct_cpu)) { correct_gpu(fn, opt, (const bfc_ch_t*)ptr); return; }
-		if (bfc_correct_cpu) { bfc_correct_cpu(fn, opt, ptr); return; }
-		fprintf(stderr, "[E::%s] `-R` (refine_ec) is the reference's correct.c: link it as bfc_correct_cpu (INTEGRATION.md)\n", __func__);
-		abort();
+		if (((env = getenv("BFC_GPU_EC")) != 0 && strcmp(env, "1") == 0) || !bfc_correct_cpu) correct_gpu(fn, opt, (const bfc_ch_t*)ptr);
+		else bfc_correct_cpu(fn, opt, ptr);
+		return;
 	}
 	if (!(&bfc_verbose) || bfc_verbose >= 3)
 		fprintf(stderr, "[M::%s @%.1f*%.1f%%] Starting...\n", __func__, t_real() - t0, 100. * t_cpu() / (t_real() - t0 + 1e-6));

@@ -6,6 +6,11 @@
 // the two directions' results (lmax bytes each) live in a per-lane slice of a global workspace.  A read that would overflow either
 // array, or is longer than lmax, is left untouched with aux2 = BFCG_EC_FALLBACK and corrected after the batch by the host instance of
 // the same code (bfcg_ec1_host): the results do not depend on hcap / scap / lmax (BFCG_EC_HEAP / BFCG_EC_STACK / BFCG_EC_LMAX).
+//
+// Refinement (`bfc -R`: a corrector made with opt->refine_ec, bfcg_ec_batch_refine) runs the RF instances of the same code.  Its bases
+// may come from the quality string (bfcg_ec1.h), so the coverage pass gets a decoded copy of the stream (k_decode writes it into the
+// bfcg_kcov_t's input buffer) and k_ec<true> corrects the original bytes in a buffer of their own: a read it leaves alone comes back as
+// it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -47,20 +52,21 @@ struct HostLookup {
 	int operator()(uint64_t y0, uint64_t y1) const { const uint64_t y[2] = {y0, y1}; return bfc_ch_get(ch, y); }
 };
 
-// one read of n bases; the heap and stack grow until the read fits
-static void host_ec1(const bfc_ch_t *ch, const Opt &o, uint8_t *seq, uint8_t *qual, int n, uint32_t *aux, uint32_t *aux2)
+// one read of n bases; the heap and stack grow until the read fits.  ori: the read's earlier stats (RF only)
+template <bool RF>
+static void host_ec1(const bfc_ch_t *ch, const Opt &o, uint8_t *seq, uint8_t *qual, int n, Result ori, uint32_t *aux, uint32_t *aux2)
 {
 	const HostLookup lk = {ch};
 	uint16_t *cov = (uint16_t *)malloc((size_t)(n > 0 ? n : 1) * 2);
 	uint8_t *ecb = (uint8_t *)malloc((size_t)(n > 0 ? n : 1) * 2);
-	kcov(o, seq, n, lk, cov);
+	kcov<RF>(o, seq, qual, n, lk, cov);
 	Result res;
 	for (int hcap = 64, scap = 4 * n + 256;; hcap *= 4, scap *= 4) {
 		Work w;
 		w.hcap = hcap; w.scap = scap;
 		w.heap = (Heap1 *)malloc(sizeof(Heap1) * (size_t)hcap); w.stack = (Stack1 *)malloc(sizeof(Stack1) * (size_t)scap);
 		if (!w.heap || !w.stack) { fprintf(stderr, "[E::bfcg_ec1_host] out of memory\n"); abort(); }
-		const int rc = ec1(o, seq, qual, cov, n, lk, w, ecb, ecb + n, &res);
+		const int rc = ec1<RF>(o, seq, qual, cov, n, lk, w, ecb, ecb + n, &res, ori);
 		free(w.heap); free(w.stack);
 		if (rc == EC_OK) break;
 	}
@@ -71,8 +77,19 @@ static void host_ec1(const bfc_ch_t *ch, const Opt &o, uint8_t *seq, uint8_t *qu
 extern "C" int bfcg_ec1_host(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t *aux, uint32_t *aux2)
 {
 	if (!ch || !opt || !seq || opt->k != bfc_ch_get_k(ch)) return ec_err("bad arguments to bfcg_ec1_host");
+	if (opt->refine_ec) return ec_err("bfcg_ec1_host: refine_ec is set (bfcg_ec1_host_refine corrects with a read's earlier stats)");
 	const Opt o = ec_opt(opt, mode);
-	host_ec1(ch, o, (uint8_t *)seq, (uint8_t *)qual, (int)strlen(seq), aux, aux2);
+	host_ec1<false>(ch, o, (uint8_t *)seq, (uint8_t *)qual, (int)strlen(seq), Result(), aux, aux2);
+	return 0;
+}
+
+extern "C" int bfcg_ec1_host_refine(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t ori_aux, uint32_t ori_aux2,
+                                    uint32_t *aux, uint32_t *aux2)
+{
+	if (!ch || !opt || !seq || opt->k != bfc_ch_get_k(ch)) return ec_err("bad arguments to bfcg_ec1_host_refine");
+	const Opt o = ec_opt(opt, mode);
+	Result ori; ori.aux = ori_aux; ori.aux2 = ori_aux2;
+	host_ec1<true>(ch, o, (uint8_t *)seq, (uint8_t *)qual, (int)strlen(seq), ori, aux, aux2);
 	return 0;
 }
 
@@ -87,11 +104,13 @@ struct DevLookup {
 
 enum { EC_BT = 256 };
 
-// ctr[0]: next read; ctr[1]: table lookups; ctr[2]: reads left to the host
+// ctr[0]: next read; ctr[1]: table lookups; ctr[2]: reads left to the host.  ori_aux / ori_aux2: the reads' earlier stats (RF only)
+template <bool RF>
 __global__ __launch_bounds__(EC_BT) void k_ec(Opt o, int l_pre, int cshift, const unsigned long long *__restrict__ tab, uint8_t *seq, uint8_t *qual,
                                               const uint16_t *__restrict__ cov, const uint64_t *__restrict__ off, uint64_t n_reads,
                                               uint32_t *__restrict__ aux, uint32_t *__restrict__ aux2, Heap1 *heap_ws, Stack1 *stack_ws, uint8_t *ec_ws,
-                                              int hcap, int scap, int lmax, unsigned long long *ctr)
+                                              int hcap, int scap, int lmax, unsigned long long *ctr,
+                                              const uint32_t *__restrict__ ori_aux, const uint32_t *__restrict__ ori_aux2)
 {
 	const uint64_t lane = (uint64_t)blockIdx.x * EC_BT + threadIdx.x;
 	unsigned n_look = 0, n_host = 0;
@@ -104,14 +123,27 @@ __global__ __launch_bounds__(EC_BT) void k_ec(Opt o, int l_pre, int cshift, cons
 		if (r >= n_reads) break;
 		const uint64_t a = off[r];
 		const int n = (int)(off[r + 1] - a - 1);
-		Result res;
-		if (n > lmax || ec1(o, seq + a, qual ? qual + a : nullptr, cov + a, n, lk, w, ec0, ec1b, &res) != EC_OK) {
+		Result res, ori;
+		if (RF) { ori.aux = ori_aux[r]; ori.aux2 = ori_aux2[r]; }
+		if (n > lmax || ec1<RF>(o, seq + a, qual ? qual + a : nullptr, cov + a, n, lk, w, ec0, ec1b, &res, ori) != EC_OK) {
 			res.aux = 0; res.aux2 = BFCG_EC_FALLBACK; ++n_host;
 		}
 		aux[r] = res.aux; aux2[r] = res.aux2;
 	}
 	atomicAdd(&ctr[1], (unsigned long long)n_look);
 	if (n_host) atomicAdd(&ctr[2], (unsigned long long)n_host);
+}
+
+// the bases refinement reads (base_at<true>) as sequence bytes, for the coverage pass: one wavefront per read, separators copied as they are
+enum { DEC_BT = 256, DEC_W = 64 };
+__global__ __launch_bounds__(DEC_BT) void k_decode(const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual, const uint64_t *__restrict__ off,
+                                                   uint64_t n_reads, uint8_t *__restrict__ out)
+{
+	const uint64_t r = (uint64_t)blockIdx.x * (DEC_BT / DEC_W) + threadIdx.x / DEC_W;
+	if (r >= n_reads) return;
+	const uint64_t a = off[r], e = off[r + 1] - 1;                // [a, e): the read's bases; e: its separator
+	for (uint64_t p = a + threadIdx.x % DEC_W; p <= e; p += DEC_W)
+		out[p] = p == e ? seq[p] : (uint8_t)"ACGTN"[base_at<true>(seq + a, qual ? qual + a : nullptr, (int)(p - a))];
 }
 
 struct bfcg_ec {
@@ -127,6 +159,9 @@ struct bfcg_ec {
 	uint8_t *d_qual, *d_ec;
 	uint64_t *d_off;
 	uint32_t *d_aux, *d_aux2;
+	int refine;
+	uint8_t *d_oseq;                                           // refinement: the original bytes k_ec<true> rewrites
+	uint32_t *d_oaux, *d_oaux2;                                // refinement: the reads' earlier stats
 	Heap1 *d_heap;
 	Stack1 *d_stack;
 	unsigned long long *d_ctr;
@@ -147,6 +182,7 @@ extern "C" void bfcg_ec_destroy(bfcg_ec_t *e)
 	if (e->st) { (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->st); }
 	(void)hipFree(e->d_qual); (void)hipFree(e->d_ec); (void)hipFree(e->d_off); (void)hipFree(e->d_aux); (void)hipFree(e->d_aux2);
 	(void)hipFree(e->d_heap); (void)hipFree(e->d_stack); (void)hipFree(e->d_ctr);
+	(void)hipFree(e->d_oseq); (void)hipFree(e->d_oaux); (void)hipFree(e->d_oaux2);
 	if (e->st) { (void)hipEventDestroy(e->e0); (void)hipEventDestroy(e->e1); (void)hipStreamDestroy(e->st); }
 	bfcg_kcov_destroy(e->kc);
 	free(e);
@@ -156,8 +192,8 @@ extern "C" void bfcg_ec_destroy(bfcg_ec_t *e)
 
 extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, int device, uint64_t max_pos, uint64_t max_reads)
 {
-	if (!ch || !opt || opt->k != bfc_ch_get_k(ch) || max_pos == 0 || max_reads == 0 || opt->filter_mode || opt->refine_ec) {
-		ec_err("bad arguments to bfcg_ec_create (a table-mode bfc_opt_t whose k is the table's, without refine_ec)");
+	if (!ch || !opt || opt->k != bfc_ch_get_k(ch) || max_pos == 0 || max_reads == 0 || opt->filter_mode) {
+		ec_err("bad arguments to bfcg_ec_create (a table-mode bfc_opt_t whose k is the table's)");
 		return NULL;
 	}
 	bfcg_ec_t *e = (bfcg_ec_t *)calloc(1, sizeof(bfcg_ec_t));
@@ -166,6 +202,7 @@ extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, i
 	uint64_t hist[256], hist_high[64];
 	e->ch = ch;
 	e->o = ec_opt(opt, bfc_ch_hist(ch, hist, hist_high));        // correct.c:627
+	e->refine = opt->refine_ec != 0;
 	e->tab = bfcg::kcov_table(e->kc, &e->P, &e->device);
 	e->max_pos = max_pos; e->max_reads = max_reads;
 	e->hcap = env_int("BFCG_EC_HEAP", 16, 1, 1 << 16);
@@ -184,38 +221,67 @@ extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, i
 	ECN(hipMalloc(&e->d_stack, sizeof(Stack1) * e->lanes * (uint64_t)e->scap));
 	ECN(hipMalloc(&e->d_ec, e->lanes * 2 * (uint64_t)e->lmax));
 	ECN(hipMalloc(&e->d_ctr, 3 * sizeof(unsigned long long)));
+	if (e->refine) {
+		ECN(hipMalloc(&e->d_oseq, max_pos));
+		ECN(hipMalloc(&e->d_oaux, max_reads * 4)); ECN(hipMalloc(&e->d_oaux2, max_reads * 4));
+	}
 	return e;
 }
 
-// seq / qual: host streams of n_pos positions in the batch format of PART 2 (qual NULL: no read has a quality string); rewritten in place
-extern "C" int bfcg_ec_batch(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, uint32_t *aux, uint32_t *aux2)
+// seq / qual: host streams of n_pos positions in the batch format of PART 2 (qual NULL: no read has a quality string); rewritten in place.
+// ori_aux / ori_aux2: NULL for table mode, the reads' earlier stats for refinement.
+static int ec_batch(bfcg_ec_t *e, const char *fn, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads,
+                    const uint32_t *ori_aux, const uint32_t *ori_aux2, uint32_t *aux, uint32_t *aux2)
 {
-	if (!e || !seq || !off || !aux || !aux2) return ec_err("bad arguments to bfcg_ec_batch");
+	const int rf = ori_aux != nullptr;
+	if (!e || !seq || !off || !aux || !aux2 || (rf && !ori_aux2)) return ec_err("bad arguments to %s", fn);
+	if (rf != e->refine)
+		return ec_err(rf ? "%s: the corrector was made without refine_ec (bfcg_ec_batch corrects in table mode)"
+		                 : "%s: the corrector was made with refine_ec (bfcg_ec_batch_refine takes the reads' earlier stats)", fn);
 	if (n_pos > e->max_pos || n_reads > e->max_reads) return ec_err("correction batch exceeds the capacity given to bfcg_ec_create");
-	if (n_reads && off[n_reads] != n_pos) return ec_err("bfcg_ec_batch: off[n_reads] must be n_pos");
+	if (n_reads && off[n_reads] != n_pos) return ec_err("%s: off[n_reads] must be n_pos", fn);
 	e->last_ms = 0; e->last_lookups = 0; e->last_host = 0;
 	if (n_reads == 0) return 0;
 	for (uint64_t r = 0; r < n_reads; ++r)                       // every read ends in its separator inside the batch
-		if (off[r + 1] <= off[r]) return ec_err("bfcg_ec_batch: read %llu has no separator", (unsigned long long)r);
+		if (off[r + 1] <= off[r]) return ec_err("%s: read %llu has no separator", fn, (unsigned long long)r);
 	uint8_t *d_seq = (uint8_t *)bfcg_kcov_dev_seq(e->kc);
 	const uint16_t *d_cov = (const uint16_t *)bfcg_kcov_dev_out(e->kc);
+	uint8_t *d_ec_seq = rf ? e->d_oseq : d_seq;                   // the bytes k_ec rewrites
+	float ms_dec = 0;
 	ECK(hipSetDevice(e->device));
-	ECK(hipMemcpy(d_seq, seq, n_pos, hipMemcpyHostToDevice));
+	if (!rf) ECK(hipMemcpy(d_seq, seq, n_pos, hipMemcpyHostToDevice));
+	else {                                                       // the coverage pass sees the decoded bases (k_decode into its input buffer)
+		ECK(hipMemcpyAsync(e->d_oseq, seq, n_pos, hipMemcpyHostToDevice, e->st));
+		if (qual) ECK(hipMemcpyAsync(e->d_qual, qual, n_pos, hipMemcpyHostToDevice, e->st));
+		ECK(hipMemcpyAsync(e->d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice, e->st));
+		ECK(hipMemcpyAsync(e->d_oaux, ori_aux, n_reads * 4, hipMemcpyHostToDevice, e->st));
+		ECK(hipMemcpyAsync(e->d_oaux2, ori_aux2, n_reads * 4, hipMemcpyHostToDevice, e->st));
+		const uint64_t per = DEC_BT / DEC_W;
+		ECK(hipEventRecord(e->e0, e->st));
+		hipLaunchKernelGGL(k_decode, dim3((unsigned)((n_reads + per - 1) / per)), dim3(DEC_BT), 0, e->st, e->d_oseq, qual ? e->d_qual : nullptr,
+		                   (const uint64_t *)e->d_off, n_reads, d_seq);
+		ECK(hipGetLastError());
+		ECK(hipEventRecord(e->e1, e->st));
+		ECK(hipStreamSynchronize(e->st));                         // bfcg_kcov_batch runs on a stream of its own
+		ECK(hipEventElapsedTime(&ms_dec, e->e0, e->e1));
+	}
 	if (bfcg_kcov_batch(e->kc, nullptr, d_seq, n_pos, e->o.min_cov, nullptr) != 0) return -1;
-	const float ms_cov = bfcg_kcov_last_ms(e->kc);
-	if (qual) ECK(hipMemcpyAsync(e->d_qual, qual, n_pos, hipMemcpyHostToDevice, e->st));
-	ECK(hipMemcpyAsync(e->d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice, e->st));
+	const float ms_cov = bfcg_kcov_last_ms(e->kc) + ms_dec;
+	if (!rf) {
+		if (qual) ECK(hipMemcpyAsync(e->d_qual, qual, n_pos, hipMemcpyHostToDevice, e->st));
+		ECK(hipMemcpyAsync(e->d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice, e->st));
+	}
 	ECK(hipMemsetAsync(e->d_ctr, 0, 3 * sizeof(unsigned long long), e->st));
 	uint64_t lanes = (n_reads + EC_BT - 1) / EC_BT * EC_BT;
 	if (lanes > e->lanes) lanes = e->lanes;
 	ECK(hipEventRecord(e->e0, e->st));
-	hipLaunchKernelGGL(k_ec, dim3((unsigned)(lanes / EC_BT)), dim3(EC_BT), 0, e->st, e->o, e->P.l_pre, e->P.tab_cshift, e->tab, d_seq,
-	                   qual ? e->d_qual : nullptr, d_cov, (const uint64_t *)e->d_off, n_reads, e->d_aux, e->d_aux2, e->d_heap, e->d_stack, e->d_ec,
-	                   e->hcap, e->scap, e->lmax, e->d_ctr);
+	hipLaunchKernelGGL(rf ? k_ec<true> : k_ec<false>, dim3((unsigned)(lanes / EC_BT)), dim3(EC_BT), 0, e->st, e->o, e->P.l_pre, e->P.tab_cshift, e->tab,
+	                   d_ec_seq, qual ? e->d_qual : nullptr, d_cov, (const uint64_t *)e->d_off, n_reads, e->d_aux, e->d_aux2, e->d_heap, e->d_stack,
+	                   e->d_ec, e->hcap, e->scap, e->lmax, e->d_ctr, (const uint32_t *)e->d_oaux, (const uint32_t *)e->d_oaux2);
 	ECK(hipGetLastError());
 	ECK(hipEventRecord(e->e1, e->st));
 	unsigned long long ctr[3];
-	ECK(hipMemcpyAsync(seq, d_seq, n_pos, hipMemcpyDeviceToHost, e->st));
+	ECK(hipMemcpyAsync(seq, d_ec_seq, n_pos, hipMemcpyDeviceToHost, e->st));
 	if (qual) ECK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
 	ECK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
 	ECK(hipMemcpyAsync(aux2, e->d_aux2, n_reads * 4, hipMemcpyDeviceToHost, e->st));
@@ -228,11 +294,26 @@ extern "C" int bfcg_ec_batch(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t
 	for (uint64_t r = 0; r < n_reads; ++r) {                     // the reads the device left to the host instance
 		if (aux2[r] != BFCG_EC_FALLBACK) continue;
 		const uint64_t a = off[r];
-		host_ec1(e->ch, e->o, seq + a, qual ? qual + a : nullptr, (int)(off[r + 1] - a - 1), &aux[r], &aux2[r]);
+		uint8_t *s = seq + a, *q = qual ? qual + a : nullptr;
+		const int n = (int)(off[r + 1] - a - 1);
+		if (rf) { Result ori; ori.aux = ori_aux[r]; ori.aux2 = ori_aux2[r]; host_ec1<true>(e->ch, e->o, s, q, n, ori, &aux[r], &aux2[r]); }
+		else host_ec1<false>(e->ch, e->o, s, q, n, Result(), &aux[r], &aux2[r]);
 		++e->last_host;
 	}
 	e->host_reads += e->last_host;
 	return 0;
+}
+
+extern "C" int bfcg_ec_batch(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, uint32_t *aux, uint32_t *aux2)
+{
+	return ec_batch(e, "bfcg_ec_batch", seq, qual, n_pos, off, n_reads, nullptr, nullptr, aux, aux2);
+}
+
+extern "C" int bfcg_ec_batch_refine(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads,
+                                    const uint32_t *ori_aux, const uint32_t *ori_aux2, uint32_t *aux, uint32_t *aux2)
+{
+	if (!ori_aux) return ec_err("bad arguments to bfcg_ec_batch_refine");
+	return ec_batch(e, "bfcg_ec_batch_refine", seq, qual, n_pos, off, n_reads, ori_aux, ori_aux2, aux, aux2);
 }
 
 extern "C" float bfcg_ec_last_ms(bfcg_ec_t *e) { return e->last_ms; }

@@ -8,6 +8,14 @@
 // (lcov | hcov << 6 | solid_end << 12, bfcg_kcov_batch's format).  The one base the brute path may change (bfc_ec_greedy_k) is an
 // override (pos, base).
 //
+// Refinement (`bfc -R`, opt.refine_ec) is the template parameter RF of every function that reads a base: the table-mode instances are
+// the code they were before.  With RF a base comes from the quality string where bfc wrote it there (bfc_seq_conv's b_from_q,
+// correct.c:31): (signed char)qual - 33 <= 5 gives b = (qual - 34) & 7, every other position decodes its sequence byte as above.  Values
+// 5..7 come only from quality bytes <= 33 (e.g. '!'), which bfc never writes; the reference then indexes past "ACGTN" (correct.c:457,
+// undefined), here they are folded to 4 (N).  The read's earlier stats (worker_ec's ori_st, correct.c:543) come in as the (aux, aux2) pair
+// worker_ec packs, and end the correction as correct.c:438-442 / 470 do: rf_code 2 (the earlier stats, the read untouched) when they say
+// ec_code 0 with fewer absent k-mers than the new path, else rf_code 3 after a correction; the early exits keep rf_code 1.
+//
 // The search keeps the reference's data: a binary heap ordered by tot_pen with ksort's tie behaviour (pop: the last element to the
 // root and sift down, taking the right child only if the left one is "less"; push: append and sift up, stopping when the new element is
 // "less" than its parent; "less" = larger tot_pen) and a stack of extension steps linked by parent index.  A heap entry holds the two
@@ -29,7 +37,9 @@ namespace ec1k {
 enum { MAX_PATHS = 4, HIST = 5, HIST_HIGH = 2 };              // bfc.h:11-13
 enum { CODE_MISC = 1, CODE_MANY_N = 2, CODE_NO_SOLID = 3, CODE_UNCORR_N = 4, CODE_MANY_FAIL = 5 };
 enum { EC_OK = 0, EC_OVERFLOW = 1 };
-#define BFCG_EC_FALLBACK 0xffffffffu                              // aux2 of a read left to the host (rf_code 3 never occurs in table mode)
+// aux2 of a read left to the host.  No result can have it: it would be n_absent 2^22 - 1 with rf_code 3, but rf_code 3 only follows a
+// correction on the device, where a read has at most lmax <= 2^16 bases and so fewer absent k-mers; rf_code 2 sets bit 9 alone.
+#define BFCG_EC_FALLBACK 0xffffffffu
 
 struct Opt {                                                   // the bfc_opt_t fields the corrector reads, and the count table's mode
 	int k, q, max_end_ext, win_multi_ec, min_cov;
@@ -57,14 +67,24 @@ EC_HD int nt4(uint8_t c)                                       // seq_nt6_table 
 	return c >= 128 ? 4 : u == 'A' ? 0 : u == 'C' ? 1 : u == 'G' ? 2 : u == 'T' ? 3 : 4;
 }
 
+// base code of position p (bfc_seq_conv, correct.c:31); with RF, from the quality byte where bfc wrote one there
+template <bool RF> EC_HD int base_at(const uint8_t *seq, const uint8_t *qual, int p)
+{
+	if (RF && qual) {
+		const int q = (int)(signed char)qual[p] - 33;
+		if (q <= 5) { const int b = (q - 1) & 7; return b > 4 ? 4 : b; }
+	}
+	return nt4(seq[p]);
+}
+
 struct Base { int b, ob, q, lcov, hcov; };
 
 // position i of the read in orientation dir (1: the reverse complement of the whole read)
-EC_HD Base ec_base(const Opt &o, const Read &r, int dir, int i)
+template <bool RF> EC_HD Base ec_base(const Opt &o, const Read &r, int dir, int i)
 {
 	Base c;
 	const int p = dir ? r.n - 1 - i : i;
-	const int ob = nt4(r.seq[p]);
+	const int ob = base_at<RF>(r.seq, r.qual, p);
 	int b = p == r.brute_pos ? r.brute_b : ob;
 	c.q = ob > 3 ? 0 : !r.qual ? 1 : (int)(signed char)r.qual[p] - 33 >= o.q ? 1 : 0;
 	c.ob = dir && ob < 4 ? 3 - ob : ob;
@@ -106,12 +126,12 @@ template <class Lookup> EC_HD int occ(const Lookup &lk, int k, uint64_t x0, uint
 }
 
 // bfc_ec_kcov (correct.c:96-117) into packed words: the host instance's coverage (the device has k_occ / k_cov)
-template <class Lookup> EC_HD void kcov(const Opt &o, const uint8_t *seq, int n, const Lookup &lk, uint16_t *cov)
+template <bool RF, class Lookup> EC_HD void kcov(const Opt &o, const uint8_t *seq, const uint8_t *qual, int n, const Lookup &lk, uint16_t *cov)
 {
 	uint64_t x0 = 0, x1 = 0;
 	for (int i = 0; i < n; ++i) cov[i] = 0;
 	for (int i = 0, l = 0; i < n; ++i) {
-		const int c = nt4(seq[i]);
+		const int c = base_at<RF>(seq, qual, i);
 		if (c > 3) { l = 0; x0 = x1 = 0; continue; }
 		kmer_append(o.k, x0, x1, c);
 		if (++l < o.k) continue;
@@ -179,7 +199,7 @@ EC_HD int push(const Opt &o, Work &w, int &hn, int &sn, const Heap1 &z, int pen,
 // bfc_ec1dir (correct.c:249-386) in orientation dir from `start`; end is the read's length.  ec[i] (this orientation) gets the chosen
 // path's base or 4 where the read is not corrected.  *rv: n_absent of the path (>= 0), -2 (heap ran empty), -3 (too many failures),
 // -1 (no path).  Returns EC_OK or EC_OVERFLOW.
-template <class Lookup>
+template <bool RF, class Lookup>
 EC_HD int ec1dir(const Opt &o, const Read &r, int dir, int start, const Lookup &lk, Work &w, uint8_t *ec, int *max_heap, int *rv)
 {
 	const int n = r.n, end = n, k = o.k;
@@ -191,7 +211,7 @@ EC_HD int ec1dir(const Opt &o, const Read &r, int dir, int start, const Lookup &
 	for (int j = 0; j < HIST_HIGH; ++j) z.ecpos_high[j] = -1;
 	int l = 0;
 	for (z.i = start; z.i < end; ++z.i) {                      // the first k-1 bases of the first k-mer
-		const int c = ec_base(o, r, dir, z.i).b;
+		const int c = ec_base<RF>(o, r, dir, z.i).b;
 		if (c < 4) {
 			if (++l == k) break;
 			kmer_append(k, z.x0, z.x1, c);
@@ -210,7 +230,7 @@ EC_HD int ec1dir(const Opt &o, const Read &r, int dir, int start, const Lookup &
 		if (!stop) {
 			const int has_c = z.i < n;
 			Base c; c.b = 4; c.ob = 4; c.q = 0; c.lcov = c.hcov = 0;
-			if (has_c) c = ec_base(o, r, dir, z.i);
+			if (has_c) c = ec_base<RF>(o, r, dir, z.i);
 			int os = -1, fixed = 0, other_ext = 0, n_added = 0, added[4], added_b[4];
 			if (z.i > end) fixed = 1;
 			if (has_c && c.b < 4) {
@@ -263,7 +283,7 @@ EC_HD int ec1dir(const Opt &o, const Read &r, int dir, int start, const Lookup &
 			if (n_paths == MAX_PATHS) break;
 		}
 	}
-	for (int i = 0; i < n; ++i) ec[i] = (uint8_t)ec_base(o, r, dir, i).b;
+	for (int i = 0; i < n; ++i) ec[i] = (uint8_t)ec_base<RF>(o, r, dir, i).b;
 	if (n_paths == 0) return EC_OK;
 	int n_absent = 0;                                          // buf_backtrack (correct.c:235-247)
 	for (int e = path[min_path]; e >= 0; e = w.stack[e].parent) {
@@ -277,15 +297,16 @@ EC_HD int ec1dir(const Opt &o, const Read &r, int dir, int start, const Lookup &
 
 struct Result { uint32_t aux, aux2; };
 
-// bfc_ec1 (correct.c:388-476) and worker_ec's packing (correct.c:552-553).  seq / qual are rewritten in place when ec_code is 0.
-// ec0 / ec1 hold n bytes each.  Returns EC_OK or EC_OVERFLOW (nothing written then).
-template <class Lookup>
-EC_HD int ec1(const Opt &o, uint8_t *seq, uint8_t *qual, const uint16_t *cov, int n, const Lookup &lk, Work &w, uint8_t *ec0, uint8_t *ec1b, Result *res)
+// bfc_ec1 (correct.c:388-476) and worker_ec's packing (correct.c:552-553).  seq / qual are rewritten in place when ec_code is 0 (and,
+// with RF, the earlier stats `ori` do not keep the read).  ec0 / ec1 hold n bytes each.  Returns EC_OK or EC_OVERFLOW (nothing written then).
+template <bool RF, class Lookup>
+EC_HD int ec1(const Opt &o, uint8_t *seq, uint8_t *qual, const uint16_t *cov, int n, const Lookup &lk, Work &w, uint8_t *ec0, uint8_t *ec1b, Result *res,
+              Result ori)
 {
 	const int k = o.k;
 	int ec_code = CODE_MISC, brute = 0, n_ec = 0, n_ec_high = 0, n_absent = 0, mh = 0, n_n = 0, start = 0, end = 0;
 	Read r; r.seq = seq; r.qual = qual; r.cov = cov; r.n = n; r.brute_pos = r.brute_b = -1;
-	for (int i = 0; i < n; ++i) n_n += nt4(seq[i]) > 3;
+	for (int i = 0; i < n; ++i) n_n += base_at<RF>(seq, qual, i) > 3;
 	if (n_n > n * .05) { ec_code = CODE_MANY_N; goto done; }
 	{                                                          // bfc_ec_best_island (correct.c:119-130) on the coverage words
 		int l = 0, mx = 0, mx_i = -1, i;
@@ -301,7 +322,7 @@ EC_HD int ec1(const Opt &o, uint8_t *seq, uint8_t *qual, const uint16_t *cov, in
 				uint64_t x0 = 0, x1 = 0;
 				int ll = 0;
 				for (end = start; end < n; ++end) {
-					const int c = nt4(seq[end]);
+					const int c = base_at<RF>(seq, qual, end);
 					if (c < 4) { kmer_append(k, x0, x1, c); if (++ll == k) break; }
 					else ll = 0, x0 = x1 = 0;
 				}
@@ -333,15 +354,19 @@ EC_HD int ec1(const Opt &o, uint8_t *seq, uint8_t *qual, const uint16_t *cov, in
 	}
 	{
 		int rv0, rv1, mh0, mh1;
-		if (ec1dir(o, r, 0, start, lk, w, ec0, &mh0, &rv0) != EC_OK) return EC_OVERFLOW;
+		if (ec1dir<RF>(o, r, 0, start, lk, w, ec0, &mh0, &rv0) != EC_OK) return EC_OVERFLOW;
 		if (rv0 < 0) { ec_code = rv0 == -2 ? CODE_UNCORR_N : rv0 == -3 ? CODE_MANY_FAIL : CODE_MISC; goto done; }
-		if (ec1dir(o, r, 1, n - end, lk, w, ec1b, &mh1, &rv1) != EC_OK) return EC_OVERFLOW;
+		if (ec1dir<RF>(o, r, 1, n - end, lk, w, ec1b, &mh1, &rv1) != EC_OK) return EC_OVERFLOW;
 		if (rv1 < 0) { ec_code = rv1 == -2 ? CODE_UNCORR_N : rv1 == -3 ? CODE_MANY_FAIL : CODE_MISC; goto done; }
 		mh = mh0 > mh1 ? mh0 : mh1;
 		ec_code = 0; n_absent = rv0 + rv1;
 	}
-	for (int i = 0; i < n; ++i) {                              // merge the two directions, rewrite the read
-		const Base c = ec_base(o, r, 0, i);
+	if (RF && (ori.aux & 7) == 0 && (uint32_t)(n_absent & 0x3fffff) > ori.aux2 >> 10) { // correct.c:438-442: the earlier stats stand
+		res->aux = ori.aux; res->aux2 = (ori.aux2 & ~0x300u) | 2u << 8;
+		return EC_OK;
+	}
+	for (int i = 0; i < n; ++i) {                              // merge the two directions, rewrite the read (position i is read before it is written)
+		const Base c = ec_base<RF>(o, r, 0, i);
 		const int e0 = ec0[i], t = ec1b[n - 1 - i], e1 = t < 4 ? 3 - t : 4;
 		const int b = e0 == e1 ? (e0 > 3 ? c.b : e0) : e1 > 3 ? e0 : e0 > 3 ? e1 : c.ob;
 		const int diff = b != c.ob;
@@ -352,6 +377,7 @@ EC_HD int ec1(const Opt &o, uint8_t *seq, uint8_t *qual, const uint16_t *cov, in
 done:
 	res->aux = (uint32_t)(n_ec & 0x3fff) << 18 | (uint32_t)(n_ec_high & 0x3fff) << 4 | (uint32_t)brute << 3 | (uint32_t)ec_code;
 	res->aux2 = (uint32_t)(n_absent & 0x3fffff) << 10 | (uint32_t)(mh & 0xff);
+	if (RF) res->aux2 |= (ec_code == 0 ? 3u : 1u) << 8;        // rf_code: 3 after a correction (correct.c:470), else bfc_ec1's initial 1
 	return EC_OK;
 }
 

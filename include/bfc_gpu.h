@@ -80,8 +80,8 @@ void *bfc_count(const char *fn, const bfc_opt_t *opt);
  * (opt->filter_mode, ptr = the bfc_bf_t* bfc_count returned): bloom queries (bbf.c:47-63), longest streak
  * (correct.c:478-497) and the keep/trim rule (correct.c:557-569) run on the GPU, output as correct.c:595-611.
  * With filter_mode off it forwards to bfc_correct_cpu(), i.e. the reference's correct.c compiled with
- * -Dbfc_correct=bfc_correct_cpu.  Error correction (table mode, no refine_ec) runs on the GPU (bfcg_ec_*, PART 2)
- * when BFC_GPU_EC=1 is set or bfc_correct_cpu is not linked; otherwise it is bfc_correct_cpu's. */
+ * -Dbfc_correct=bfc_correct_cpu.  Error correction (table mode, with or without refine_ec, i.e. `-R`) runs on the GPU
+ * (bfcg_ec_*, PART 2) when BFC_GPU_EC=1 is set or bfc_correct_cpu is not linked; otherwise it is bfc_correct_cpu's. */
 void bfc_correct(const char *fn, const bfc_opt_t *opt, const void *ptr);
 
 /* ============================================================ PART 2: device-level API */
@@ -296,13 +296,24 @@ void *bfcg_kcov_dev_out(bfcg_kcov_t *t);   /* device result of the last batch (m
 
 /* BFC's error correction (bfc_ec1, correct.c:388-476) for whole batches of reads (bfcg_ec.hip): the k-mer coverage pass above, then one
  * read per lane of a persistent grid (bfcg_ec1.h: the per-read search, shared with the host).  Output is byte-identical to the reference's
- * worker_ec / bfc_ec_cb in table mode (opt->filter_mode and opt->refine_ec off) for any other option.  The table is uploaded once from
+ * worker_ec / bfc_ec_cb in table mode (opt->filter_mode off) for any other option, refine_ec included.  The table is uploaded once from
  * the host bfc_ch_t, which must outlive the object: reads the device cannot hold (heap or stack full, longer than its bound) are corrected
  * after the batch by the host instance, bfcg_ec1_host, on that table.  BFCG_EC_HEAP / BFCG_EC_STACK / BFCG_EC_LMAX set the device's heap
  * and stack entries and read length per lane (results do not depend on them).
  *   bfcg_ec_batch: the stream and off[] as bfcg_trim_batch (off[n_reads] = n_pos); qual NULL: no quality strings.  seq / qual are
  *   rewritten in place as bfc_ec1 does (reads with ec_code != 0 untouched); aux / aux2 as worker_ec packs them (correct.c:552-553).
- *   bfcg_ec1_host: one NUL-terminated read on the host; mode = bfc_ch_hist(ch, ...). */
+ *   bfcg_ec1_host: one NUL-terminated read on the host; mode = bfc_ch_hist(ch, ...).
+ * Refinement (`bfc -R`, opt->refine_ec set at bfcg_ec_create; bfcg_ec_batch then refuses the corrector): bases are read from the quality
+ * string where bfc wrote them there (bfc_seq_conv's b_from_q, correct.c:31; quality bytes <= 33 decode to N), and every read carries
+ * the stats of its earlier correction, ori_aux / ori_aux2, packed as aux / aux2 (worker_ec's ori_st, correct.c:542-546; all zero for a
+ * read that had none).  Each read given is corrected -- skipping the reads whose stats say so (ec_code 0, max_heap < 50) is the caller's
+ * job, as worker_ec returns before bfc_ec1.  aux2's rf_code (bits 8-9) is 3 for a corrected read, 2 where the earlier stats stand
+ * (correct.c:438-442: the read untouched, aux / aux2 = ori with rf_code 2), 1 where ec_code != 0.
+ *   bfcg_ec_batch_refine: bfcg_ec_batch with ori_aux[n_reads] / ori_aux2[n_reads].
+ *   bfcg_ec1_host_refine: bfcg_ec1_host with one read's earlier stats (bfcg_ec1_host refuses refine_ec).
+ *   bfcg_ec_parse_stats: worker_ec's test and parse_stats (correct.c:517-531, 542-543) on a read's comment: returns 1 and the stats
+ *   packed as above (rf_code 1, every field cut to ecstat_t's width as its bit-fields do: max_heap 300 is 44) if it starts with "ec:Z:",
+ *   else 0 (aux / aux2 untouched).  It never reads past the comment's NUL: fields missing at its end are 0, where the reference reads on. */
 typedef struct bfcg_ec bfcg_ec_t;
 bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, int device, uint64_t max_pos, uint64_t max_reads);
 int   bfcg_ec_batch(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, uint32_t *aux, uint32_t *aux2);
@@ -311,6 +322,11 @@ float bfcg_ec_last_ms(bfcg_ec_t *e);          /* GPU time of the last batch: cov
 uint64_t bfcg_ec_host_reads(bfcg_ec_t *e);    /* reads the host fallback corrected, since creation */
 uint64_t bfcg_ec_last_lookups(bfcg_ec_t *e);  /* table lookups of the last batch's correction kernel (the coverage pass adds one per k-mer) */
 int   bfcg_ec1_host(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t *aux, uint32_t *aux2);
+int   bfcg_ec_batch_refine(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads,
+                           const uint32_t *ori_aux, const uint32_t *ori_aux2, uint32_t *aux, uint32_t *aux2);
+int   bfcg_ec1_host_refine(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t ori_aux, uint32_t ori_aux2,
+                           uint32_t *aux, uint32_t *aux2);
+int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);
