@@ -140,6 +140,19 @@ SYMBOLS = {
     "bfcg_ec_batch_refine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, u32p, u32p, u32p, u32p]),
     "bfcg_ec1_host_refine": (C.c_int, [C.c_void_p, C.POINTER(BfcOpt), C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, u32p, u32p]),
     "bfcg_ec_parse_stats": (C.c_int, [C.c_char_p, u32p, u32p]),
+    "bfcg_kmers_create": (C.c_void_p, [C.c_void_p, C.c_int]),
+    "bfcg_kmers_attach": (C.c_void_p, [C.c_void_p]),
+    "bfcg_kmers_destroy": (None, [C.c_void_p]),
+    "bfcg_kmers_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "bfcg_kmers_hist": (C.c_int, [C.c_void_p, u64p, u64p]),
+    "bfcg_kmers_sub_sizes": (C.c_int, [C.c_void_p, u32p]),
+    "bfcg_kmers_hist_sizes": (C.c_int, [C.c_void_p, u64p, u64p, u32p]),
+    "bfcg_kmers_list": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "bfcg_kmers_last_ms": (C.c_float, [C.c_void_p]),
+    "bfcg_kmer_decode_host": (C.c_int, [C.c_int, C.c_int, C.c_uint32, C.c_uint64, u64p]),
+    "bfcg_kmer_2str": (None, [C.c_int, u64p, C.c_char_p]),
+    "bfcg_kmers_format": (C.c_uint64, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_kmers_format_sizes": (C.c_uint64, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "bfcg_hash_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_seen_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
 }

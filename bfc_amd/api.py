@@ -554,6 +554,119 @@ class GpuKcov:
         return self.L.bfcg_kcov_dev_seq(self.t)
 
 
+class GpuKmers:
+    """The count table read out on the GPU (bfcg_kmers_*): what the reference's hash2cnt prints from a dump -- the spectrum, the sub-table
+    sizes and the k-mers with their counts.  `table` is a HostTable (uploaded once) or a GpuCounter whose device table is read in place
+    (it must outlive this object and must not count meanwhile)."""
+
+    def __init__(self, table, device=0):
+        self.L = _lib.load()
+        self._keep = table
+        if isinstance(table, GpuCounter):
+            self.t = self.L.bfcg_kmers_attach(table.ctx)
+        else:
+            self.t = self.L.bfcg_kmers_create(table.ptr, device)
+        if not self.t:
+            raise BfcGpuError("bfcg_kmers_create failed: " + self.L.bfcg_last_error().decode())
+        info = (C.c_int * 3)()
+        self.L.bfcg_kmers_info(self.t, info)
+        self.k, self.l_pre, self.cshift = info[0], info[1], info[2]
+        self._ms = 0.0
+
+    def close(self):
+        if self.t:
+            self.L.bfcg_kmers_destroy(self.t)
+            self.t = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def hist(self):
+        """(mode, cnt[256], high[64]) as bfc_ch_hist (htab.c:110)."""
+        cnt, high = np.zeros(256, dtype=np.uint64), np.zeros(64, dtype=np.uint64)
+        mode = self.L.bfcg_kmers_hist(self.t, cnt.ctypes.data_as(u64p), high.ctypes.data_as(u64p))
+        if mode < -1:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return mode, cnt, high
+
+    def sub_sizes(self):
+        sizes = np.zeros(1 << self.l_pre, dtype=np.uint32)
+        if self.L.bfcg_kmers_sub_sizes(self.t, sizes.ctypes.data_as(u32p)) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return sizes
+
+    def hist_sizes(self):
+        """(mode, cnt[256], high[64], sizes) from ONE pass over the table: hist() and sub_sizes() stream it once each."""
+        cnt, high, sizes = np.zeros(256, dtype=np.uint64), np.zeros(64, dtype=np.uint64), np.zeros(1 << self.l_pre, dtype=np.uint32)
+        mode = self.L.bfcg_kmers_hist_sizes(self.t, cnt.ctypes.data_as(u64p), high.ctypes.data_as(u64p), sizes.ctypes.data_as(u32p))
+        if mode < -1:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return mode, cnt, high, sizes
+
+    MAX_SLOTS = 1 << 35  # of one bfcg_kmers_list call (it takes fewer than 2^36)
+
+    def list_raw(self, min_cnt, min_diff, sub_lo, sub_hi, cap):
+        """One bfcg_kmers_list call: (rc, n, y (cap, 2) u64, cnt_high u16 (cap))."""
+        y, ch = np.zeros((cap, 2), dtype=np.uint64), np.zeros(cap, dtype=np.uint16)
+        n = C.c_uint64()
+        rc = self.L.bfcg_kmers_list(self.t, int(min_cnt), int(min_diff), int(sub_lo), int(sub_hi), y.ctypes.data, ch.ctypes.data, cap, C.byref(n))
+        if rc < 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        return rc, int(n.value), y, ch
+
+    def pieces(self, min_cnt=0, min_diff=0, sub_lo=0, sub_hi=None, piece=1 << 24, sizes=None):
+        """The listing in pieces of about `piece` k-mers and MAX_SLOTS slots at most (whole sub-tables, ascending), sized from `sizes`
+        (what sub_sizes() or hist_sizes() returned; None: one pass to get them): yields (y (n, 2) u64, cnt_high (n) u16) per piece;
+        last_ms() then is the time of the pieces' kernels so far."""
+        sub_hi = (1 << self.l_pre) if sub_hi is None else sub_hi
+        if self.k > 37:  # fail before any work, with the library's message
+            self.list_raw(min_cnt, min_diff, sub_lo, sub_hi, 0)
+        ends = np.cumsum((self.sub_sizes() if sizes is None else sizes)[sub_lo:sub_hi], dtype=np.uint64)
+        max_subs = max(1, self.MAX_SLOTS >> self.cshift)
+        self._ms, lo, done = 0.0, sub_lo, 0
+        while lo < sub_hi:
+            hi = sub_lo + int(np.searchsorted(ends, done + piece, side="right"))
+            hi = min(max(hi, lo + 1), lo + max_subs, sub_hi)
+            cap = int(ends[hi - 1 - sub_lo]) - done
+            rc, n, y, ch = self.list_raw(min_cnt, min_diff, lo, hi, cap)
+            if rc != 0:
+                raise BfcGpuError("sub-tables [%d, %d) hold %d k-mers, their sizes said %d: the table changed under the listing" % (lo, hi, n, cap))
+            self._ms += float(self.L.bfcg_kmers_last_ms(self.t))
+            yield y[:n], ch[:n]
+            lo, done = hi, done + cap
+
+    def list(self, min_cnt=0, min_diff=0, sub_lo=0, sub_hi=None, piece=1 << 24):
+        """(y (n, 2) u64, count u8, high u8): the k-mers with count >= min_cnt and min(count, 63) - high >= min_diff, sub-tables ascending."""
+        parts = list(self.pieces(min_cnt, min_diff, sub_lo, sub_hi, piece))
+        y = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 2), dtype=np.uint64)
+        ch = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.uint16)
+        return y, (ch & 0xff).astype(np.uint8), (ch >> 8).astype(np.uint8)
+
+    def strings(self, y):
+        """The k-mers as a list of str (bfc_kmer_2str, kmer.h:97)."""
+        y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 2)
+        ch = np.zeros(len(y), dtype=np.uint16)
+        return [ln.split("\t")[0] for ln in self.format(y, ch).decode().splitlines()]
+
+    def format(self, y, cnt_high):
+        """hash2cnt's lines for a piece, formatted in C: bytes."""
+        y = np.ascontiguousarray(y, dtype=np.uint64)
+        cnt_high = np.ascontiguousarray(cnt_high, dtype=np.uint16)
+        buf = C.create_string_buffer(max(1, len(cnt_high) * (self.k + 8)))
+        n = self.L.bfcg_kmers_format(self.k, y.ctypes.data, cnt_high.ctypes.data, len(cnt_high), buf)
+        return buf.raw[:n]
+
+    def last_ms(self):
+        """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() one pass, list() all its pieces."""
+        return self._ms
+
+
 class GpuCorrector:
     """BFC's error correction (bfc_ec1, correct.c:388-476) for whole batches of reads on the GPU (bfcg_ec_*), with the host instance of the
     same code as a twin (bfcg_ec1_host).  `table` is a HostTable (bfc_count / bfc_ch_restore); it must outlive this object.  `opt` is a

@@ -1990,6 +1990,15 @@ extern "C" float bfcg_kcov_last_ms(bfcg_kcov_t *t) { return t->last_ms; }
 // the corrector (bfcg_ec.hip) runs behind a coverage context: its table in HBM, the probe parameters, the device it lives on
 namespace bfcg {
 const unsigned long long *kcov_table(bfcg_kcov_t *t, KParams *P, int *device) { *P = t->P; *device = t->device; return t->table; }
+// the table read-out (bfcg_kmers.hip) borrows a counting context's table as bfcg_kcov_attach does: drained, in the host's layout, not exported
+const unsigned long long *ctx_borrow_table(bfcg_ctx_t *c, KParams *P, int *device)
+{
+	if (!c || c->P.filter_mode) { set_err("bfcg_kmers_attach needs a table-mode context"); return NULL; }
+	if (drain(c) != 0) return NULL;
+	if (c->P.seg && seg_to_legacy(c) != 0) return NULL;
+	*P = c->P; *device = c->prm.device;
+	return c->B.table;
+}
 }
 extern "C" void *bfcg_kcov_dev_seq(bfcg_kcov_t *t) { return t->d_seq; }
 extern "C" void *bfcg_kcov_dev_out(bfcg_kcov_t *t) { return t->d_out; }

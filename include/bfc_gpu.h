@@ -328,6 +328,40 @@ int   bfcg_ec1_host_refine(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, c
                            uint32_t *aux, uint32_t *aux2);
 int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
 
+/* The count table read out where it lies in HBM (bfcg_kmers.hip): what the reference's hash2cnt (hash2cnt.c) prints from a dump.  The table
+ * is uploaded once from a host bfc_ch_t (bfcg_kmers_create) or borrowed in place from a table-mode counting context (bfcg_kmers_attach,
+ * with bfcg_kcov_attach's contract: the context is drained, nothing is exported, it must outlive the object and must not count meanwhile).
+ *   bfcg_kmers_info       out[0] k, out[1] l_pre (2^l_pre sub-tables), out[2] log2 slots per sub-table
+ *   bfcg_kmers_hist       bfc_ch_hist (htab.c:110) in one streaming pass: returns the mode (largest bin with i >= 3, -1 if none), -2 on error
+ *   bfcg_kmers_sub_sizes  sizes[2^l_pre]: the keys of every sub-table (hash2cnt -s)
+ *   bfcg_kmers_hist_sizes both from ONE pass (each of the two calls above streams the whole table and drops the other half of what the
+ *                         kernel computed: nothing is cached, because an attached table may change between calls); cnt / high together,
+ *                         or sizes, may be NULL; returns as bfcg_kmers_hist (-1 also when no histogram was asked for)
+ *   bfcg_kmers_list       the k-mers of sub-tables [sub_lo, sub_hi) with count >= min_cnt and min(count, 63) - high >= min_diff (hash2cnt's
+ *                         -m / -d): y[2 i], y[2 i + 1] = the two bit planes of k-mer i (bit l = the base l from the 3' end, low / high code
+ *                         bit, of the strand the hash chose), cnt_high[i] = high << 8 | count.  Sub-tables ascending, unordered inside one.
+ *                         0: *n k-mers written; 1: cap too small, nothing written, *n = the number needed; -1: error -- k > 37, whose
+ *                         keys do not hold the whole hash (hash2cnt.c:37; sizes and histogram work for every k)
+ *   bfcg_kmers_last_ms    GPU time of the last call's kernels (HIP events)
+ *   bfcg_kmer_decode_host one slot of sub-table `sub` decoded on the host by the same code (bfcg_kdec.h), checked against the forward
+ *                         hash; -1 for k > 37
+ *   bfcg_kmer_2str        the planes as text (k + 1 bytes), kmer.h:97
+ *   bfcg_kmers_format / _format_sizes   hash2cnt's lines "%s\t%d\t%d\n" (at most k + 8 bytes each) / "%d\n" (at most 11): bytes written */
+typedef struct bfcg_kmers bfcg_kmers_t;
+bfcg_kmers_t *bfcg_kmers_create(const bfc_ch_t *ch, int device);
+bfcg_kmers_t *bfcg_kmers_attach(bfcg_ctx_t *ctx);
+void  bfcg_kmers_destroy(bfcg_kmers_t *t);
+int   bfcg_kmers_info(bfcg_kmers_t *t, int out[3]);
+int   bfcg_kmers_hist(bfcg_kmers_t *t, uint64_t cnt[256], uint64_t high[64]);
+int   bfcg_kmers_sub_sizes(bfcg_kmers_t *t, uint32_t *sizes);
+int   bfcg_kmers_hist_sizes(bfcg_kmers_t *t, uint64_t cnt[256], uint64_t high[64], uint32_t *sizes);
+int   bfcg_kmers_list(bfcg_kmers_t *t, int min_cnt, int min_diff, uint32_t sub_lo, uint32_t sub_hi, uint64_t *y, uint16_t *cnt_high, uint64_t cap, uint64_t *n);
+float bfcg_kmers_last_ms(bfcg_kmers_t *t);
+int   bfcg_kmer_decode_host(int k, int l_pre, uint32_t sub, uint64_t slot, uint64_t y[2]);
+void  bfcg_kmer_2str(int k, const uint64_t y[2], char *buf);
+uint64_t bfcg_kmers_format(int k, const uint64_t *y, const uint16_t *cnt_high, uint64_t n, char *buf);
+uint64_t bfcg_kmers_format_sizes(const uint32_t *sizes, uint64_t n, char *buf);
+
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);
 /* per-position seen flags of the last batch (debug_seen): 0 none, 1 not seen, 2 seen */
