@@ -489,25 +489,29 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 
 namespace bfcg {
 
+// k_bloom3<threads, PF, COLD>, named in this selector alone.  PF = 4: 80 registers, three workgroups per CU at the 53 KB of LDS a full-size list takes; PF = 2: 47 registers, four per CU where the LDS
+// footprint allows it (a shorter list: bfcg_ctx.hip decides per batch)
+typedef void (*BloomFn)(KParams, BloomArgs);
+static BloomFn bloom3_kernel(bool pf2, bool cold)
+{
+	if (cold) return pf2 ? k_bloom3<512, 2, true> : k_bloom3<512, 4, true>;
+	return pf2 ? k_bloom3<512, 2, false> : k_bloom3<512, 4, false>;
+}
+static hipError_t set_bloom3_max_lds(BloomFn fn, int lds) { return hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds < BLOOM3_LDS_FLOOR ? BLOOM3_LDS_FLOOR : lds); }
 hipError_t set_bloom3_lds_attr(int lds)
 {
-	hipError_t e = hipFuncSetAttribute((const void *)k_bloom3<512, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-	if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_bloom3<512, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-	if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_bloom3<512, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-	if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_bloom3<512, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+	hipError_t e = hipSuccess;
+	for (int i = 0; i < 4 && e == hipSuccess; ++i) e = set_bloom3_max_lds(bloom3_kernel(i & 1, i & 2), lds);
 	return e;
 }
 
-// PF = 4: 80 registers, three workgroups per CU at the 53 KB of LDS a full-size list takes; PF = 2: 47 registers, four per CU where the LDS
-// footprint allows it (a shorter list: bfcg_ctx.hip decides per batch)
 void run_bloom3(const KParams &P, const BloomArgs &A, int nfine, size_t lds, hipStream_t st)
 {
 	static int pf = 0;
 	if (!pf) { const char *e = getenv("BFCG_B3_PF"); pf = e && atoi(e) == 2 ? 2 : e && atoi(e) == 4 ? 4 : 1; } // (1: by the batch)
-	if (P.b3_cold && P.b3_warm) hipLaunchKernelGGL((k_bloom3<512, 2, true>), dim3(nfine), dim3(512), lds, st, P, A); // (the walk for a warm batch: the short list, four workgroups per CU)
-	else if (P.b3_cold) hipLaunchKernelGGL((k_bloom3<512, 4, true>), dim3(nfine), dim3(512), lds, st, P, A);
-	else if (pf == 2 || (pf == 1 && P.b3_warm)) hipLaunchKernelGGL((k_bloom3<512, 2, false>), dim3(nfine), dim3(512), lds, st, P, A);
-	else hipLaunchKernelGGL((k_bloom3<512, 4, false>), dim3(nfine), dim3(512), lds, st, P, A);
+	// (the walk for a warm batch takes the short list, four workgroups per CU, and PF = 2 with it)
+	const bool pf2 = P.b3_cold ? P.b3_warm != 0 : pf == 2 || (pf == 1 && P.b3_warm);
+	hipLaunchKernelGGL(bloom3_kernel(pf2, P.b3_cold != 0), dim3(nfine), dim3(512), lds, st, P, A);
 }
 
 } // namespace bfcg
@@ -731,9 +735,10 @@ __global__ __launch_bounds__(BT, 6) void k_bloom3fm(KParams P, BloomArgs A)
 }
 
 namespace bfcg {
-hipError_t set_bloom3fm_lds_attr(int lds) { return hipFuncSetAttribute((const void *)k_bloom3fm<512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); }
+static const BloomFn bloom3fm_kernel = k_bloom3fm<512, 2>; // (the one variant, named here alone)
+hipError_t set_bloom3fm_lds_attr(int lds) { return set_bloom3_max_lds(bloom3fm_kernel, lds); }
 void run_bloom3fm(const KParams &P, const BloomArgs &A, int nfine, size_t lds, hipStream_t st)
 {
-	hipLaunchKernelGGL((k_bloom3fm<512, 2>), dim3(nfine), dim3(512), lds, st, P, A);
+	hipLaunchKernelGGL(bloom3fm_kernel, dim3(nfine), dim3(512), lds, st, P, A);
 }
 } // namespace bfcg

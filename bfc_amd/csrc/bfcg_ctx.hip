@@ -214,7 +214,7 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 			if (P.b3) rwb = 10;
 		}
 		const size_t second = prm->filter_mode ? region : P.seg ? 0 : (size_t)P.ag_cap * ((P.k > 32 ? 24 : 16) + (prm->track_order ? 8 : 0)); // second filter's slice, or the aggregation table
-		size_t budget = (size_t)53000;
+		size_t budget = (size_t)53000; // (BLOOM3_LDS_FLOOR in bfcg_dev.h is this number rounded up to 16: change them together)
 		if (region + second + 16 * 1024 > budget) budget = 80 * 1024 - 1024;
 		if (region + second + 16 * 1024 > budget) budget = 160 * 1024 - 1024;
 		if ((e = getenv("BFCG_LDS")) != 0 && (size_t)atoi(e) >= region + second + 4096 && (size_t)atoi(e) <= 160 * 1024 - 1024) budget = (size_t)atoi(e);

@@ -215,6 +215,7 @@ __device__ __forceinline__ uint32_t b3_bit(uint32_t w, uint32_t b) { return __bu
 
 namespace bfcg {
 // bfcg_bloom3.hip
+constexpr int BLOOM3_LDS_FLOOR = (53000 + 15) & ~15; // least LDS cap of k_bloom3 / k_bloom3fm: bfcg_create's first LDS `budget` (bfcg_ctx.hip: change them together), which a batch's list may lay out anew
 hipError_t set_bloom3_lds_attr(int lds);
 void run_bloom3(const KParams &P, const BloomArgs &A, int nfine, size_t lds, hipStream_t st);
 hipError_t set_bloom3fm_lds_attr(int lds);

@@ -2160,16 +2160,83 @@ static inline int grid_for(int64_t n_tiles, int cap) { return (int)(n_tiles < ca
 // faster -- the kernel's floor is its skeleton of LDS ranks, scan, staging and barriers, not the hashing: DESIGN.md section 6b.)
 // Round 5: 16-byte records take 3072 too -- with 2^10 level-1 buckets (config c5: k = 51, -b37) the stage of 4096 records, their bucket bytes and
 // the counters were 92 KiB: ONE workgroup per CU, 17 ps per k-mer against 8 for c3's 12-byte records; 3072 positions: 75 KiB, two per CU.
-template <int RW> struct S1 { static constexpr int BT = 512, TILE = RW == 3 ? 4096 : 3072; };
-static_assert(S1<3>::TILE == 4096 && S1<4>::TILE == 3072 && S1<5>::TILE == 3072, "bfcg_tile1_of_rw (bfcg_internal.h) sizes the host's buffers");
-#define TILE2 BFCG_TILE2
-#define BT2 512
+// The tile itself is bfcg_tile1_of_rw (bfcg_internal.h), which also sizes the host's buffers.
+#define BTS1 512
+#define BT2 512 // level 2: tiles of bfcg_tile_of_rw records
 // Round 6: level 2 at 2^10 regions per bucket (config c4's -b37).  A tile of 4096 records spread over 1024 regions leaves as runs of FOUR records --
 // 48 bytes, a sector and a half -- and the kernel that streams at 4.8-5.0 TB/s at c3's 2^9 regions (runs of eight = 96 bytes = three whole sectors) moved
 // c4e's records at 3.5 (profiles/round5_c4e.md: WRITE_SIZE 1.09 x the records, so the bytes were right and the rate was not).  Tiles of 8192 records
 // with 1024 threads restore the run length: 96 KiB of stage + 8 KiB of counters, one workgroup per CU.
 #define TILE2_BIG 8192
 #define BT2_BIG 1024
+
+// ---- The kernels that take dynamic LDS.  Each family has one selector, the only place that names its instantiations: a launch asks it for its
+// kernel and register_lds_t (run by bfcg_create) walks it, both with the family's *_lds_bytes, so what can be launched has its LDS cap registered.
+// A variant the selector does not hold for a record size ends the process (a refused launch would leave the stream running and the counts wrong).
+template <typename F> static F have(F fn, const char *family, int v, int rw) { if (!fn) { fprintf(stderr, "[bfcg] %s: no variant %d for records of %d dwords\n", family, v, rw); abort(); } return fn; }
+static hipError_t set_max_lds(const void *fn, size_t bytes) { return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
+
+// k_scatter1<.., ONEPASS, KC (k at compile time), FAST (scatter1_fast's geometry)>.  LDS: the stage of a tile's records (16-byte records that
+// leave their bucket's bits out keep the bucket in 2 more bytes) and 8 bytes of counters per bucket, 16 in one pass
+typedef void (*Scatter1Fn)(KParams, const uint8_t *, const uint8_t *, int64_t, const uint32_t *, uint32_t *, OnePass);
+enum { S1V_TWO_PASS, S1V_ONEPASS, S1V_FAST, S1V_FAST_K33, S1V_N }; // (all but the first: one pass)
+template <typename W, int RW> static Scatter1Fn scatter1_kernel(int v)
+{
+	if (v == S1V_TWO_PASS) return k_scatter1<W, RW, bfcg_tile1_of_rw(RW), BTS1>;
+	if (v == S1V_ONEPASS) return k_scatter1<W, RW, bfcg_tile1_of_rw(RW), BTS1, true>;
+	if constexpr (RW == 3) if (v == S1V_FAST) return k_scatter1<W, RW, bfcg_tile1_of_rw(RW), BTS1, true, 0, true>;
+	if constexpr (RW == 3) if (v == S1V_FAST_K33) return k_scatter1<W, RW, bfcg_tile1_of_rw(RW), BTS1, true, sizeof(W) == 8 ? 33 : 0, true>;
+	return nullptr;
+}
+static constexpr size_t scatter1_lds_bytes(int rw, int nb1, bool onepass, int rec_n) { return (size_t)bfcg_tile1_of_rw(rw) * (rw * 4 + ((rec_n > 0 && rw == 4) ? 2 : 0)) + (size_t)(onepass ? 16 : 8) * nb1; }
+
+// k_scatter2<.., TILE, BT, ONEPASS2, FAST2 (scatter2_fast's geometry; round 5: 16-byte records too -- their first word holds the same low bits
+// of y0)>; BIG: KParams.l2_big.  LDS: the stage of a tile's records and a counter per region of the bucket
+struct Scatter2K { void (*fn)(KParams, const uint32_t *, const uint32_t *, const uint32_t *, int, int, const uint32_t *, const uint32_t *, uint32_t *, OnePass2); int tile, bt; };
+enum { S2V_TWO_PASS, S2V_ONEPASS, S2V_FAST, S2V_FAST_BIG, S2V_N };
+template <typename W, int RW> static Scatter2K scatter2_kernel(int v)
+{
+	constexpr int T2 = bfcg_tile_of_rw(RW);
+	if (v == S2V_TWO_PASS) return {k_scatter2<W, RW, T2, BT2>, T2, BT2};
+	if (v == S2V_ONEPASS) return {k_scatter2<W, RW, T2, BT2, true>, T2, BT2};
+	if constexpr (RW == 3 || RW == 4) if (v == S2V_FAST) return {k_scatter2<W, RW, T2, BT2, true, true>, T2, BT2};
+	if constexpr (RW == 3) if (v == S2V_FAST_BIG) return {k_scatter2<W, RW, TILE2_BIG, BT2_BIG, true, true>, TILE2_BIG, BT2_BIG};
+	return {nullptr, 0, 0};
+}
+static constexpr size_t scatter2_lds_bytes(int rw, int tile, int nb2) { return (size_t)tile * (rw * 4) + (size_t)4 * nb2; }
+// rows of level 2 <= records/tile + one ragged row per segment; surplus blocks exit at once
+static inline unsigned level2_grid(uint64_t n_rec_bound, int tile, int n_seg) { return (unsigned)(((n_rec_bound / tile + n_seg + 1 + 7) / 8) * 8); }
+
+// k_bloom<.., threads, PF, NH (0: any number of hashes), TRACK, FM (filter mode), STREAM, SEGOUT, F3 (bloom_fast3's geometry)>.  LDS: bloom_lds_bytes
+struct BloomK { void (*fn)(KParams, BloomArgs); int bt; };
+enum { BV_1024, BV_512, BV_ANYH, BV_TRACK, BV_TRACK_ANYH, BV_FM_1024, BV_FM, BV_FM_ANYH, BV_STREAM, BV_SEG, BV_SEG_ANYH, BV_SEG_F3, BV_N };
+template <typename W, int RW> static BloomK bloom_kernel(int v)
+{
+	switch (v) {
+	case BV_1024: return {k_bloom<W, RW, 1024, 2, 4, false>, 1024};
+	case BV_512: return {k_bloom<W, RW, 512, 4, 4, false>, 512};
+	case BV_ANYH: return {k_bloom<W, RW, 512, 4, 0, false>, 512};
+	case BV_TRACK: return {k_bloom<W, RW, 512, 4, 4, true>, 512};
+	case BV_TRACK_ANYH: return {k_bloom<W, RW, 512, 4, 0, true>, 512};
+	case BV_FM_1024: return {k_bloom<W, RW, 1024, 2, 4, false, true>, 1024};
+	case BV_FM: return {k_bloom<W, RW, 512, 4, 4, false, true>, 512};
+	case BV_FM_ANYH: return {k_bloom<W, RW, 512, 4, 0, false, true>, 512};
+	case BV_STREAM: return {k_bloom<W, RW, 512, 4, 4, false, false, true>, 512};
+	case BV_SEG: return {k_bloom<W, RW, 512, 4, 4, false, false, true, true>, 512};
+	case BV_SEG_ANYH: return {k_bloom<W, RW, 512, 4, 0, false, false, true, true>, 512};
+	case BV_SEG_F3: if constexpr (RW == 3) return {k_bloom<W, RW, 512, 4, 4, false, false, true, true, true>, 512};
+	}
+	return {nullptr, 0};
+}
+template <typename W, int RW> static void launch_bloom(int v, const KParams &P, const BloomArgs &A, int nfine, hipStream_t st)
+{ const BloomK k = bloom_kernel<W, RW>(v); hipLaunchKernelGGL(have(k.fn, "k_bloom", v, RW), dim3(nfine), dim3(k.bt), (size_t)bloom_lds_bytes(P), st, P, A); }
+
+// k_commit_seg<threads> and k_seg_rehash<threads> hold a block of a region's segment: 8 bytes per slot and, where the commit's workgroup has
+// fewer than 1024 threads, 4 bytes of counters; largest at the largest block, 2^BFCG_SEG_MAX_SHIFT slots
+static BloomK commit_seg_kernel(int seg_blk) { return seg_blk >= 13 ? BloomK{k_commit_seg<1024>, 1024} : seg_blk == 12 ? BloomK{k_commit_seg<512>, 512} : BloomK{k_commit_seg<256>, 256}; }
+static constexpr size_t commit_seg_lds_bytes(int seg_blk) { return (size_t)(seg_blk >= 13 ? 8 : 12) << seg_blk; }
+static constexpr size_t seg_rehash_lds_bytes(int seg_blk) { return (size_t)8 << seg_blk; }
+static const auto seg_rehash_kernel = k_seg_rehash<512>; // (the one variant, named here alone)
 
 // BFCG_DEBUG_SYNC=1: wait behind every stage's launches and say which one the device failed in (a memory fault names no kernel)
 static void dbg_sync(hipStream_t st, const char *what)
@@ -2193,7 +2260,7 @@ static inline bool scatter1_fast(const KParams &P)
 template <typename W, int RW>
 static void run_stage_a_t(const KParams &P, const BatchBufs &B, const uint8_t *seq, const uint8_t *qual, int64_t n_pos, uint32_t *out1, hipStream_t st, hipEvent_t *ev)
 {
-	constexpr int T1 = S1<RW>::TILE, BTS1 = S1<RW>::BT, T2 = RW == 5 ? 2048 : RW == 4 ? 3072 : TILE2;
+	constexpr int T1 = bfcg_tile1_of_rw(RW), T2 = bfcg_tile_of_rw(RW);
 	const int nb1 = 1 << P.F1;
 	const int64_t tiles1 = (n_pos + T1 - 1) / T1;
 	const int n_chunks = (int)((tiles1 + SCAN_CH - 1) / SCAN_CH);
@@ -2204,7 +2271,7 @@ static void run_stage_a_t(const KParams &P, const BatchBufs &B, const uint8_t *s
 	hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(nb1 < 64 ? 64 : nb1), 0, st, B.chunk1, n_chunks, nb1, B.start1, B.row_base, T2);
 	hipLaunchKernelGGL(k_apply, dim3(n_chunks), dim3(256), 0, st, B.rows1, (int)tiles1, nb1, B.chunk1);
 	if (ev) hipEventRecord(ev[1], st);
-	hipLaunchKernelGGL((k_scatter1<W, RW, T1, BTS1>), dim3(g1), dim3(BTS1), (size_t)T1 * (RW * 4 + ((P.rec_n > 0 && RW == 4) ? 2 : 0)) + (size_t)8 * nb1, st, P, seq, qual, n_pos, B.rows1, out1, OnePass{nullptr, 0u, nullptr, nullptr, 0u, 0u, 0u, 0u});
+	hipLaunchKernelGGL(have(scatter1_kernel<W, RW>(S1V_TWO_PASS), "k_scatter1", S1V_TWO_PASS, RW), dim3(g1), dim3(BTS1), scatter1_lds_bytes(RW, nb1, false, P.rec_n), st, P, seq, qual, n_pos, B.rows1, out1, OnePass{nullptr, 0u, nullptr, nullptr, 0u, 0u, 0u, 0u});
 	if (ev) hipEventRecord(ev[2], st);
 }
 
@@ -2212,7 +2279,7 @@ static void run_stage_a_t(const KParams &P, const BatchBufs &B, const uint8_t *s
 template <typename W, int RW>
 static void run_stage_a_onepass_t(const KParams &P, const BatchBufs &B, const uint8_t *seq, const uint8_t *qual, int64_t n_pos, uint32_t *out1, hipStream_t st, hipEvent_t *ev)
 {
-	constexpr int T1 = S1<RW>::TILE, BTS1 = S1<RW>::BT, T2 = RW == 5 ? 2048 : RW == 4 ? 3072 : TILE2;
+	constexpr int T1 = bfcg_tile1_of_rw(RW), T2 = bfcg_tile_of_rw(RW);
 	const int nb1 = 1 << P.F1;
 	const int64_t tiles1 = (n_pos + T1 - 1) / T1;
 	if (ev) hipEventRecord(ev[0], st);
@@ -2220,7 +2287,7 @@ static void run_stage_a_onepass_t(const KParams &P, const BatchBufs &B, const ui
 	hipMemsetAsync(B.op_flags, 0, 4 * sizeof(uint32_t), st); // this slot's overflow flags (its previous batch's stage B and flag copy are complete: the caller waited)
 	if (ev) hipEventRecord(ev[1], st);
 	unsigned g1 = (unsigned)(((tiles1 + 7) / 8) * 8);
-	const size_t lds1 = (size_t)T1 * (RW * 4 + ((P.rec_n > 0 && RW == 4) ? 2 : 0)) + (size_t)16 * nb1;
+	const size_t lds1 = scatter1_lds_bytes(RW, nb1, true, P.rec_n);
 	OnePass OP{B.op_cursor, B.op_cap, B.op_flags, B.stats, 1u, B.op_own_lo, B.op_own_n, B.op_own_delta};
 	{ // as many workgroups as are resident at once (a CU's 160 KiB of LDS, at most 2048 threads), each walking its tiles; a multiple of 8 (XCDs)
 		static int n_cu = 0;
@@ -2239,18 +2306,11 @@ static void run_stage_a_onepass_t(const KParams &P, const BatchBufs &B, const ui
 		while (ch > 1 && (uint64_t)(g1 / 8) * (ch / 2) * 36 > B.op_cap) ch >>= 1;
 		OP.chunk = forced > 0 ? (uint32_t)forced : ch;
 	}
-	if constexpr (RW == 3) {
-		WcPlan wc;
-		if (B.cnt_live && scatter1_fast(P) && scatter1_wc_plan(P, OP, 3, n_pos, &wc)) run_scatter1_wc(P, seq, qual, n_pos, out1, OP, wc, st); // (round 5: write-combining buffers in LDS)
-		else if (scatter1_fast(P)) {
-			if (sizeof(W) == 8 && P.k == 33) hipLaunchKernelGGL((k_scatter1<W, RW, T1, BTS1, true, sizeof(W) == 8 ? 33 : 0, true>), dim3(g1), dim3(BTS1), lds1, st, P, seq, qual, n_pos, (const uint32_t *)nullptr, out1, OP);
-			else hipLaunchKernelGGL((k_scatter1<W, RW, T1, BTS1, true, 0, true>), dim3(g1), dim3(BTS1), lds1, st, P, seq, qual, n_pos, (const uint32_t *)nullptr, out1, OP);
-		} else hipLaunchKernelGGL((k_scatter1<W, RW, T1, BTS1, true>), dim3(g1), dim3(BTS1), lds1, st, P, seq, qual, n_pos, (const uint32_t *)nullptr, out1, OP);
-	} else {
-		WcPlan wc;
-		if (RW == 4 && B.cnt_live && scatter1_wc_plan(P, OP, 4, n_pos, &wc)) run_scatter1_wc(P, seq, qual, n_pos, out1, OP, wc, st); // (16-byte records at 2^10 buckets: config c5)
-		else hipLaunchKernelGGL((k_scatter1<W, RW, T1, BTS1, true>), dim3(g1), dim3(BTS1), lds1, st, P, seq, qual, n_pos, (const uint32_t *)nullptr, out1, OP);
-	}
+	WcPlan wc; // (write-combining buffers in LDS: 12-byte records of scatter1_fast's geometry -- round 5 --, 16-byte records at 2^10 buckets -- config c5)
+	const bool fast = RW == 3 && scatter1_fast(P);
+	const int v = !fast ? S1V_ONEPASS : sizeof(W) == 8 && P.k == 33 ? S1V_FAST_K33 : S1V_FAST;
+	if ((fast || RW == 4) && B.cnt_live && scatter1_wc_plan(P, OP, RW, n_pos, &wc)) run_scatter1_wc(P, seq, qual, n_pos, out1, OP, wc, st);
+	else hipLaunchKernelGGL(have(scatter1_kernel<W, RW>(v), "k_scatter1", v, RW), dim3(g1), dim3(BTS1), lds1, st, P, seq, qual, n_pos, nullptr, out1, OP);
 	dbg_sync(st, "k_scatter1 (one pass)");
 	uint32_t *sg = B.op_seg;
 	hipLaunchKernelGGL(k_seg_setup, dim3(1), dim3(1024), 0, st, P, B.op_cursor, B.op_cap, B.op_flags, (RW == 3 && P.l2_big) ? TILE2_BIG : T2, sg, sg + 8 * nb1, sg + 16 * nb1, sg + 24 * nb1 + 1);
@@ -2295,10 +2355,8 @@ static dim3 seg_grid(const KParams &P, uint32_t n_fine, uint32_t bt)
 }
 static void launch_commit_seg(const KParams &P, const BloomArgs &A, int nfine, hipStream_t st)
 {
-	const dim3 grid = seg_grid(P, (uint32_t)nfine, P.seg_blk >= 13 ? 1024u : P.seg_blk == 12 ? 512u : 256u); // one workgroup per (region, block of its segment)
-	if (P.seg_blk >= 13) hipLaunchKernelGGL((k_commit_seg<1024>), grid, dim3(1024), (size_t)8 << P.seg_blk, st, P, A);
-	else if (P.seg_blk == 12) hipLaunchKernelGGL((k_commit_seg<512>), grid, dim3(512), (size_t)12 << P.seg_blk, st, P, A); // (+ 4 bytes of counters per slot)
-	else hipLaunchKernelGGL((k_commit_seg<256>), grid, dim3(256), (size_t)12 << P.seg_blk, st, P, A);
+	const BloomK k = commit_seg_kernel(P.seg_blk);
+	hipLaunchKernelGGL(k.fn, seg_grid(P, (uint32_t)nfine, (uint32_t)k.bt), dim3(k.bt), commit_seg_lds_bytes(P.seg_blk), st, P, A); // one workgroup per (region, block of its segment)
 	dbg_sync(st, "k_commit_seg");
 }
 void run_commit_pages(const KParams &P, const BatchBufs &B, uint32_t n_fine, uint32_t pages, hipStream_t st)
@@ -2310,47 +2368,34 @@ void run_commit_pages(const KParams &P, const BatchBufs &B, uint32_t n_fine, uin
 	launch_commit_seg(P, A, (int)n_fine, st);
 }
 
-// stage B: records in `in1` as n_seg segments (seg_beg/seg_end, row_base over segments, bucket_start over the
-// nb_loc = n_seg/segs_per_bucket owned level-1 buckets) -> fine buckets -> bloom regions -> table
+// stage B's level 2: the n_seg segments of `in1` -> records grouped by bloom region; returns where they lie and the regions' starts
 template <typename W, int RW>
-static void run_stage_b_t(const KParams &P, const BatchBufs &B, const uint32_t *in1, const uint32_t *seg_beg, const uint32_t *seg_end, int n_seg,
-                          int segs_per_bucket, const uint32_t *row_base, const uint32_t *bucket_start, uint64_t n_rec_bound, hipStream_t st, hipEvent_t *ev)
+static std::pair<const uint32_t *, const uint32_t *> run_level2_t(const KParams &P, const BatchBufs &B, const uint32_t *in1, const uint32_t *seg_beg, const uint32_t *seg_end, int n_seg,
+                                                                  int segs_per_bucket, const uint32_t *row_base, const uint32_t *bucket_start, uint64_t n_rec_bound, hipStream_t st)
 {
+	if (P.F2 == 0) return {in1, bucket_start};
 	const int nb_loc = n_seg / segs_per_bucket, nfine = nb_loc << P.F2;
-	const uint32_t *fine_recs = in1; const uint32_t *fine_start = bucket_start;
-	if (P.F2 > 0) {
-		constexpr int T2 = RW == 5 ? 2048 : RW == 4 ? 3072 : TILE2; // = bfcg_tile_of(k)
-		// rows of level 2 <= records/T2 + one ragged row per segment; surplus blocks exit at once
-		const unsigned g2 = (unsigned)(((n_rec_bound / T2 + n_seg + 1 + 7) / 8) * 8);
-		bool big_done = false;
-		if constexpr (RW == 3) {
-			if (B.cap2 && P.l2_big && scatter2_fast(P)) { // (the segments' rows were counted in tiles of TILE2_BIG by this batch's k_seg_setup)
-				const unsigned g2b = (unsigned)(((n_rec_bound / TILE2_BIG + n_seg + 1 + 7) / 8) * 8);
-				hipMemsetAsync(B.cnt2, 0, sizeof(uint32_t) * (size_t)nfine, st);
-				hipLaunchKernelGGL((k_scatter2<W, RW, TILE2_BIG, BT2_BIG, true, true>), dim3(g2b), dim3(BT2_BIG), (size_t)TILE2_BIG * (RW * 4) + ((size_t)4 << P.F2), st, P, in1, seg_beg, seg_end, n_seg, segs_per_bucket, row_base,
-				                   (const uint32_t *)nullptr, (uint32_t *)B.recs2, OnePass2{B.cnt2, B.cap2, B.op_flags});
-				big_done = true;
-			}
-		}
-		if (big_done) ;
-		else if (B.cap2) { // one pass: region slabs and cursors
-			hipMemsetAsync(B.cnt2, 0, sizeof(uint32_t) * (size_t)nfine, st);
-			if ((RW == 3 || RW == 4) && scatter2_fast(P)) // (round 5: 16-byte records too -- their first word holds the same low bits of y0)
-				hipLaunchKernelGGL((k_scatter2<W, RW, T2, BT2, true, RW == 3 || RW == 4>), dim3(g2), dim3(BT2), (size_t)T2 * (RW * 4) + ((size_t)4 << P.F2), st, P, in1, seg_beg, seg_end, n_seg, segs_per_bucket, row_base,
-				                   (const uint32_t *)nullptr, (uint32_t *)B.recs2, OnePass2{B.cnt2, B.cap2, B.op_flags});
-			else
-			hipLaunchKernelGGL((k_scatter2<W, RW, T2, BT2, true>), dim3(g2), dim3(BT2), (size_t)T2 * (RW * 4) + ((size_t)4 << P.F2), st, P, in1, seg_beg, seg_end, n_seg, segs_per_bucket, row_base,
-			                   (const uint32_t *)nullptr, (uint32_t *)B.recs2, OnePass2{B.cnt2, B.cap2, B.op_flags});
-		} else {
-			hipLaunchKernelGGL((k_hist2<W, RW, T2, BT2>), dim3(g2), dim3(BT2), 0, st, P, in1, seg_beg, seg_end, n_seg, segs_per_bucket, row_base, B.rows2);
-			hipLaunchKernelGGL(k_scan2, dim3(nb_loc), dim3((1 << P.F2) < 64 ? 64 : (1 << P.F2)), 0, st, P, bucket_start, segs_per_bucket, row_base, B.rows2, B.start2, B.cnt_live);
-			hipLaunchKernelGGL((k_scatter2<W, RW, T2, BT2>), dim3(g2), dim3(BT2), (size_t)T2 * (RW * 4) + ((size_t)4 << P.F2), st, P, in1, seg_beg, seg_end, n_seg, segs_per_bucket, row_base, B.rows2,
-			                   (uint32_t *)B.recs2, OnePass2{nullptr, 0u, nullptr});
-		}
-		fine_recs = (const uint32_t *)B.recs2; fine_start = B.start2;
-		dbg_sync(st, "level 2");
+	int v = S2V_TWO_PASS;
+	if (B.cap2) { // one pass: region slabs and cursors
+		const bool fast = (RW == 3 || RW == 4) && scatter2_fast(P);
+		v = !fast ? S2V_ONEPASS : RW == 3 && P.l2_big ? S2V_FAST_BIG : S2V_FAST; // (BIG: the segments' rows were counted in tiles of TILE2_BIG by this batch's k_seg_setup)
+		hipMemsetAsync(B.cnt2, 0, sizeof(uint32_t) * (size_t)nfine, st);
+	} else {
+		hipLaunchKernelGGL((k_hist2<W, RW, bfcg_tile_of_rw(RW), BT2>), dim3(level2_grid(n_rec_bound, bfcg_tile_of_rw(RW), n_seg)), dim3(BT2), 0, st, P, in1, seg_beg, seg_end, n_seg, segs_per_bucket, row_base, B.rows2);
+		hipLaunchKernelGGL(k_scan2, dim3(nb_loc), dim3((1 << P.F2) < 64 ? 64 : (1 << P.F2)), 0, st, P, bucket_start, segs_per_bucket, row_base, B.rows2, B.start2, B.cnt_live);
 	}
-	if (ev) hipEventRecord(ev[3], st);
+	const Scatter2K k = scatter2_kernel<W, RW>(v);
+	hipLaunchKernelGGL(have(k.fn, "k_scatter2", v, RW), dim3(level2_grid(n_rec_bound, k.tile, n_seg)), dim3(k.bt), scatter2_lds_bytes(RW, k.tile, 1 << P.F2), st, P, in1, seg_beg, seg_end, n_seg, segs_per_bucket, row_base,
+	                   B.cap2 ? nullptr : B.rows2, (uint32_t *)B.recs2, B.cap2 ? OnePass2{B.cnt2, B.cap2, B.op_flags} : OnePass2{nullptr, 0u, nullptr});
+	dbg_sync(st, "level 2");
+	return {(const uint32_t *)B.recs2, B.start2};
+}
+
+// stage B's bloom insert: fills the kernels' arguments, picks and launches the kernel.  Where it hands the seen k-mers over to a commit of their
+// own, the arguments say so: seg_tab (region-owned segments) or else stream_out (as records)
+template <typename W, int RW>
+static BloomArgs run_bloom_t(const KParams &P, const BatchBufs &B, const uint32_t *fine_recs, const uint32_t *fine_start, int nfine, hipStream_t st)
+{
 	BloomArgs A;
 	memset(&A, 0, sizeof(A));
 	A.recs = fine_recs; A.start = fine_start; A.bloom = B.bloom; A.bloom_hi = B.bloom_hi; A.table = B.table; A.stats = B.stats;
@@ -2360,60 +2405,51 @@ static void run_stage_b_t(const KParams &P, const BatchBufs &B, const uint32_t *
 	A.cnt2 = nullptr; A.cap2 = 0; A.flags = B.op_flags; A.sticky = B.op_sticky; // (op_flags: NULL unless this batch went through the one-pass partition)
 	if (P.F2 > 0 && B.cap2) { A.cnt2 = B.cnt2; A.cap2 = B.cap2; }
 	else if (P.F2 > 0 && B.cnt_live) A.cnt2 = B.cnt_live; // two passes: the regions' counts beside their starts (region_list)
-	size_t lds = (size_t)bloom_lds_bytes(P);
+	const bool h4 = P.n_hashes == 4;
 	if (P.filter_mode && B.bloom_hi) { // both filters' slices in LDS, nothing to hand over
-		if (RW == 4 && P.b3fm) run_bloom3fm(P, A, nfine, lds, st); // (bfcg_bloom3.hip)
-		else if (P.n_hashes == 4 && P.bloom_bt == 1024) hipLaunchKernelGGL((k_bloom<W, RW, 1024, 2, 4, false, true>), dim3(nfine), dim3(1024), lds, st, P, A);
-		else if (P.n_hashes == 4) hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 4, false, true>), dim3(nfine), dim3(512), lds, st, P, A);
-		else hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 0, false, true>), dim3(nfine), dim3(512), lds, st, P, A);
+		if (RW == 4 && P.b3fm) run_bloom3fm(P, A, nfine, (size_t)bloom_lds_bytes(P), st); // (bfcg_bloom3.hip)
+		else launch_bloom<W, RW>(!h4 ? BV_FM_ANYH : P.bloom_bt == 1024 ? BV_FM_1024 : BV_FM, P, A, nfine, st);
 	} else if (P.seg && B.seg_tab && (B.stream_out || B.ho)) { // region-owned table segments: seen k-mers are handed to k_commit_seg, one workgroup per region
 		A.stream_out = B.stream_out; A.seg_tab = B.seg_tab; A.table = nullptr; A.agg_out = nullptr;
 		A.ho = B.ho; A.ho_stride = B.ho_stride; A.ho_cur = B.ho_cur; A.ho_mark = B.ho_stride ? B.ho_mark + (size_t)B.ho_page * B.ho_mark_stride : nullptr;
-		bool f3 = false;
-		if constexpr (RW == 3) {
-			if (P.b3 && (P.b3_cold || !P.dedupe)) { f3 = true; run_bloom3(P, A, nfine, lds, st); } // (bfcg_bloom3.hip; without its COLD mode, cold batches with copies resolved by class stay with k_bloom)
-			else if (P.n_hashes == 4 && bloom_fast3(P)) { f3 = true; hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 4, false, false, true, true, true>), dim3(nfine), dim3(512), lds, st, P, A); }
-		}
-		if (f3) ;
-		else if (P.n_hashes == 4) hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 4, false, false, true, true>), dim3(nfine), dim3(512), lds, st, P, A);
-		else hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 0, false, false, true, true>), dim3(nfine), dim3(512), lds, st, P, A);
-		if (ev) hipEventRecord(ev[4], st);
-		dbg_sync(st, "k_bloom");
+		if (RW == 3 && P.b3 && (P.b3_cold || !P.dedupe)) run_bloom3(P, A, nfine, (size_t)bloom_lds_bytes(P), st); // (bfcg_bloom3.hip; without its COLD mode, cold batches with copies resolved by class stay with k_bloom)
+		else launch_bloom<W, RW>(!h4 ? BV_SEG_ANYH : RW == 3 && bloom_fast3(P) ? BV_SEG_F3 : BV_SEG, P, A, nfine, st);
+	} else if (B.stream && B.stream_out && !P.track && h4) { // low-multiplicity batches: no aggregation (ctx decides, see bfcg_ctx.hip)
+		A.stream_out = B.stream_out;
+		launch_bloom<W, RW>(BV_STREAM, P, A, nfine, st);
+	} else if (P.track) launch_bloom<W, RW>(h4 ? BV_TRACK : BV_TRACK_ANYH, P, A, nfine, st); // (order stamps for the byte-identical dump: its own instantiation, so that the default path pays nothing for it)
+	else launch_bloom<W, RW>(!h4 ? BV_ANYH : P.bloom_bt == 1024 ? BV_1024 : BV_512, P, A, nfine, st);
+	return A;
+}
+
+// stage B's commit: the seen k-mers into the count table
+template <typename W, int RW>
+static void run_commit_t(const KParams &P, const BatchBufs &B, BloomArgs &A, int nfine, hipStream_t st)
+{
+	const auto waves = [&] { return dim3((unsigned)((nfine + 4 * COMMIT_RPW - 1) / (4 * COMMIT_RPW))); }; // a region per wave, 4 waves per workgroup
+	if (A.seg_tab) {
 		if (B.ho_stride == 0 || B.ho_commit) { // the log's pages so far (or this batch's entries at its records' offsets) into the segments
 			A.ho_mark = B.ho_mark; A.ho_mark_stride = B.ho_mark_stride; A.ho_pages = B.ho_page + 1; A.ho_keys = B.ho_keys;
 			launch_commit_seg(P, A, nfine, st);
 		}
-		if (A.flags) hipLaunchKernelGGL(k_seal, dim3(1), dim3(1), 0, st, B.op_flags, B.op_sticky);
-		if (ev) hipEventRecord(ev[5], st);
-		return;
-	} else if (B.stream && B.stream_out && !P.track && P.n_hashes == 4) { // low-multiplicity batches: no aggregation (ctx decides, see bfcg_ctx.hip)
-		A.stream_out = B.stream_out;
-		hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 4, false, false, true>), dim3(nfine), dim3(512), lds, st, P, A);
-		if (ev) hipEventRecord(ev[4], st);
-		dbg_sync(st, "k_bloom");
-		hipLaunchKernelGGL((k_commit_stream<W, RW>), dim3((unsigned)((nfine + 4 * COMMIT_RPW - 1) / (4 * COMMIT_RPW))), dim3(256), 0, st, P, A);
-		if (A.flags) hipLaunchKernelGGL(k_seal, dim3(1), dim3(1), 0, st, B.op_flags, B.op_sticky);
-		if (ev) hipEventRecord(ev[5], st);
-		return;
-	} else if (P.track) { // order stamps for the byte-identical dump: its own instantiation, so that the default path pays nothing for it
-		if (P.n_hashes == 4) hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 4, true>), dim3(nfine), dim3(512), lds, st, P, A);
-		else hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 0, true>), dim3(nfine), dim3(512), lds, st, P, A);
-	} else if (P.n_hashes == 4) {
-		if (P.bloom_bt == 1024) hipLaunchKernelGGL((k_bloom<W, RW, 1024, 2, 4, false>), dim3(nfine), dim3(1024), lds, st, P, A);
-		else hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 4, false>), dim3(nfine), dim3(512), lds, st, P, A);
-	} else hipLaunchKernelGGL((k_bloom<W, RW, 512, 4, 0, false>), dim3(nfine), dim3(512), lds, st, P, A);
+	} else if (A.stream_out) hipLaunchKernelGGL((k_commit_stream<W, RW>), waves(), dim3(256), 0, st, P, A);
+	else if (B.agg_out && nfine > (1 << 18)) hipLaunchKernelGGL((P.track ? k_commit<W, true, true> : k_commit<W, false, true>), waves(), dim3(256), 0, st, P, A);
+	else if (B.agg_out) hipLaunchKernelGGL((P.track ? k_commit<W, true, false> : k_commit<W, false, false>), dim3((unsigned)(((uint64_t)nfine * P.ag_cap + 255) / 256)), dim3(256), 0, st, P, A);
+}
+
+// stage B: records in `in1` as n_seg segments (seg_beg/seg_end, row_base over segments, bucket_start over the
+// nb_loc = n_seg/segs_per_bucket owned level-1 buckets) -> fine buckets -> bloom regions -> table
+template <typename W, int RW>
+static void run_stage_b_t(const KParams &P, const BatchBufs &B, const uint32_t *in1, const uint32_t *seg_beg, const uint32_t *seg_end, int n_seg,
+                          int segs_per_bucket, const uint32_t *row_base, const uint32_t *bucket_start, uint64_t n_rec_bound, hipStream_t st, hipEvent_t *ev)
+{
+	const int nfine = (n_seg / segs_per_bucket) << P.F2;
+	const auto [fine_recs, fine_start] = run_level2_t<W, RW>(P, B, in1, seg_beg, seg_end, n_seg, segs_per_bucket, row_base, bucket_start, n_rec_bound, st);
+	if (ev) hipEventRecord(ev[3], st);
+	BloomArgs A = run_bloom_t<W, RW>(P, B, fine_recs, fine_start, nfine, st);
 	if (ev) hipEventRecord(ev[4], st);
-	if (B.agg_out) {
-		const uint64_t slots = (uint64_t)nfine * P.ag_cap;
-		const unsigned gs = (unsigned)((slots + 255) / 256), gw = (unsigned)((nfine + 4 * COMMIT_RPW - 1) / (4 * COMMIT_RPW)); // 4 waves per workgroup
-		if (nfine > (1 << 18)) {
-			if (P.track) hipLaunchKernelGGL((k_commit<W, true, true>), dim3(gw), dim3(256), 0, st, P, A);
-			else hipLaunchKernelGGL((k_commit<W, false, true>), dim3(gw), dim3(256), 0, st, P, A);
-		} else {
-			if (P.track) hipLaunchKernelGGL((k_commit<W, true, false>), dim3(gs), dim3(256), 0, st, P, A);
-			else hipLaunchKernelGGL((k_commit<W, false, false>), dim3(gs), dim3(256), 0, st, P, A);
-		}
-	}
+	if (A.seg_tab || A.stream_out) dbg_sync(st, "k_bloom"); // (before a commit of its own)
+	run_commit_t<W, RW>(P, B, A, nfine, st);
 	if (A.flags) hipLaunchKernelGGL(k_seal, dim3(1), dim3(1), 0, st, B.op_flags, B.op_sticky);
 	if (ev) hipEventRecord(ev[5], st);
 }
@@ -2438,7 +2474,7 @@ void run_pack_rows(const KParams &P, const BatchBufs &B, int n_ranks, uint32_t r
 void run_seg_setup_mg(const KParams &P, int rw_dwords, const uint32_t *rows, uint32_t row_w, int n_ranks, int s_lo, int s_hi, uint32_t cap, uint32_t *seg, unsigned long long *total, hipStream_t st)
 {
 	const int nb1 = 1 << P.F1, nb_loc = nb1 / n_ranks, n_seg = nb1 * 8;
-	hipLaunchKernelGGL(k_seg_setup_mg, dim3(1), dim3(1024), 0, st, rows, row_w, n_ranks, s_lo, s_hi, nb_loc, cap, rw_dwords == 5 ? 2048 : rw_dwords == 4 ? 3072 : TILE2, seg, seg + n_seg, seg + 2 * n_seg, seg + 3 * n_seg + 1, total);
+	hipLaunchKernelGGL(k_seg_setup_mg, dim3(1), dim3(1024), 0, st, rows, row_w, n_ranks, s_lo, s_hi, nb_loc, cap, bfcg_tile_of_rw(rw_dwords), seg, seg + n_seg, seg + 2 * n_seg, seg + 3 * n_seg + 1, total);
 }
 
 void run_stage_b(const KParams &P, const BatchBufs &B, const uint64_t *in1, const uint32_t *seg_beg, const uint32_t *seg_end, int n_seg, int segs_per_bucket,
@@ -2460,48 +2496,22 @@ int bloom_lds_bytes(const KParams &P)
 	return (int)(((size_t)64 << P.R) + (size_t)P.fs_cap * 4 + second + (size_t)P.list_cap * (P.b3 ? 10 : 8) + 16);
 }
 
-template <typename W, int RW> static hipError_t set_attr_t(int lds)
+// the LDS caps of every variant the selectors hold, each family's at the largest its *_lds_bytes gets (BFCG_MAXB buckets; a block of a
+// segment of 2^BFCG_SEG_MAX_SHIFT slots); `lds`: bloom_lds_bytes of the context's geometry
+template <typename W, int RW> static void register_lds_t(int lds, hipError_t *err)
 {
-	hipError_t e;
-	constexpr int T1 = S1<RW>::TILE, BTS1 = S1<RW>::BT, T2 = RW == 5 ? 2048 : RW == 4 ? 3072 : TILE2;
-	e = hipFuncSetAttribute((const void *)k_scatter1<W, RW, T1, BTS1>, hipFuncAttributeMaxDynamicSharedMemorySize, T1 * (RW * 4 + 2) + 8 * BFCG_MAXB); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_scatter1<W, RW, T1, BTS1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T1 * (RW * 4 + 2) + 16 * BFCG_MAXB); if (e != hipSuccess) return e;
-	if constexpr (RW == 3) {
-		e = hipFuncSetAttribute((const void *)k_scatter1<W, RW, T1, BTS1, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T1 * (RW * 4 + 2) + 16 * BFCG_MAXB); if (e != hipSuccess) return e;
-		e = hipFuncSetAttribute((const void *)k_scatter1<W, RW, T1, BTS1, true, sizeof(W) == 8 ? 33 : 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T1 * (RW * 4 + 2) + 16 * BFCG_MAXB); if (e != hipSuccess) return e;
-	}
-	e = hipFuncSetAttribute((const void *)k_scatter2<W, RW, T2, BT2>, hipFuncAttributeMaxDynamicSharedMemorySize, T2 * (RW * 4) + 8 * BFCG_MAXB); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_scatter2<W, RW, T2, BT2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T2 * (RW * 4) + 8 * BFCG_MAXB); if (e != hipSuccess) return e;
-	if (RW == 3 || RW == 4) { e = hipFuncSetAttribute((const void *)k_scatter2<W, RW, T2, BT2, true, RW == 3 || RW == 4>, hipFuncAttributeMaxDynamicSharedMemorySize, T2 * (RW * 4) + 8 * BFCG_MAXB); if (e != hipSuccess) return e; }
-	if constexpr (RW == 3) { e = hipFuncSetAttribute((const void *)k_scatter2<W, RW, TILE2_BIG, BT2_BIG, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE2_BIG * (RW * 4) + 8 * BFCG_MAXB); if (e != hipSuccess) return e; }
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 1024, 2, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 4, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 4, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	if constexpr (RW == 3) { e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 4, false, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e; }
-	if constexpr (RW == 3) { e = set_bloom3_lds_attr(lds > 53008 ? lds : 53008); if (e != hipSuccess) return e; }
-	if constexpr (RW == 4) { e = set_bloom3fm_lds_attr(lds > 53008 ? lds : 53008); if (e != hipSuccess) return e; } // (its COLD mode lays the same third of a CU's LDS out differently)
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 0, false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_commit_seg<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 << BFCG_SEG_MAX_SHIFT); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_commit_seg<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 << BFCG_SEG_MAX_SHIFT); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_commit_seg<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 << BFCG_SEG_MAX_SHIFT); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 1024, 2, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	e = hipFuncSetAttribute((const void *)k_bloom<W, RW, 512, 4, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); if (e != hipSuccess) return e;
-	return hipSuccess;
+	hipError_t e = hipSuccess;
+	for (int v = 0; v < S1V_N && e == hipSuccess; ++v) if (const Scatter1Fn fn = scatter1_kernel<W, RW>(v)) e = set_max_lds((const void *)fn, scatter1_lds_bytes(RW, BFCG_MAXB, v != S1V_TWO_PASS, 1));
+	for (int v = 0; v < S2V_N && e == hipSuccess; ++v) if (const Scatter2K k = scatter2_kernel<W, RW>(v); k.fn) e = set_max_lds((const void *)k.fn, scatter2_lds_bytes(RW, k.tile, BFCG_MAXB));
+	for (int v = 0; v < BV_N && e == hipSuccess; ++v) if (const BloomK k = bloom_kernel<W, RW>(v); k.fn) e = set_max_lds((const void *)k.fn, (size_t)lds);
+	for (int blk = 11; blk <= 13 && e == hipSuccess; ++blk) // (a block size for each of k_commit_seg's workgroup sizes)
+		e = set_max_lds((const void *)commit_seg_kernel(blk).fn, commit_seg_lds_bytes(BFCG_SEG_MAX_SHIFT));
+	if (RW == 3 && e == hipSuccess) e = set_bloom3_lds_attr(lds); // (bfcg_bloom3.hip)
+	if (RW == 4 && e == hipSuccess) e = set_bloom3fm_lds_attr(lds);
+	*err = e;
 }
 hipError_t set_bloom_lds_attr(const KParams &P)
-{
-	int lds = bloom_lds_bytes(P);
-	const int rw = bfcg_rec_dwords(P.k, P.rec_n);
-	if (P.k <= 32) return rw == 3 ? set_attr_t<uint32_t, 3>(lds) : set_attr_t<uint32_t, 4>(lds);
-	if (rw == 3) return set_attr_t<uint64_t, 3>(lds);
-	if (rw == 4) return set_attr_t<uint64_t, 4>(lds);
-	return set_attr_t<uint64_t, 5>(lds);
-}
+{ hipError_t e = hipSuccess; DISPATCH_W(register_lds_t, bloom_lds_bytes(P), &e); return e; }
 
 void run_query(const KParams &P, const uint8_t *seq, int64_t n_pos, const void *bloom, uint8_t *flags, hipStream_t st)
 {
@@ -2552,10 +2562,10 @@ void run_table_replay(const KParams &P, unsigned long long *tab, const uint64_t 
 	TabOrder O; O.first = first; O.sub_last = sub_last;
 	hipLaunchKernelGGL(k_table_replay, dim3(g), dim3(256), 0, st, P, tab, src, n, stats, ovf, ovf_cap, stats + (size_t)ST_SLOTS * ST_N, O);
 }
-hipError_t set_seg_lds_attr(void) { return hipFuncSetAttribute((const void *)k_seg_rehash<512>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 << BFCG_SEG_MAX_SHIFT); }
+hipError_t set_seg_lds_attr(void) { return set_max_lds((const void *)seg_rehash_kernel, seg_rehash_lds_bytes(BFCG_SEG_MAX_SHIFT)); }
 void run_seg_rehash(const KParams &P, const unsigned long long *old_tab, int old_shift, int old_blk, unsigned long long *new_tab, uint32_t n_fine, hipStream_t st)
 {
-	hipLaunchKernelGGL((k_seg_rehash<512>), seg_grid(P, n_fine, 512u), dim3(512), (size_t)8 << P.seg_blk, st, P, old_tab, old_shift, old_blk, new_tab);
+	hipLaunchKernelGGL(seg_rehash_kernel, seg_grid(P, n_fine, 512), dim3(512), seg_rehash_lds_bytes(P.seg_blk), st, P, old_tab, old_shift, old_blk, new_tab);
 }
 void run_seg_replay(const KParams &P, unsigned long long *seg_tab, const uint64_t *src, uint64_t n, unsigned long long *stats, uint64_t *ovf, uint32_t ovf_cap, hipStream_t st)
 {
