@@ -128,14 +128,18 @@ SYMBOLS = {
     "bfcg_export_bloom_resident": (C.POINTER(BfcBf), [C.c_void_p, C.c_int]),
     "bfcg_resident_drop": (None, [C.c_void_p]),
     "bfcg_export_table": (C.c_void_p, [C.c_void_p]),
+    "bfcg_export_table_resident": (C.c_void_p, [C.c_void_p]),
     "bfc_ch_get_lpre": (C.c_int, [C.c_void_p]),
     "bfc_ch_export_sorted": (C.c_uint64, [C.c_void_p, u32p, u64p]),
     "bfcg_ec_create": (C.c_void_p, [C.c_void_p, C.POINTER(BfcOpt), C.c_int, C.c_uint64, C.c_uint64]),
+    "bfcg_ec_attach": (C.c_void_p, [C.c_void_p, C.POINTER(BfcOpt), C.c_uint64, C.c_uint64]),
     "bfcg_ec_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, u32p, u32p]),
     "bfcg_ec_destroy": (None, [C.c_void_p]),
     "bfcg_ec_last_ms": (C.c_float, [C.c_void_p]),
     "bfcg_ec_host_reads": (C.c_uint64, [C.c_void_p]),
     "bfcg_ec_last_lookups": (C.c_uint64, [C.c_void_p]),
+    "bfcg_ec_retry_reads": (C.c_uint64, [C.c_void_p]),
+    "bfcg_ec_adopted": (C.c_int, [C.c_void_p]),
     "bfcg_ec1_host": (C.c_int, [C.c_void_p, C.POINTER(BfcOpt), C.c_int, C.c_void_p, C.c_void_p, u32p, u32p]),
     "bfcg_ec_batch_refine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_uint64, u32p, u32p, u32p, u32p]),
     "bfcg_ec1_host_refine": (C.c_int, [C.c_void_p, C.POINTER(BfcOpt), C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, u32p, u32p]),

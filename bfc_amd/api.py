@@ -672,6 +672,10 @@ class GpuCorrector:
     same code as a twin (bfcg_ec1_host).  `table` is a HostTable (bfc_count / bfc_ch_restore); it must outlive this object.  `opt` is a
     table-mode bfc_opt_t (bfc_opt_init, k = the table's k).  Results are the reference's worker_ec: corrected bytes, aux, aux2.
 
+    `table` may also be a GpuCounter: the corrector then attaches to the table where the counter built it (bfcg_ec_attach; nothing is
+    exported, the counter must not count meanwhile, `device` is the counter's).  There is no host table then: reads the device cannot hold
+    are corrected by its retry kernel (retry_reads()), and host_correct raises.
+
     With opt.refine_ec (`bfc -R`) every read given is refined: correct / host_correct take `ori`, the reads' earlier stats as two uint32
     arrays packed like aux / aux2 (parse_ec_stats; all zero where there were none).  Which reads to skip is the caller's choice, as in
     worker_ec (correct.c:542-546)."""
@@ -679,9 +683,18 @@ class GpuCorrector:
     def __init__(self, table, opt, device=0, max_pos=1 << 24, max_reads=1 << 18, gpu=True):
         self.L = _lib.load()
         self.table, self.opt = table, opt
+        self.e = None
+        self.attached = isinstance(table, GpuCounter)
+        if self.attached:
+            self.e = self.L.bfcg_ec_attach(table.ctx, C.byref(opt), int(max_pos), int(max_reads))
+            if not self.e:
+                raise BfcGpuError("bfcg_ec_attach failed: " + self.L.bfcg_last_error().decode())
+            km = GpuKmers(table)  # the mode bfcg_ec_attach read, for callers (the counter has not counted since)
+            self.mode = km.hist()[0]
+            km.close()
+            return
         cnt, high = np.zeros(256, dtype=np.uint64), np.zeros(64, dtype=np.uint64)
         self.mode = int(self.L.bfc_ch_hist(table.ptr, cnt.ctypes.data_as(u64p), high.ctypes.data_as(u64p)))
-        self.e = None
         if gpu:
             self.e = self.L.bfcg_ec_create(table.ptr, C.byref(opt), device, int(max_pos), int(max_reads))
             if not self.e:
@@ -736,8 +749,21 @@ class GpuCorrector:
             out_q = [qb[int(off[i]):int(off[i + 1]) - 1] for i in range(n)]
         return out_s, out_q, aux, aux2
 
+    def correct_stream(self, s, q, off):
+        """One batch already in the stream format (uint8 arrays with a separator after each read, q may be None; off: uint64[n + 1]),
+        rewritten in place: (s, q, aux, aux2).  Table mode only."""
+        n = len(off) - 1
+        aux, aux2 = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        rc = self.L.bfcg_ec_batch(self.e, s.ctypes.data, q.ctypes.data if q is not None else None, len(s), off.ctypes.data_as(u64p), n,
+                                  aux.ctypes.data_as(u32p), aux2.ctypes.data_as(u32p))
+        if rc != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        return s, q, aux, aux2
+
     def host_correct(self, seqs, quals=None, ori=None):
         """The same through the host instance, read by read."""
+        if self.attached:
+            raise BfcGpuError("host_correct: this corrector is attached to a counter's device table, there is no host table")
         n = len(seqs)
         ori = self._ori(n, ori)
         out_s, out_q = [], [] if quals is not None else None
@@ -766,6 +792,15 @@ class GpuCorrector:
 
     def host_reads(self):
         return int(self.L.bfcg_ec_host_reads(self.e))
+
+    def retry_reads(self):
+        """Reads the retry kernel corrected since creation (an attached corrector's answer for what the first kernel leaves)."""
+        return int(self.L.bfcg_ec_retry_reads(self.e))
+
+    @property
+    def adopted(self):
+        """True if the table was found resident in HBM (left there by bfc_count) instead of being uploaded."""
+        return bool(self.e) and bool(self.L.bfcg_ec_adopted(self.e))
 
 
 def parse_ec_stats(comment):

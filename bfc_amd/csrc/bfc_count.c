@@ -307,7 +307,7 @@ void *bfc_count(const char *fn, const bfc_opt_t *opt)
 	if (grp) ret = opt->filter_mode ? (void*)(getenv("BFC_GPU_NO_RESIDENT") ? bfcg_group_export_bloom(grp, 1) : bfcg_group_export_bloom_resident(grp, 1)) /* all-gathered onto every device for the sharded trim pass */
 	                                : (void*)bfcg_group_export_table(grp);
 	else ret = opt->filter_mode ? (void*)(getenv("BFC_GPU_NO_RESIDENT") ? bfcg_export_bloom(ctx, 1) : bfcg_export_bloom_resident(ctx, 1)) /* bf_high also stays in HBM for the trim pass (bfc_trim.c) */
-	                            : (void*)bfcg_export_table(ctx);
+	                            : (void*)(getenv("BFC_GPU_NO_RESIDENT") ? bfcg_export_table(ctx) : bfcg_export_table_resident(ctx)); /* the table also stays in HBM for the corrector (bfc_trim.c: correct_gpu) */
 	if (timing) fprintf(stderr, "[T::bfc_count] waited for the parser %.3f s, packed bit planes %.3f s, submitted batches %.3f s, result to the host %.3f s (%d fast / %d serial batches)\n", t_wait, t_pack, t_submit, now_real() - tt, ps.fast_batches, ps.serial_batches);
 	if (ret == 0) { fprintf(stderr, "[E::%s] cannot bring the result to the host: %s\n", __func__, bfcg_last_error()); abort(); }
 	/* (Round 4 tried to take the clean-up off the path -- buffers pinned by four threads, buffers and input released by a thread of its own under

@@ -41,7 +41,9 @@ static inline void kmer_y(int k, const uint64_t x[4], uint64_t y[2])
 /* ------------------------------------------------------------------ bloom filter (bbf.c) */
 
 /* A filter exported by bfc_count may still have its copy in HBM (bfcg_export_bloom_resident), for the trim pass to adopt.  That copy
- * dies with the host object and as soon as the host object is written to.  Weak: this file also links without the GPU objects. */
+ * dies with the host object and as soon as the host object is written to.  Weak: this file also links without the GPU objects.
+ * A count table has the same arrangement (bfcg_export_table_resident, for the corrector to adopt): bfc_ch_destroy, bfc_ch_insert and
+ * the raw allocator, through which bfc_ch_init, bfc_ch_restore and bfc_ch_union get their object, make the same call. */
 void bfcg_resident_drop(const void *bf) __attribute__((weak));
 
 bfc_bf_t *bfc_bf_alloc_raw(int n_shift, int n_hashes)
@@ -136,6 +138,7 @@ bfc_ch_t *bfc_ch_alloc_raw(int k, int l_pre, int cshift)
 {
 	bfc_ch_t *ch = (bfc_ch_t*)calloc(1, sizeof(bfc_ch_t));
 	if (!ch) return 0;
+	if (bfcg_resident_drop) bfcg_resident_drop(ch); /* an address can come back: whatever was registered for it belongs to a dead object */
 	ch->k = k; ch->l_pre = l_pre; ch->cshift = cshift;
 	ch->slots = (uint64_t*)calloc((size_t)1 << (l_pre + cshift), 8);
 	if (!ch->slots) { free(ch); return 0; }
@@ -253,6 +256,7 @@ bfc_ch_t *bfc_ch_init(int k, int l_pre)
 void bfc_ch_destroy(bfc_ch_t *ch)
 {
 	if (!ch) return;
+	if (bfcg_resident_drop) bfcg_resident_drop(ch);
 	pthread_rwlock_destroy(&ch->grow_lock);
 	free(ch->first); free(ch->sub_last);
 	free(ch->slots); free(ch);
@@ -324,6 +328,7 @@ int bfc_ch_insert(bfc_ch_t *ch, const uint64_t x[2], int is_high, int forced)
 	uint64_t key;
 	uint32_t sub = subkey(ch, x, &key);
 	(void)forced; /* lock-free upsert never has to give up (htab.c:67-72 returns -1 only on lock contention) */
+	if (bfcg_resident_drop) bfcg_resident_drop(ch); /* the copy in HBM, if any, is stale from here on (one relaxed load when there is none) */
 	if (ch->first) { pthread_rwlock_wrlock(&ch->grow_lock); drop_order(ch); pthread_rwlock_unlock(&ch->grow_lock); }
 	for (;;) {
 		int r, seen_cshift;

@@ -190,6 +190,7 @@ static void correct_gpu(const char *fn, const bfc_opt_t *opt, const bfc_ch_t *ch
 	batch_t b;
 	ec_devs_t g;
 	int d, empties = 0;
+	int n_adopted = 0;
 	uint64_t cap, max_reads, *off, n_total = 0, n_refined = 0, n_kept = 0;
 	uint32_t *aux, *aux2;
 	rinfo_t *ri;
@@ -215,6 +216,7 @@ static void correct_gpu(const char *fn, const bfc_opt_t *opt, const bfc_ch_t *ch
 	for (d = 0; d < g.n_dev; ++d) { /* a device's share of a batch: 1/N of its positions (cut at the nearest read boundary), up to all of its reads */
 		g.ecs[d] = bfcg_ec_create(ch, opt, g.devs[d], g.n_dev > 1 ? cap / (uint64_t)g.n_dev + cap / 64 + (1u << 16) : cap, max_reads);
 		if (!g.ecs[d]) { fprintf(stderr, "[E::%s] cannot set up error correction on the GPU: %s\n", "bfc_correct", bfcg_last_error()); abort(); }
+		n_adopted += bfcg_ec_adopted(g.ecs[d]); /* the copy bfc_count left in HBM (bfcg_export_table_resident): the first corrector on its device takes it */
 	}
 	if (g.n_dev > 1) g.off2 = (uint64_t*)malloc((max_reads + 1 + (uint64_t)g.n_dev) * 8);
 
@@ -294,6 +296,9 @@ static void correct_gpu(const char *fn, const bfc_opt_t *opt, const bfc_ch_t *ch
 	fprintf(stderr, "[M::%s] error correction ran on the GPU (%d device(s), %.1f ms of kernels): %llu reads, %llu of them by the host fallback",
 	        "bfc_correct", g.n_dev, g.gpu_ms, (unsigned long long)n_total, (unsigned long long)g.n_host);
 	if (opt->refine_ec) fprintf(stderr, "; -R: %llu reads refined, %llu skipped", (unsigned long long)n_refined, (unsigned long long)n_kept);
+	if (n_adopted == g.n_dev) fprintf(stderr, "; count table found in HBM");
+	else if (n_adopted == 0) fprintf(stderr, "; count table uploaded");
+	else fprintf(stderr, "; count table found in HBM by %d corrector(s), uploaded by %d", n_adopted, g.n_dev - n_adopted);
 	fputc('\n', stderr);
 	free(g.off2);
 	gzclose(ps.rd.fp);

@@ -1700,7 +1700,10 @@ extern "C" bfc_bf_t *bfcg_export_bloom(bfcg_ctx_t *c, int which)
 // (correct.c:556): bfc_count hands the host copy the reference's API promises (bfc_bf_t.b is public) AND leaves a device copy here,
 // which bfcg_trim_create adopts instead of uploading 2^(b-3) bytes again.  The copy is dropped when the host object is destroyed or
 // written to through this library (bfc_bf_destroy / bfc_bf_insert call bfcg_resident_drop).
-struct resident_t { const void *bf; void *dev; int device, n_shift; };
+// A count table has the same arrangement (bfcg_export_table_resident -> bfcg_kcov_create, i.e. bfc_count -> bfc_correct): its entry
+// carries k, l_pre and cshift instead of n_shift (k = 0 marks a filter's entry), and the bfc_ch_* functions that write to a table, free
+// one or hand out an address call bfcg_resident_drop as the bfc_bf_* ones do.
+struct resident_t { const void *bf; void *dev; int device, n_shift, k, l_pre, cshift; };
 static resident_t g_res[16];
 static std::atomic<int> g_res_n{0};
 static std::mutex g_res_mu;
@@ -1736,7 +1739,18 @@ static void *resident_take(const bfc_bf_t *bf, int device)
 	if (g_res_n.load(std::memory_order_relaxed) == 0) return 0;
 	std::lock_guard<std::mutex> lk(g_res_mu);
 	for (int i = 0; i < 16; ++i)
-		if (g_res[i].dev && g_res[i].bf == (const void *)bf && g_res[i].device == device && g_res[i].n_shift == bf->n_shift) {
+		if (g_res[i].dev && g_res[i].bf == (const void *)bf && g_res[i].device == device && g_res[i].k == 0 && g_res[i].n_shift == bf->n_shift) {
+			void *dev = g_res[i].dev; g_res[i].dev = 0; g_res_n.fetch_sub(1); return dev;
+		}
+	return 0;
+}
+// the same for a count table: the first taker owns the copy (and frees it), a second one finds nothing
+static void *resident_take_table(const bfc_ch_t *ch, int device, int k, int l_pre, int cshift)
+{
+	if (g_res_n.load(std::memory_order_relaxed) == 0) return 0;
+	std::lock_guard<std::mutex> lk(g_res_mu);
+	for (int i = 0; i < 16; ++i)
+		if (g_res[i].dev && g_res[i].bf == (const void *)ch && g_res[i].device == device && g_res[i].k == k && g_res[i].l_pre == l_pre && g_res[i].cshift == cshift) {
 			void *dev = g_res[i].dev; g_res[i].dev = 0; g_res_n.fetch_sub(1); return dev;
 		}
 	return 0;
@@ -1786,6 +1800,24 @@ extern "C" bfc_ch_t *bfcg_export_table(bfcg_ctx_t *c)
 		bfc_ch_raw_recount(ch);
 		if (bfc_ch_count(ch) != c->h_stats[ST_KEYS]) { set_err("exported table holds %llu keys, the device counted %llu", (unsigned long long)bfc_ch_count(ch), (unsigned long long)c->h_stats[ST_KEYS]); bfc_ch_destroy(ch); return NULL; }
 	}
+	return ch;
+}
+
+// the host table the reference's API promises AND a copy of c->B.table that stays in HBM behind it, for bfcg_kcov_create (the corrector)
+// on the same device to adopt instead of uploading the same bytes again.  No room, or no free entry: the host copy alone is a complete answer.
+extern "C" bfc_ch_t *bfcg_export_table_resident(bfcg_ctx_t *c)
+{
+	bfc_ch_t *ch = bfcg_export_table(c);
+	if (!ch) return NULL;
+	const uint64_t bytes = 8ULL << (c->P.l_pre + c->P.tab_cshift);
+	void *dev = 0;
+	if (hipSetDevice(c->prm.device) != hipSuccess || hipMalloc(&dev, bytes) != hipSuccess) { (void)hipGetLastError(); return ch; }
+	if (hipMemcpyAsync(dev, c->B.table, bytes, hipMemcpyDeviceToDevice, c->st) != hipSuccess ||
+	    hipStreamSynchronize(c->st) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(dev); return ch; }
+	std::lock_guard<std::mutex> lk(g_res_mu);
+	for (int i = 0; i < 16; ++i)
+		if (!g_res[i].dev) { g_res[i] = resident_t{ch, dev, c->prm.device, 0, c->P.k, c->P.l_pre, c->P.tab_cshift}; g_res_n.fetch_add(1); return ch; }
+	(void)hipFree(dev); // registry full
 	return ch;
 }
 
@@ -1910,6 +1942,7 @@ extern "C" void *bfcg_trim_dev_seq(bfcg_trim_t *t) { return t->d_seq; }
 struct bfcg_kcov {
 	KParams P;
 	int device, owns_table;
+	int adopted;    // the table was already in HBM (left there by bfc_count), not uploaded
 	hipStream_t st;
 	unsigned long long *table;
 	uint8_t *d_seq, *d_flags;
@@ -1941,8 +1974,12 @@ extern "C" bfcg_kcov_t *bfcg_kcov_create(const bfc_ch_t *ch, int device, uint64_
 	if (!t) return NULL;
 	const uint64_t bytes = 8ULL << (t->P.l_pre + t->P.tab_cshift);
 	t->owns_table = 1;
-	HIPCKN(hipMalloc(&t->table, bytes));
-	HIPCKN(hipMemcpy(t->table, bfc_ch_raw_slots((bfc_ch_t *)ch), bytes, hipMemcpyHostToDevice));
+	t->table = (unsigned long long *)resident_take_table(ch, device, t->P.k, t->P.l_pre, t->P.tab_cshift); // left in HBM by bfc_count (bfcg_export_table_resident)?
+	t->adopted = t->table != 0;
+	if (!t->table) {
+		HIPCKN(hipMalloc(&t->table, bytes));
+		HIPCKN(hipMemcpy(t->table, bfc_ch_raw_slots((bfc_ch_t *)ch), bytes, hipMemcpyHostToDevice));
+	}
 	return t;
 }
 
@@ -1990,6 +2027,9 @@ extern "C" float bfcg_kcov_last_ms(bfcg_kcov_t *t) { return t->last_ms; }
 // the corrector (bfcg_ec.hip) runs behind a coverage context: its table in HBM, the probe parameters, the device it lives on
 namespace bfcg {
 const unsigned long long *kcov_table(bfcg_kcov_t *t, KParams *P, int *device) { *P = t->P; *device = t->device; return t->table; }
+int kcov_adopted(bfcg_kcov_t *t) { return t->adopted; }
+// k of a table-mode context, -1 for a filter-mode one: what bfcg_ec_attach checks before anything is drained or converted
+int ctx_table_k(bfcg_ctx_t *c) { return c->P.filter_mode ? -1 : c->P.k; }
 // the table read-out (bfcg_kmers.hip) borrows a counting context's table as bfcg_kcov_attach does: drained, in the host's layout, not exported
 const unsigned long long *ctx_borrow_table(bfcg_ctx_t *c, KParams *P, int *device)
 {

@@ -11,6 +11,11 @@
 // may come from the quality string (bfcg_ec1.h), so the coverage pass gets a decoded copy of the stream (k_decode writes it into the
 // bfcg_kcov_t's input buffer) and k_ec<true> corrects the original bytes in a buffer of their own: a read it leaves alone comes back as
 // it was.
+//
+// A corrector attached to a counting context (bfcg_ec_attach) reads the context's table where it lies and has no host table, so the host
+// instance cannot take the reads k_ec left: they go to k_ec_retry, the same per-read code on a list of read indices, with capacities
+// that grow 4x per round as host_ec1's do -- a quarter of the lanes, each with four times the slice of the same workspace -- until no
+// read is left (ec_retry).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -25,7 +30,11 @@
 using namespace ec1k;
 
 extern "C" void bfcg_set_error(const char *msg);
-namespace bfcg { const unsigned long long *kcov_table(bfcg_kcov_t *t, KParams *P, int *device); }
+namespace bfcg {
+const unsigned long long *kcov_table(bfcg_kcov_t *t, KParams *P, int *device);
+int kcov_adopted(bfcg_kcov_t *t);
+int ctx_table_k(bfcg_ctx_t *c);
+}
 
 static int ec_err(const char *fmt, ...)
 {
@@ -134,6 +143,37 @@ __global__ __launch_bounds__(EC_BT) void k_ec(Opt o, int l_pre, int cshift, cons
 	if (n_host) atomicAdd(&ctr[2], (unsigned long long)n_host);
 }
 
+// The reads k_ec left (aux2 = BFCG_EC_FALLBACK), by index: list[0 .. n_list).  n_lanes lanes (any number: the grid's last workgroup may be
+// partly idle) with hcap / scap / lmax of this round.  ctr[0]: next list entry; ctr[1]: table lookups; ctr[2]: reads that still do not fit
+// (they keep aux2 = BFCG_EC_FALLBACK and their bytes).  The coverage is the batch's, which k_ec read too.
+template <bool RF>
+__global__ __launch_bounds__(EC_BT) void k_ec_retry(Opt o, int l_pre, int cshift, const unsigned long long *__restrict__ tab, uint8_t *seq, uint8_t *qual,
+                                                    const uint16_t *__restrict__ cov, const uint64_t *__restrict__ off, const uint64_t *__restrict__ list,
+                                                    uint64_t n_list, uint32_t *__restrict__ aux, uint32_t *__restrict__ aux2, Heap1 *heap_ws, Stack1 *stack_ws,
+                                                    uint8_t *ec_ws, int hcap, int scap, int lmax, uint64_t n_lanes, unsigned long long *ctr,
+                                                    const uint32_t *__restrict__ ori_aux, const uint32_t *__restrict__ ori_aux2)
+{
+	const uint64_t lane = (uint64_t)blockIdx.x * EC_BT + threadIdx.x;
+	if (lane >= n_lanes) return;
+	unsigned n_look = 0, n_left = 0;
+	const DevLookup lk = {o.k, l_pre, cshift, tab, &n_look};
+	Work w;
+	w.heap = heap_ws + lane * (uint64_t)hcap; w.stack = stack_ws + lane * (uint64_t)scap; w.hcap = hcap; w.scap = scap;
+	uint8_t *ec0 = ec_ws + lane * 2 * (uint64_t)lmax, *ec1b = ec0 + lmax;
+	for (;;) {
+		const uint64_t i = atomicAdd(&ctr[0], 1ULL);
+		if (i >= n_list) break;
+		const uint64_t r = list[i], a = off[r];
+		const int n = (int)(off[r + 1] - a - 1);
+		Result res, ori;
+		if (RF) { ori.aux = ori_aux[r]; ori.aux2 = ori_aux2[r]; }
+		if (n > lmax || ec1<RF>(o, seq + a, qual ? qual + a : nullptr, cov + a, n, lk, w, ec0, ec1b, &res, ori) != EC_OK) { ++n_left; continue; }
+		aux[r] = res.aux; aux2[r] = res.aux2;
+	}
+	atomicAdd(&ctr[1], (unsigned long long)n_look);
+	if (n_left) atomicAdd(&ctr[2], (unsigned long long)n_left);
+}
+
 // the bases refinement reads (base_at<true>) as sequence bytes, for the coverage pass: one wavefront per read, separators copied as they are
 enum { DEC_BT = 256, DEC_W = 64 };
 __global__ __launch_bounds__(DEC_BT) void k_decode(const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual, const uint64_t *__restrict__ off,
@@ -148,12 +188,12 @@ __global__ __launch_bounds__(DEC_BT) void k_decode(const uint8_t *__restrict__ s
 
 struct bfcg_ec {
 	bfcg_kcov_t *kc;
-	const bfc_ch_t *ch;
+	const bfc_ch_t *ch;                                        // NULL: attached to a counting context's table (no host instance: ec_retry)
 	Opt o;
 	bfcg::KParams P;
 	const unsigned long long *tab;
 	int device, hcap, scap, lmax;
-	uint64_t lanes, max_pos, max_reads;
+	uint64_t lanes, max_pos, max_reads, ec_bytes;              // ec_bytes: d_ec's size (ec_retry grows it for reads longer than lmax)
 	hipStream_t st;
 	hipEvent_t e0, e1;
 	uint8_t *d_qual, *d_ec;
@@ -166,7 +206,8 @@ struct bfcg_ec {
 	Stack1 *d_stack;
 	unsigned long long *d_ctr;
 	float last_ms;
-	uint64_t host_reads, last_lookups, last_host;
+	uint64_t host_reads, last_lookups, last_host, retry_reads;
+	uint64_t *d_list, list_cap;                                // ec_retry: the listed reads
 };
 
 static int env_int(const char *name, int dflt, int lo, int hi)
@@ -182,7 +223,7 @@ extern "C" void bfcg_ec_destroy(bfcg_ec_t *e)
 	if (e->st) { (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->st); }
 	(void)hipFree(e->d_qual); (void)hipFree(e->d_ec); (void)hipFree(e->d_off); (void)hipFree(e->d_aux); (void)hipFree(e->d_aux2);
 	(void)hipFree(e->d_heap); (void)hipFree(e->d_stack); (void)hipFree(e->d_ctr);
-	(void)hipFree(e->d_oseq); (void)hipFree(e->d_oaux); (void)hipFree(e->d_oaux2);
+	(void)hipFree(e->d_oseq); (void)hipFree(e->d_oaux); (void)hipFree(e->d_oaux2); (void)hipFree(e->d_list);
 	if (e->st) { (void)hipEventDestroy(e->e0); (void)hipEventDestroy(e->e1); (void)hipStreamDestroy(e->st); }
 	bfcg_kcov_destroy(e->kc);
 	free(e);
@@ -190,18 +231,10 @@ extern "C" void bfcg_ec_destroy(bfcg_ec_t *e)
 
 #define ECN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ec_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); bfcg_ec_destroy(e); return NULL; } } while (0)
 
-extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, int device, uint64_t max_pos, uint64_t max_reads)
+// what both kinds of corrector share, once e->kc (and e->ch) are set: options, capacities, buffers
+static bfcg_ec_t *ec_setup(bfcg_ec_t *e, const bfc_opt_t *opt, int mode, uint64_t max_pos, uint64_t max_reads)
 {
-	if (!ch || !opt || opt->k != bfc_ch_get_k(ch) || max_pos == 0 || max_reads == 0 || opt->filter_mode) {
-		ec_err("bad arguments to bfcg_ec_create (a table-mode bfc_opt_t whose k is the table's)");
-		return NULL;
-	}
-	bfcg_ec_t *e = (bfcg_ec_t *)calloc(1, sizeof(bfcg_ec_t));
-	e->kc = bfcg_kcov_create(ch, device, max_pos);                 // uploads the table once (and says so if there is no GPU)
-	if (!e->kc) { free(e); return NULL; }
-	uint64_t hist[256], hist_high[64];
-	e->ch = ch;
-	e->o = ec_opt(opt, bfc_ch_hist(ch, hist, hist_high));        // correct.c:627
+	e->o = ec_opt(opt, mode);
 	e->refine = opt->refine_ec != 0;
 	e->tab = bfcg::kcov_table(e->kc, &e->P, &e->device);
 	e->max_pos = max_pos; e->max_reads = max_reads;
@@ -219,13 +252,145 @@ extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, i
 	ECN(hipMalloc(&e->d_aux, max_reads * 4)); ECN(hipMalloc(&e->d_aux2, max_reads * 4));
 	ECN(hipMalloc(&e->d_heap, sizeof(Heap1) * e->lanes * (uint64_t)e->hcap));
 	ECN(hipMalloc(&e->d_stack, sizeof(Stack1) * e->lanes * (uint64_t)e->scap));
-	ECN(hipMalloc(&e->d_ec, e->lanes * 2 * (uint64_t)e->lmax));
+	e->ec_bytes = e->lanes * 2 * (uint64_t)e->lmax;
+	ECN(hipMalloc(&e->d_ec, e->ec_bytes));
 	ECN(hipMalloc(&e->d_ctr, 3 * sizeof(unsigned long long)));
 	if (e->refine) {
 		ECN(hipMalloc(&e->d_oseq, max_pos));
 		ECN(hipMalloc(&e->d_oaux, max_reads * 4)); ECN(hipMalloc(&e->d_oaux2, max_reads * 4));
 	}
 	return e;
+}
+
+extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, int device, uint64_t max_pos, uint64_t max_reads)
+{
+	if (!ch || !opt || opt->k != bfc_ch_get_k(ch) || max_pos == 0 || max_reads == 0 || opt->filter_mode) {
+		ec_err("bad arguments to bfcg_ec_create (a table-mode bfc_opt_t whose k is the table's)");
+		return NULL;
+	}
+	bfcg_ec_t *e = (bfcg_ec_t *)calloc(1, sizeof(bfcg_ec_t));
+	e->kc = bfcg_kcov_create(ch, device, max_pos);                 // uploads the table once, or adopts the copy bfc_count left (and says so if there is no GPU)
+	if (!e->kc) { free(e); return NULL; }
+	uint64_t hist[256], hist_high[64];
+	e->ch = ch;
+	return ec_setup(e, opt, bfc_ch_hist(ch, hist, hist_high), max_pos, max_reads); // correct.c:627
+}
+
+// A corrector on the table of a counting context, where the count kernels built it (bfcg_kcov_attach's contract: the context is drained,
+// its segments converted, it must outlive the corrector and must not count meanwhile).  Nothing is exported: the mode comes from one
+// pass of k_tab_hist, and the reads k_ec leaves go to k_ec_retry.
+extern "C" bfcg_ec_t *bfcg_ec_attach(bfcg_ctx_t *ctx, const bfc_opt_t *opt, uint64_t max_pos, uint64_t max_reads)
+{
+	if (!ctx || !opt || max_pos == 0 || max_reads == 0 || opt->filter_mode) {
+		ec_err("bad arguments to bfcg_ec_attach (a counting context and a table-mode bfc_opt_t)");
+		return NULL;
+	}
+	const int k = bfcg::ctx_table_k(ctx);
+	if (k < 0) { ec_err("bfcg_ec_attach needs a table-mode context"); return NULL; }
+	if (opt->k != k) { ec_err("bfcg_ec_attach: opt->k is %d, the context counts %d-mers", opt->k, k); return NULL; }
+	bfcg_kmers_t *km = bfcg_kmers_attach(ctx);                     // drains the context and converts its segments
+	if (!km) return NULL;
+	uint64_t hist[256], hist_high[64];
+	const int mode = bfcg_kmers_hist(km, hist, hist_high);       // bfc_ch_hist's mode (correct.c:627), read once
+	bfcg_kmers_destroy(km);
+	if (mode < -1) return NULL;
+	bfcg_ec_t *e = (bfcg_ec_t *)calloc(1, sizeof(bfcg_ec_t));
+	e->kc = bfcg_kcov_attach(ctx, max_pos);
+	if (!e->kc) { free(e); return NULL; }
+	return ec_setup(e, opt, mode, max_pos, max_reads);
+}
+
+// An attached corrector's answer for the reads k_ec left (aux2[r] == BFCG_EC_FALLBACK in the host's copy, which is refreshed here): rounds of
+// k_ec_retry over the list of those reads.  Every round has 4x the heap and stack entries per lane of the one before, as host_ec1's loop,
+// and an lmax that covers the longest read listed.  The workspace is the corrector's own while a lane's slice fits it -- the arrays are
+// lane-major, so a quarter of the lanes get four times the slice -- and a larger one after that, for at most 64 lanes (*big_heap /
+// *big_stack: the caller frees them).  An allocation that fails ends the batch with an error that names the read; the host's streams have
+// not been written by then.
+enum { EC_RETRY_BIG_LANES = 64, EC_RETRY_MAX_CAP = 1 << 28 };
+static int ec_retry_rounds(bfcg_ec_t *e, const char *fn, int rf, uint8_t *d_seq, uint8_t *d_qual, const uint16_t *d_cov, const uint64_t *off, uint64_t n_reads,
+                           uint32_t *aux2, uint64_t *list, Heap1 **big_heap, Stack1 **big_stack)
+{
+	uint64_t n_list = 0;
+	for (uint64_t r = 0; r < n_reads; ++r) if (aux2[r] == BFCG_EC_FALLBACK) list[n_list++] = r;
+	const uint64_t n_first = n_list;
+	if (n_list > e->list_cap) {
+		(void)hipFree(e->d_list); e->d_list = nullptr; e->list_cap = 0;
+		ECK(hipMalloc(&e->d_list, n_list * 8));
+		e->list_cap = n_list;
+	}
+	uint64_t lanes = e->lanes, hcap = (uint64_t)e->hcap, scap = (uint64_t)e->scap;
+	int big = 0;                                                 // the rounds have left the corrector's workspace
+	while (n_list) {
+		hcap *= 4; scap *= 4;
+		if (hcap > EC_RETRY_MAX_CAP || scap > EC_RETRY_MAX_CAP)
+			return ec_err("%s: read %llu does not fit a search of 2^28 heap or stack entries", fn, (unsigned long long)list[0]);
+		int lmax = e->lmax;
+		for (uint64_t i = 0; i < n_list; ++i) {
+			const int n = (int)(off[list[i] + 1] - off[list[i]] - 1);
+			if (n > lmax) lmax = n;
+		}
+		Heap1 *heap = e->d_heap;
+		Stack1 *stack = e->d_stack;
+		if (!big) lanes /= 4;
+		if (big || lanes == 0) {                                 // a single lane's slice no longer fits: a larger workspace for the reads that are left
+			big = 1;
+			lanes = n_list < EC_RETRY_BIG_LANES ? n_list : EC_RETRY_BIG_LANES;
+			for (;; lanes = 1) {
+				(void)hipFree(*big_heap); (void)hipFree(*big_stack); *big_heap = nullptr; *big_stack = nullptr;
+				if (hipMalloc(big_heap, sizeof(Heap1) * lanes * hcap) == hipSuccess && hipMalloc(big_stack, sizeof(Stack1) * lanes * scap) == hipSuccess) break;
+				(void)hipGetLastError();
+				if (lanes == 1)
+					return ec_err("%s: read %llu needs %llu heap and %llu stack entries, which the device cannot allocate", fn, (unsigned long long)list[0],
+					              (unsigned long long)hcap, (unsigned long long)scap);
+			}
+			heap = *big_heap; stack = *big_stack;
+		}
+		const uint64_t n_lanes = lanes < n_list ? lanes : n_list;
+		if (n_lanes * 2 * (uint64_t)lmax > e->ec_bytes) {        // grown for good: k_ec's lanes * 2 * e->lmax bytes still fit
+			uint8_t *d = nullptr;
+			if (hipMalloc(&d, n_lanes * 2 * (uint64_t)lmax) != hipSuccess) {
+				(void)hipGetLastError();
+				return ec_err("%s: read %llu: no room for the results of %llu lanes of %d bases", fn, (unsigned long long)list[0], (unsigned long long)n_lanes, lmax);
+			}
+			(void)hipFree(e->d_ec);
+			e->d_ec = d; e->ec_bytes = n_lanes * 2 * (uint64_t)lmax;
+		}
+		unsigned long long ctr[3];
+		ECK(hipMemsetAsync(e->d_ctr, 0, 3 * sizeof(unsigned long long), e->st));
+		ECK(hipMemcpyAsync(e->d_list, list, n_list * 8, hipMemcpyHostToDevice, e->st));
+		ECK(hipEventRecord(e->e0, e->st));
+		hipLaunchKernelGGL(rf ? k_ec_retry<true> : k_ec_retry<false>, dim3((unsigned)((n_lanes + EC_BT - 1) / EC_BT)), dim3(EC_BT), 0, e->st, e->o, e->P.l_pre,
+		                   e->P.tab_cshift, e->tab, d_seq, d_qual, d_cov, (const uint64_t *)e->d_off, (const uint64_t *)e->d_list, n_list, e->d_aux, e->d_aux2,
+		                   heap, stack, e->d_ec, (int)hcap, (int)scap, lmax, n_lanes, e->d_ctr, (const uint32_t *)e->d_oaux, (const uint32_t *)e->d_oaux2);
+		ECK(hipGetLastError());
+		ECK(hipEventRecord(e->e1, e->st));
+		ECK(hipMemcpyAsync(aux2, e->d_aux2, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+		ECK(hipMemcpyAsync(ctr, e->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->st));
+		ECK(hipStreamSynchronize(e->st));
+		float ms = 0;
+		ECK(hipEventElapsedTime(&ms, e->e0, e->e1));
+		e->last_ms += ms;
+		e->last_lookups += ctr[1];
+		uint64_t m = 0;
+		for (uint64_t i = 0; i < n_list; ++i) if (aux2[list[i]] == BFCG_EC_FALLBACK) list[m++] = list[i];
+		if (m != ctr[2]) return ec_err("%s: the retry kernel left %llu reads, their marks say %llu", fn, ctr[2], (unsigned long long)m);
+		n_list = m;
+	}
+	e->retry_reads += n_first;
+	return 0;
+}
+
+static int ec_retry(bfcg_ec_t *e, const char *fn, int rf, uint8_t *d_seq, uint8_t *d_qual, const uint16_t *d_cov, const uint64_t *off, uint64_t n_reads,
+                    uint32_t *aux2, uint64_t n_left)
+{
+	uint64_t *list = (uint64_t *)malloc(n_left * 8);
+	if (!list) return ec_err("%s: out of host memory", fn);
+	Heap1 *big_heap = nullptr;
+	Stack1 *big_stack = nullptr;
+	const int rc = ec_retry_rounds(e, fn, rf, d_seq, d_qual, d_cov, off, n_reads, aux2, list, &big_heap, &big_stack);
+	(void)hipFree(big_heap); (void)hipFree(big_stack);
+	free(list);
+	return rc;
 }
 
 // seq / qual: host streams of n_pos positions in the batch format of PART 2 (qual NULL: no read has a quality string); rewritten in place.
@@ -281,9 +446,12 @@ static int ec_batch(bfcg_ec_t *e, const char *fn, uint8_t *seq, uint8_t *qual, u
 	ECK(hipGetLastError());
 	ECK(hipEventRecord(e->e1, e->st));
 	unsigned long long ctr[3];
-	ECK(hipMemcpyAsync(seq, d_ec_seq, n_pos, hipMemcpyDeviceToHost, e->st));
-	if (qual) ECK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
-	ECK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+	const int attached = e->ch == nullptr;                       // the streams leave the device behind the retry rounds, if there are any
+	if (!attached) {
+		ECK(hipMemcpyAsync(seq, d_ec_seq, n_pos, hipMemcpyDeviceToHost, e->st));
+		if (qual) ECK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
+		ECK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+	}
 	ECK(hipMemcpyAsync(aux2, e->d_aux2, n_reads * 4, hipMemcpyDeviceToHost, e->st));
 	ECK(hipMemcpyAsync(ctr, e->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->st));
 	ECK(hipStreamSynchronize(e->st));
@@ -291,6 +459,14 @@ static int ec_batch(bfcg_ec_t *e, const char *fn, uint8_t *seq, uint8_t *qual, u
 	ECK(hipEventElapsedTime(&ms, e->e0, e->e1));
 	e->last_ms = ms_cov + ms;
 	e->last_lookups = ctr[1];
+	if (attached) {                                              // no host table: the reads k_ec left are corrected on the device too
+		if (ctr[2] && ec_retry(e, fn, rf, d_ec_seq, qual ? e->d_qual : nullptr, d_cov, off, n_reads, aux2, ctr[2]) != 0) return -1;
+		ECK(hipMemcpyAsync(seq, d_ec_seq, n_pos, hipMemcpyDeviceToHost, e->st));
+		if (qual) ECK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
+		ECK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+		ECK(hipStreamSynchronize(e->st));
+		return 0;
+	}
 	for (uint64_t r = 0; r < n_reads; ++r) {                     // the reads the device left to the host instance
 		if (aux2[r] != BFCG_EC_FALLBACK) continue;
 		const uint64_t a = off[r];
@@ -319,3 +495,5 @@ extern "C" int bfcg_ec_batch_refine(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, u
 extern "C" float bfcg_ec_last_ms(bfcg_ec_t *e) { return e->last_ms; }
 extern "C" uint64_t bfcg_ec_host_reads(bfcg_ec_t *e) { return e->host_reads; }
 extern "C" uint64_t bfcg_ec_last_lookups(bfcg_ec_t *e) { return e->last_lookups; }
+extern "C" uint64_t bfcg_ec_retry_reads(bfcg_ec_t *e) { return e->retry_reads; }
+extern "C" int bfcg_ec_adopted(bfcg_ec_t *e) { return bfcg::kcov_adopted(e->kc); }

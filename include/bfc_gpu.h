@@ -241,6 +241,10 @@ bfc_bf_t *bfcg_export_bloom(bfcg_ctx_t *c, int which);   /* host bfc_bf_t (calle
 bfc_bf_t *bfcg_export_bloom_resident(bfcg_ctx_t *c, int which);
 void bfcg_resident_drop(const void *bf);                   /* drop the HBM copy behind a host filter, if there is one */
 bfc_ch_t *bfcg_export_table(bfcg_ctx_t *c);              /* host bfc_ch_t (caller: bfc_ch_destroy) */
+/* the same, and a copy of the table stays in HBM behind the returned object until bfc_ch_destroy / a host bfc_ch_insert on it: the first
+ * bfcg_kcov_create / bfcg_ec_create on the same device adopts that copy instead of uploading 8 << (l_pre + cshift) bytes (bfc_count ->
+ * bfc_correct); a second one uploads.  Without room for the copy the host table alone is returned.  bfcg_resident_drop drops it too. */
+bfc_ch_t *bfcg_export_table_resident(bfcg_ctx_t *c);
 
 /* Ingest only, no GPU: parses `fn` (FASTA/FASTQ, plain or gzip) into the batches bfc_count would submit -- kseq's grammar
  * (kseq.h:185-224) and bseq_read's batch boundary (bseq.c:52-76) -- and digests them: out[0] batches, [1] reads, [2] stream positions,
@@ -313,14 +317,24 @@ void *bfcg_kcov_dev_out(bfcg_kcov_t *t);   /* device result of the last batch (m
  *   bfcg_ec1_host_refine: bfcg_ec1_host with one read's earlier stats (bfcg_ec1_host refuses refine_ec).
  *   bfcg_ec_parse_stats: worker_ec's test and parse_stats (correct.c:517-531, 542-543) on a read's comment: returns 1 and the stats
  *   packed as above (rf_code 1, every field cut to ecstat_t's width as its bit-fields do: max_heap 300 is 44) if it starts with "ec:Z:",
- *   else 0 (aux / aux2 untouched).  It never reads past the comment's NUL: fields missing at its end are 0, where the reference reads on. */
+ *   else 0 (aux / aux2 untouched).  It never reads past the comment's NUL: fields missing at its end are 0, where the reference reads on.
+ * A corrector on a counting context's table, with no host table (bfcg_ec_attach): bfcg_kcov_attach's contract -- a table-mode context, which
+ * is drained and whose segments are converted to the host's layout; it must outlive the corrector and must not count meanwhile.  opt->k
+ * must be the context's k, opt->filter_mode is refused (both before anything is drained), refine_ec is honoured as above.  Nothing is
+ * exported: the mode is bfc_ch_hist's, from one pass over the table on the device at attach, and the reads the device cannot hold are
+ * corrected by a second kernel over the list of those reads whose capacities grow 4x per round until none is left (bfcg_ec_retry_reads
+ * counts them; bfcg_ec_host_reads stays 0; bfcg_ec_last_ms / _last_lookups include those launches).  If the device cannot allocate what
+ * a read needs the batch fails with an error that names the read, and seq / qual are as they were given. */
 typedef struct bfcg_ec bfcg_ec_t;
 bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, int device, uint64_t max_pos, uint64_t max_reads);
+bfcg_ec_t *bfcg_ec_attach(bfcg_ctx_t *ctx, const bfc_opt_t *opt, uint64_t max_pos, uint64_t max_reads);
 int   bfcg_ec_batch(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, uint32_t *aux, uint32_t *aux2);
 void  bfcg_ec_destroy(bfcg_ec_t *e);
 float bfcg_ec_last_ms(bfcg_ec_t *e);          /* GPU time of the last batch: coverage + correction kernels (HIP events) */
 uint64_t bfcg_ec_host_reads(bfcg_ec_t *e);    /* reads the host fallback corrected, since creation */
 uint64_t bfcg_ec_last_lookups(bfcg_ec_t *e);  /* table lookups of the last batch's correction kernel (the coverage pass adds one per k-mer) */
+uint64_t bfcg_ec_retry_reads(bfcg_ec_t *e);   /* reads the retry kernel corrected, since creation (0 on a corrector made by bfcg_ec_create) */
+int   bfcg_ec_adopted(bfcg_ec_t *e);          /* 1 if the table was found resident in HBM (bfcg_export_table_resident: no upload) */
 int   bfcg_ec1_host(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t *aux, uint32_t *aux2);
 int   bfcg_ec_batch_refine(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads,
                            const uint32_t *ori_aux, const uint32_t *ori_aux2, uint32_t *aux, uint32_t *aux2);

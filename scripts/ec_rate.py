@@ -4,6 +4,9 @@
     python scripts/ec_rate.py --set c3      # c3's read set (seed 3, 248 Mbp, 30x) with c3's table (-k33 -b35), a sample of its reads
     python scripts/ec_rate.py --refine      # `bfc -R` (bfcg_ec_batch_refine): E. coli 30x's first pass (run here, on the GPU) with every
                                             # ec:Z:0 comment's max_heap set to 60, so that every read is refined, on that file's own table
+    python scripts/ec_rate.py --attach      # the hand-over from counting to correcting, timed from the end of the last count batch to the end
+                                            # of the first corrected batch, twice in this process on the same input: (a) export_table() +
+                                            # GpuCorrector(HostTable), (b) GpuCorrector(GpuCounter), i.e. bfcg_ec_attach (one JSON line)
 
 The table is counted on the GPU and exported to the host (bfcg_ec_create uploads it once).  GPU time is bfcg_ec_last_ms summed over
 batches (HIP events around the two kernels of a batch; inputs already staged); lookups are counted on the device.  The reference:
@@ -21,6 +24,7 @@ ap.add_argument("--set", default="ecoli", choices=["ecoli", "c3"])
 ap.add_argument("--reads", type=int, default=0, help="reads to correct on the GPU (0: ecoli all, c3 4M)")
 ap.add_argument("--ref-reads", type=int, default=200_000, help="reads the reference corrects (0: skip)")
 ap.add_argument("--batch", type=int, default=1 << 20, help="reads per bfcg_ec_batch")
+ap.add_argument("--attach", action="store_true", help="time the hand-over of the table to the corrector, exported and attached, and exit")
 ap.add_argument("--refine", action="store_true", help="then refine (-R) the first pass's output, every read (prints a second JSON line)")
 args = ap.parse_args()
 
@@ -30,11 +34,46 @@ rs = gen.ReadSet(seed=S["seed"], G=S["G"], cov=S["cov"])
 stride = rs.L + 1
 n_ec = args.reads or S["reads"] or rs.n_reads
 CH = 2_000_000
-g = bfc_amd.GpuCounter(S["k"], S["b"], max_batch_pos=CH * stride)
-for r0 in range(0, rs.n_reads, CH):
-    r1 = min(rs.n_reads, r0 + CH)
-    seq, qual, off = rs.reads(r0, r1)
-    g.count_host(bfc_amd.to_stream(seq, off), bfc_amd.to_stream(qual, off))
+
+
+def count_all():
+    g = bfc_amd.GpuCounter(S["k"], S["b"], max_batch_pos=CH * stride)
+    for r0 in range(0, rs.n_reads, CH):
+        r1 = min(rs.n_reads, r0 + CH)
+        seq, qual, off = rs.reads(r0, r1)
+        g.count_host(bfc_amd.to_stream(seq, off), bfc_amd.to_stream(qual, off))
+    return g
+
+
+if args.attach:
+    B = min(args.batch, n_ec)
+    seq, qual, off = rs.reads(0, B)
+    s0, q0 = bfc_amd.to_stream(seq, off), bfc_amd.to_stream(qual, off)
+    opt = bfc_amd.bfc_opt_init(); opt.k = S["k"]
+    res = dict(set=args.set, mode="attach", k=S["k"], b=S["b"], reads_counted=rs.n_reads, first_batch_reads=B)
+    outs = {}
+    for how in ("export", "attach"):
+        g = count_all()
+        g.sync()                                                 # the end of the last count batch
+        t1 = time.perf_counter()
+        t = g.export_table() if how == "export" else None
+        t2 = time.perf_counter()
+        c = bfc_amd.GpuCorrector(t if t is not None else g, opt, max_pos=B * stride, max_reads=B)
+        t3 = time.perf_counter()
+        outs[how] = c.correct_stream(s0.copy(), q0.copy(), np.arange(B + 1, dtype=np.uint64) * np.uint64(stride))
+        t4 = time.perf_counter()
+        km = bfc_amd.GpuKmers(g)                                 # (no upload: the context holds the same table in the host's layout by now)
+        res[how] = dict(hand_over_s=round(t4 - t1, 4), export_s=round(t2 - t1, 4), create_s=round(t3 - t2, 4), first_batch_s=round(t4 - t3, 4),
+                        first_batch_gpu_ms=round(c.last_ms(), 2), table_bytes=8 << (km.l_pre + km.cshift), mode=c.mode,
+                        host_reads=c.host_reads(), retry_reads=c.retry_reads())
+        km.close(); c.close(); g.close()
+        if t is not None:
+            t.close()
+    res["same_output"] = all(np.array_equal(a, b) for a, b in zip(outs["export"], outs["attach"]))
+    print(json.dumps(res))
+    sys.exit(0)
+
+g = count_all()
 t = g.export_table()
 g.close()
 print("[ec_rate] %s: %d reads counted, table exported (%.1fs)" % (args.set, rs.n_reads, time.time() - t0), file=sys.stderr, flush=True)
