@@ -9,8 +9,6 @@
 #include <stdarg.h>
 #include <sys/mman.h>
 #include <time.h>
-#include <atomic>
-#include <mutex>
 #include <vector>
 #include <thread>
 #include <vector>
@@ -25,14 +23,12 @@ enum { HO_MAX_PAGES = BFCG_HO_MAX_PAGES };
 enum { OP_FLAG_WORDS = 12, OP_STICKY = 8 }; // bfcg_ctx.op_flags: two slots of four words, the sticky poison word
 static double dbg_now(void) { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 static inline void set_seg_shift(KParams &P, int s, int blk_max) { P.seg_shift = s; P.seg_blk = s < blk_max ? s : blk_max; }
-static int set_err(const char *fmt, ...)
+int bfcg::fail(const char *fmt, ...)
 {
 	va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
 	fprintf(stderr, "[E::bfcg] %s\n", g_err);
 	return -1;
 }
-#define HIPCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return set_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define HIPCKN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return NULL; } } while (0)
 
 struct bfcg_ctx {
 	bfcg_params_t prm;
@@ -113,7 +109,7 @@ struct bfcg_ctx {
 };
 
 extern "C" const char *bfcg_last_error(void) { return g_err; }
-extern "C" void bfcg_set_error(const char *msg) { set_err("%s", msg); } // bfcg_mg.hip reports through the same channel
+extern "C" void bfcg_set_error(const char *msg) { fail("%s", msg); } // bfcg_mg.hip reports through the same channel
 
 extern "C" int bfcg_device_count(void)
 {
@@ -141,26 +137,27 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 	int ndev = 0;
 	const bool timing = getenv("BFC_GPU_TIMING") != 0; // (phase times on stderr, as bfc_count's)
 	const double t_c0 = dbg_now();
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err("no HIP device available: the counting path has no CPU fallback"); return NULL; }
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { fail("no HIP device available: the counting path has no CPU fallback"); return NULL; }
 	const double t_c1 = dbg_now();
-	if (prm->device < 0 || prm->device >= ndev) { set_err("device %d out of range (%d devices)", prm->device, ndev); return NULL; }
-	if (prm->k < 1 || prm->k > 63) { set_err("k=%d outside [1,63] (bfc.h:8, htab.c:23)", prm->k); return NULL; }
-	if (prm->bf_shift < 9 + 0 || prm->bf_shift > 37) { set_err("bf_shift=%d outside [9,37] (bbf.c:9, bfc.h:9)", prm->bf_shift); return NULL; }
-	if (prm->n_hashes < 1 || prm->n_hashes > 12) { set_err("n_hashes=%d outside [1,12]", prm->n_hashes); return NULL; }
-	if (prm->max_batch_pos == 0 || prm->max_batch_pos >= (1ULL << 32)) { set_err("max_batch_pos must be in [1, 2^32)"); return NULL; }
+	if (prm->device < 0 || prm->device >= ndev) { fail("device %d out of range (%d devices)", prm->device, ndev); return NULL; }
+	if (prm->k < 1 || prm->k > 63) { fail("k=%d outside [1,63] (bfc.h:8, htab.c:23)", prm->k); return NULL; }
+	if (prm->bf_shift < 9 + 0 || prm->bf_shift > 37) { fail("bf_shift=%d outside [9,37] (bbf.c:9, bfc.h:9)", prm->bf_shift); return NULL; }
+	if (prm->n_hashes < 1 || prm->n_hashes > 12) { fail("n_hashes=%d outside [1,12]", prm->n_hashes); return NULL; }
+	if (prm->max_batch_pos == 0 || prm->max_batch_pos >= (1ULL << 32)) { fail("max_batch_pos must be in [1, 2^32)"); return NULL; }
 	const int n_ranks = prm->n_ranks > 0 ? prm->n_ranks : 1;
 	int log2n = 0; while ((1 << log2n) < n_ranks) ++log2n;
-	if ((1 << log2n) != n_ranks || n_ranks > 64 || prm->rank < 0 || prm->rank >= n_ranks) { set_err("n_ranks=%d must be a power of two <= 64 and 0 <= rank=%d < n_ranks", n_ranks, prm->rank); return NULL; }
-	if (n_ranks > 1 && prm->max_batch_pos >= (1ULL << (32 - log2n))) { set_err("with %d ranks a batch holds < 2^%d positions", n_ranks, 32 - log2n); return NULL; }
-	HIPCKN(hipSetDevice(prm->device));
+	if ((1 << log2n) != n_ranks || n_ranks > 64 || prm->rank < 0 || prm->rank >= n_ranks) { fail("n_ranks=%d must be a power of two <= 64 and 0 <= rank=%d < n_ranks", n_ranks, prm->rank); return NULL; }
+	if (n_ranks > 1 && prm->max_batch_pos >= (1ULL << (32 - log2n))) { fail("with %d ranks a batch holds < 2^%d positions", n_ranks, 32 - log2n); return NULL; }
+	BFCG_CKN((void)0, hipSetDevice(prm->device));
 
 	bfcg_ctx_t *c = (bfcg_ctx_t *)calloc(1, sizeof(bfcg_ctx_t));
+	if (!c) { fail("out of host memory"); return NULL; }
 	c->prm = *prm;
 	KParams &P = c->P;
 	P.k = prm->k; P.q = prm->q; P.bf_shift = prm->bf_shift; P.n_hashes = prm->n_hashes; P.filter_mode = prm->filter_mode;
 	P.l_pre = clamp_lpre(prm->k, prm->l_pre);
 	if (!prm->filter_mode && 2 * prm->k < P.l_pre) { // htab.c:49-50 shifts by 2k - l_pre: negative, undefined in the reference itself
-		set_err("k=%d is too small for l_pre=%d: the count table needs 2k >= l_pre (htab.c:45-58)", prm->k, P.l_pre); free(c); return NULL;
+		fail("k=%d is too small for l_pre=%d: the count table needs 2k >= l_pre (htab.c:45-58)", prm->k, P.l_pre); bfcg_destroy(c); return NULL;
 	}
 	// geometry of the bloom kernel; environment overrides are tuning knobs, not semantics
 	{
@@ -177,9 +174,9 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 			const int f1 = atoi(e);
 			if (f1 >= 1 && f1 <= 10 && P.F - f1 >= 1 && P.F - f1 <= 10 && f1 >= log2n) { P.F1 = f1; P.F2 = P.F - f1; }
 		}
-		if (P.F1 > 10) { set_err("bf_shift=%d needs more than two scatter levels at region_shift=%d", P.bf_shift, P.R); free(c); return NULL; }
+		if (P.F1 > 10) { fail("bf_shift=%d needs more than two scatter levels at region_shift=%d", P.bf_shift, P.R); bfcg_destroy(c); return NULL; }
 		if (n_ranks > 1 && P.F2 == 0) { // with several ranks level 2 also gathers a bucket's records from the sources' blocks: it must exist
-			if (P.F <= log2n) { set_err("bf_shift=%d gives %d bloom regions: too few for %d ranks", P.bf_shift, 1 << P.F, n_ranks); free(c); return NULL; }
+			if (P.F <= log2n) { fail("bf_shift=%d gives %d bloom regions: too few for %d ranks", P.bf_shift, 1 << P.F, n_ranks); bfcg_destroy(c); return NULL; }
 			P.F1 = (P.F + 1) / 2 > log2n ? (P.F + 1) / 2 : log2n; P.F2 = P.F - P.F1;
 		}
 #ifdef BFCG_MEASURE
@@ -291,7 +288,7 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 	// their own, and under rocprofv3 the overlapped kernels stretch.  So: two streams for batches up to 2^28 positions.  BFCG_PIPELINE=0/1 overrides.
 	{ const char *e = getenv("BFCG_PIPELINE"); c->pipeline = e ? atoi(e) != 0 : prm->max_batch_pos <= (1ULL << 28); }
 
-	if (n_ranks > 1 && log2n > P.F1) { set_err("multi-GPU needs a two-level partition with 2^F1=%d >= n_ranks (bf_shift=%d is too small)", 1 << P.F1, P.bf_shift); free(c); return NULL; }
+	if (n_ranks > 1 && log2n > P.F1) { fail("multi-GPU needs a two-level partition with 2^F1=%d >= n_ranks (bf_shift=%d is too small)", 1 << P.F1, P.bf_shift); bfcg_destroy(c); return NULL; }
 	P.idx_rank = n_ranks > 1 ? (uint32_t)prm->rank << (32 - log2n) : 0u;
 	c->bloom_bytes = (1ULL << (P.bf_shift - 3)) >> log2n; // owner computes: this rank keeps 1/n_ranks of the regions
 
@@ -300,12 +297,12 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 	const int nb1 = 1 << P.F1, nfine = (1 << P.F) >> log2n; // fine buckets owned by this rank
 	// records arriving from all ranks for the owned buckets: hashing balances them; 25 % + 1 M head room, checked per batch
 	c->recv_cap = n_ranks > 1 ? B.max_kmers + B.max_kmers / 4 + (1u << 20) : B.max_kmers;
-	HIPCKN(hipStreamCreate(&c->st)); HIPCKN(hipStreamCreate(&c->stA)); HIPCKN(hipStreamCreate(&c->stC));
+	BFCG_CKN(bfcg_destroy(c), hipStreamCreate(&c->st)); BFCG_CKN(bfcg_destroy(c), hipStreamCreate(&c->stA)); BFCG_CKN(bfcg_destroy(c), hipStreamCreate(&c->stC));
 	for (int b = 0; b < 2; ++b) {
-		for (int i = 0; i < 7; ++i) HIPCKN(hipEventCreate(&c->evt[b][i]));
-		HIPCKN(hipEventCreateWithFlags(&c->evA[b], hipEventDisableTiming)); HIPCKN(hipEventCreateWithFlags(&c->evB[b], hipEventDisableTiming));
+		for (int i = 0; i < 7; ++i) BFCG_CKN(bfcg_destroy(c), hipEventCreate(&c->evt[b][i]));
+		BFCG_CKN(bfcg_destroy(c), hipEventCreateWithFlags(&c->evA[b], hipEventDisableTiming)); BFCG_CKN(bfcg_destroy(c), hipEventCreateWithFlags(&c->evB[b], hipEventDisableTiming));
 	}
-	HIPCKN(hipEventCreateWithFlags(&c->evCopy, hipEventDisableTiming));
+	BFCG_CKN(bfcg_destroy(c), hipEventCreateWithFlags(&c->evCopy, hipEventDisableTiming));
 	{
 		const uint64_t tile = (uint64_t)bfcg_tile_of_rw(c->rw / 4), tile1 = (uint64_t)bfcg_tile1_of_rw(c->rw / 4);
 		const uint64_t tiles1 = (prm->max_batch_pos + tile1 - 1) / tile1, chunks1 = (tiles1 + BFCG_SCAN_CH - 1) / BFCG_SCAN_CH;
@@ -313,14 +310,14 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 		// included -- up to the slabs' capacity, 9/8 of the batch (+ rounding) --, and the two-pass level 2 keeps a histogram row for every tile of that
 		const uint64_t rows2 = (c->recv_cap + c->recv_cap / 8) / tile + (uint64_t)nb1 * 16 + 8;
 		for (int b = 0; b < 2; ++b) {
-			HIPCKN(hipMalloc(&c->rows1[b], sizeof(uint32_t) * tiles1 * nb1));
-			HIPCKN(hipMalloc(&c->chunk1[b], sizeof(uint32_t) * chunks1 * nb1));
-			HIPCKN(hipMalloc(&c->start1[b], sizeof(uint32_t) * (nb1 + 1) * 2));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->rows1[b], sizeof(uint32_t) * tiles1 * nb1));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->chunk1[b], sizeof(uint32_t) * chunks1 * nb1));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->start1[b], sizeof(uint32_t) * (nb1 + 1) * 2));
 		}
 		B.rows1 = c->rows1[0]; B.chunk1 = c->chunk1[0]; B.start1 = c->start1[0]; B.row_base = B.start1 + nb1 + 1;
 		if (P.F2 > 0) {
-			HIPCKN(hipMalloc(&B.rows2, sizeof(uint32_t) * rows2 * (1u << P.F2)));
-			HIPCKN(hipMalloc(&B.start2, sizeof(uint32_t) * (nfine + 1)));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.rows2, sizeof(uint32_t) * rows2 * (1u << P.F2)));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.start2, sizeof(uint32_t) * (nfine + 1)));
 		}
 	}
 	{ // one-pass level 1: 8 slabs per bucket, together 9/8 of the batch's positions (a stream holds ~0.8 k-mers per position: a quarter of head room)
@@ -340,9 +337,9 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 	const uint64_t recs1_n = c->onepass_ok ? (uint64_t)c->op_cap * nb1 * 8 + (uint64_t)bfcg_tile1_of_rw(c->rw / 4) + 64 : B.max_kmers;
 	// (batches above 2^28 positions run on ONE stream -- c->pipeline -- so stage A of a batch never runs beside stage B of the one before: both
 	// slots share one level-1 buffer there, which leaves config c4 34 GB more for the hand-over log and the table's growth)
-	HIPCKN(hipMalloc(&c->recs1[0], recs1_n * c->rw));
+	BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->recs1[0], recs1_n * c->rw));
 	if (n_ranks == 1 && !c->pipeline) c->recs1[1] = c->recs1[0];
-	else HIPCKN(hipMalloc(&c->recs1[1], recs1_n * c->rw));
+	else BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->recs1[1], recs1_n * c->rw));
 	{ // a rank of a multi-GPU run partitions what it RECEIVES in one pass (level 2 is the owner's own stage B; level 1 feeds the exchange and stays two-pass)
 		const char *e = getenv("BFCG_ONEPASS");
 		c->mg_op2_ok = P.F2 > 0 && !(e && atoi(e) == 0); // (also the single rank of a group of one: bench.py with BFC_BENCH_FORCE_DIST, tests)
@@ -350,17 +347,17 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 	{ const char *e = getenv("BFCG_MG_SLABS"); c->mg_slab_ok = P.F2 > 0 && !(e && atoi(e) == 0); } // (a rank's level 1 in one pass: bfcg_mg_scatter_slabs; used by groups only)
 	if (c->onepass_ok || c->mg_slab_ok) {
 		for (int b = 0; b < 2; ++b) {
-			HIPCKN(hipMalloc(&c->op_cursor[b], sizeof(uint32_t) * (8 * nb1 * 32 + 32))); // (+ the tile counter of k_scatter1)
-			HIPCKN(hipMalloc(&c->op_seg[b], sizeof(uint32_t) * ((size_t)25 * nb1 + 8)));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->op_cursor[b], sizeof(uint32_t) * (8 * nb1 * 32 + 32))); // (+ the tile counter of k_scatter1)
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->op_seg[b], sizeof(uint32_t) * ((size_t)25 * nb1 + 8)));
 		}
 	}
-	if (c->mg_slab_ok) for (int b = 0; b < 2; ++b) HIPCKN(hipHostMalloc(&c->h_rows[b], sizeof(uint32_t) * ((size_t)8 * nb1 + 2 * (size_t)n_ranks)));
+	if (c->mg_slab_ok) for (int b = 0; b < 2; ++b) BFCG_CKN(bfcg_destroy(c), hipHostMalloc(&c->h_rows[b], sizeof(uint32_t) * ((size_t)8 * nb1 + 2 * (size_t)n_ranks)));
 	if (c->onepass_ok || c->mg_op2_ok || c->mg_slab_ok) {
-		for (int b = 0; b < 2; ++b) HIPCKN(hipHostMalloc(&c->h_flags[b], 4 * sizeof(uint32_t)));
+		for (int b = 0; b < 2; ++b) BFCG_CKN(bfcg_destroy(c), hipHostMalloc(&c->h_flags[b], 4 * sizeof(uint32_t)));
 		// per batch slot b: op_flags[4 b + 0] a level-1 slab overflowed (raised on stage A's stream), [4 b + 2] a region's slab (stage B's stream);
 		// op_flags[8]: the run is poisoned (k_seal, stage B's stream only) -- a batch's stage B never reads what another batch's stage A writes
-		HIPCKN(hipMalloc(&c->op_flags, OP_FLAG_WORDS * sizeof(uint32_t)));
-		HIPCKN(hipMemset(c->op_flags, 0, OP_FLAG_WORDS * sizeof(uint32_t)));
+		BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->op_flags, OP_FLAG_WORDS * sizeof(uint32_t)));
+		BFCG_CKN(bfcg_destroy(c), hipMemset(c->op_flags, 0, OP_FLAG_WORDS * sizeof(uint32_t)));
 	}
 	if (c->mg_op2_ok) for (int i = 0; i < 4; ++i) c->mg_seg[i] = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)n_ranks * (size_t)(nb1 >> log2n) * 8); // (slab fills: 8 per source and bucket)
 	B.recs1 = c->recs1[0];
@@ -370,14 +367,14 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 		const uint64_t cap2 = (B.max_kmers + B.max_kmers / 8) / (uint64_t)nfine + 64, n2 = cap2 * (uint64_t)nfine + 8192; // (a tile of slack: 8192 = the largest level-2 tile, KParams.l2_big)
 		if (!(e && atoi(e) == 0) && n2 < 0xffffffffULL) {
 			c->cap2 = (uint32_t)cap2; c->recs2_n = n2 > c->recv_cap ? n2 : c->recv_cap;
-			HIPCKN(hipMalloc(&c->cnt2, sizeof(uint32_t) * (size_t)nfine));
-		} else { c->mg_op2_ok = 0; HIPCKN(hipMalloc(&c->cnt2, sizeof(uint32_t) * (size_t)nfine)); } // (the counters also serve the two-pass level 2: BatchBufs.cnt_live)
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->cnt2, sizeof(uint32_t) * (size_t)nfine));
+		} else { c->mg_op2_ok = 0; BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->cnt2, sizeof(uint32_t) * (size_t)nfine)); } // (the counters also serve the two-pass level 2: BatchBufs.cnt_live)
 		B.cnt_live = c->cnt2;
 	}
-	if (P.F2 > 0) HIPCKN(hipMalloc(&B.recs2, c->recs2_n * c->rw));
+	if (P.F2 > 0) BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.recs2, c->recs2_n * c->rw));
 	c->seg_words = (size_t)25 * nb1 + 8; // (slab mode: 8 segments per source and bucket)
-	{ HIPCKN(hipMalloc(&c->d_seg, sizeof(uint32_t) * 2 * c->seg_words)); HIPCKN(hipHostMalloc(&c->h_seg, sizeof(uint32_t) * 2 * c->seg_words)); }
-	HIPCKN(hipMalloc(&B.bloom, c->bloom_bytes));
+	{ BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->d_seg, sizeof(uint32_t) * 2 * c->seg_words)); BFCG_CKN(bfcg_destroy(c), hipHostMalloc(&c->h_seg, sizeof(uint32_t) * 2 * c->seg_words)); }
+	BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.bloom, c->bloom_bytes));
 	P.f_base = (uint32_t)c->rank * (uint32_t)nfine;
 	if (c->seg_ok) { // segments start with a quarter of a batch's positions in slots, like the table below
 		int sh = prm->tab_cshift > 0 ? prm->tab_cshift + 3 : 6;
@@ -391,8 +388,8 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 		{ const char *e = getenv("BFCG_SEG_TOTAL"); c->seg_total_max = e && atoi(e) >= c->seg_blk_max && atoi(e) <= BFCG_SEG_TOTAL_MAX ? atoi(e) : BFCG_SEG_TOTAL_MAX; }
 		if (c->seg_total_max > c->seg_blk_max + 15) c->seg_total_max = c->seg_blk_max + 15; // (the blocks are a grid's second dimension: at most 65 535)
 		P.seg = 1; set_seg_shift(P, sh, c->seg_blk_max); c->seg_cap_shift = sh;
-		HIPCKN(set_seg_lds_attr());
-		HIPCKN(hipMalloc(&B.seg_tab, ((uint64_t)nfine << sh) * 8));
+		BFCG_CKN(bfcg_destroy(c), set_seg_lds_attr());
+		BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.seg_tab, ((uint64_t)nfine << sh) * 8));
 		{ // the hand-over log: ho_K pages per region where level 2 bounds a region's share of a batch (its slab), else one batch at its records' offsets
 			const char *e = getenv("BFCG_COMMIT_K");
 			int K = e ? atoi(e) : 4;
@@ -406,44 +403,44 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 			c->ho_stride = c->cap2 ? (uint32_t)K * c->cap2 : 0u;
 			uint64_t entries = (uint64_t)nfine * c->ho_stride;
 			if (entries < c->recs2_n) entries = c->recs2_n; // (two-pass batches hand over at their records' offsets)
-			HIPCKN(hipMalloc(&c->ho, (entries + 4096) * 8));
-			HIPCKN(hipMalloc(&c->ho_cur, sizeof(uint32_t) * (size_t)nfine));
-			HIPCKN(hipMalloc(&c->ho_mark, sizeof(uint32_t) * (size_t)nfine * HO_MAX_PAGES));
-			HIPCKN(hipMalloc(&c->ho_keys, sizeof(unsigned long long) * ST_SLOTS * HO_MAX_PAGES));
-			for (int b = 0; b < 2; ++b) HIPCKN(hipHostMalloc(&c->h_ho_keys[b], sizeof(unsigned long long) * ST_SLOTS * HO_MAX_PAGES));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->ho, (entries + 4096) * 8));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->ho_cur, sizeof(uint32_t) * (size_t)nfine));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->ho_mark, sizeof(uint32_t) * (size_t)nfine * HO_MAX_PAGES));
+			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->ho_keys, sizeof(unsigned long long) * ST_SLOTS * HO_MAX_PAGES));
+			for (int b = 0; b < 2; ++b) BFCG_CKN(bfcg_destroy(c), hipHostMalloc(&c->h_ho_keys[b], sizeof(unsigned long long) * ST_SLOTS * HO_MAX_PAGES));
 		}
 	}
-	if (P.filter_mode) HIPCKN(hipMalloc(&B.bloom_hi, c->bloom_bytes));
-	else if (!c->seg_ok) HIPCKN(hipMalloc(&B.table, 8ULL << (P.l_pre + P.tab_cshift)));
-	if (P.track) { HIPCKN(hipMalloc(&B.tab_first, 8ULL << (P.l_pre + P.tab_cshift))); HIPCKN(hipMalloc(&B.sub_last, 8ULL << P.l_pre)); }
-	HIPCKN(hipMalloc(&B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1))); // last row: unslotted words
+	if (P.filter_mode) BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.bloom_hi, c->bloom_bytes));
+	else if (!c->seg_ok) BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.table, 8ULL << (P.l_pre + P.tab_cshift)));
+	if (P.track) { BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.tab_first, 8ULL << (P.l_pre + P.tab_cshift))); BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.sub_last, 8ULL << P.l_pre)); }
+	BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1))); // last row: unslotted words
 	// parked k-mers of a batch that outruns the table (the host grows it and replays them): a batch cannot create more keys than
 	// half its k-mers, bloom false positives aside
 	{ uint64_t cap = prm->max_batch_pos / 2; if (cap < (1u << 20)) cap = 1u << 20; if (cap > (1u << 28)) cap = 1u << 28; B.tab_ovf_cap = (uint32_t)cap; }
-	HIPCKN(hipMalloc(&B.tab_ovf, (uint64_t)B.tab_ovf_cap * 40));
+	BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.tab_ovf, (uint64_t)B.tab_ovf_cap * 40));
 	// HBM first-setter pool for regions whose LDS tables overflow: 256 slices of 2 entries per region bit (the most a region can need), each
 	// behind a lock word.  A workgroup takes any free slice and waits for one if all are taken (their holders never wait for anything), so no
 	// input can exhaust the pool; 512 MiB instead of the 2 GiB that one slice per possibly resident workgroup cost at every context creation
 	B.pool_slices = 256;
 	{
 		const uint64_t pool_words = (uint64_t)B.pool_slices + (uint64_t)B.pool_slices * ((uint64_t)1024 << P.R);
-		HIPCKN(hipMalloc(&B.pool, pool_words * 8));
-		HIPCKN(hipMemset(B.pool, 0, (size_t)B.pool_slices * 8));
+		BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.pool, pool_words * 8));
+		BFCG_CKN(bfcg_destroy(c), hipMemset(B.pool, 0, (size_t)B.pool_slices * 8));
 	}
-	if (prm->debug_seen) HIPCKN(hipMalloc(&B.seen_out, prm->max_batch_pos));
+	if (prm->debug_seen) BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.seen_out, prm->max_batch_pos));
 	if (!P.filter_mode) { // filter mode hands nothing over: both filters' slices are in LDS
 		// (the aggregation buffer of the host-layout commit -- 1.6 GB at -b35, 6.4 GB at -b37 -- is allocated when a batch first needs it:
 		// a context on region-owned segments never does unless its table escapes to the host's layout: ensure_agg)
-		if (!c->seg_ok) HIPCKN(hipMalloc(&B.agg_out, (uint64_t)nfine * P.ag_cap * (P.track ? 32 : 24)));
-		HIPCKN(hipMalloc(&B.agg_cnt, sizeof(uint32_t) * nfine));
+		if (!c->seg_ok) BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.agg_out, (uint64_t)nfine * P.ag_cap * (P.track ? 32 : 24)));
+		BFCG_CKN(bfcg_destroy(c), hipMalloc(&B.agg_cnt, sizeof(uint32_t) * nfine));
 	}
-	for (int b = 0; b < 2; ++b) { HIPCKN(hipMalloc(&c->d_seq2[b], prm->max_batch_pos)); HIPCKN(hipMalloc(&c->d_qual2[b], prm->max_batch_pos + 64)); }
+	for (int b = 0; b < 2; ++b) { BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->d_seq2[b], prm->max_batch_pos)); BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->d_qual2[b], prm->max_batch_pos + 64)); }
 	c->d_seq = c->d_seq2[0]; c->d_qual = c->d_qual2[0];
-	HIPCKN(hipHostMalloc(&c->h_stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 2)));
-	for (int b = 0; b < 2; ++b) HIPCKN(hipHostMalloc(&c->h_snap[b], sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1)));
+	BFCG_CKN(bfcg_destroy(c), hipHostMalloc(&c->h_stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 2)));
+	for (int b = 0; b < 2; ++b) BFCG_CKN(bfcg_destroy(c), hipHostMalloc(&c->h_snap[b], sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1)));
 	const double t_c2 = dbg_now();
-	HIPCKN(set_bloom_lds_attr(P));
-	HIPCKN(set_scatter1wc_lds_attr());
+	BFCG_CKN(bfcg_destroy(c), set_bloom_lds_attr(P));
+	BFCG_CKN(bfcg_destroy(c), set_scatter1wc_lds_attr());
 	const double t_c3 = dbg_now();
 	if (bfcg_reset(c) != 0) { bfcg_destroy(c); return NULL; }
 	if (timing) fprintf(stderr, "[T::bfcg_create] HIP runtime up %.3f s, device buffers %.3f s, kernel attributes %.3f s, filter and table cleared %.3f s\n", t_c1 - t_c0, t_c2 - t_c1, t_c3 - t_c2, dbg_now() - t_c3);
@@ -464,10 +461,11 @@ extern "C" void bfcg_destroy(bfcg_ctx_t *c)
 	for (int b = 0; b < 2; ++b) { (void)hipFree(c->op_cursor[b]); (void)hipFree(c->op_seg[b]); if (c->h_flags[b]) (void)hipHostFree(c->h_flags[b]); if (c->h_rows[b]) (void)hipHostFree(c->h_rows[b]); }
 	(void)hipFree(c->op_flags); (void)hipFree(c->cnt2); for (int i = 0; i < 4; ++i) free(c->mg_seg[i]);
 	(void)hipFree(c->B.tab_ovf); (void)hipFree(c->B.pool); (void)hipFree(c->B.seen_out); (void)hipFree(c->B.agg_out); (void)hipFree(c->B.agg_cnt);
-	(void)hipHostFree(c->h_stats); (void)hipHostFree(c->h_snap[0]); (void)hipHostFree(c->h_snap[1]); (void)hipFree(c->d_seg); if (c->h_seg) (void)hipHostFree(c->h_seg);
-	for (int b = 0; b < 2; ++b) { for (int i = 0; i < 7; ++i) (void)hipEventDestroy(c->evt[b][i]); (void)hipEventDestroy(c->evA[b]); (void)hipEventDestroy(c->evB[b]); }
-	(void)hipEventDestroy(c->evCopy);
-	(void)hipStreamDestroy(c->st); (void)hipStreamDestroy(c->stA); (void)hipStreamDestroy(c->stC);
+	for (void *h : {(void *)c->h_stats, (void *)c->h_snap[0], (void *)c->h_snap[1]}) if (h) (void)hipHostFree(h); (void)hipFree(c->d_seg); if (c->h_seg) (void)hipHostFree(c->h_seg);
+	// (a context whose creation failed half way has only some of its handles)
+	for (int b = 0; b < 2; ++b) for (hipEvent_t e : {c->evt[b][0], c->evt[b][1], c->evt[b][2], c->evt[b][3], c->evt[b][4], c->evt[b][5], c->evt[b][6], c->evA[b], c->evB[b]}) if (e) (void)hipEventDestroy(e);
+	if (c->evCopy) (void)hipEventDestroy(c->evCopy);
+	for (hipStream_t st : {c->st, c->stA, c->stC}) if (st) (void)hipStreamDestroy(st);
 	free(c);
 }
 
@@ -499,43 +497,43 @@ extern "C" int bfcg_reset(bfcg_ctx_t *c)
 {
 	const double t_dbg = dbg_now();
 	struct dbg_guard { double t; ~dbg_guard() { if (getenv("BFCG_DEBUG")) fprintf(stderr, "[D::reset] %.3f ms\n", (dbg_now() - t) * 1e3); } } dg{t_dbg};
-	HIPCK(hipSetDevice(c->prm.device));
+	BFCG_CK(hipSetDevice(c->prm.device));
 	if (c->pend && drain(c) != 0) return -1;
 	// the statistics first: stage A of the next batch (stream stA) adds to them and only has to wait for that small memset; the
 	// filters and the table are touched by stage B alone, on this same stream, so zeroing them needs no host synchronisation
-	HIPCK(hipMemsetAsync(c->B.stats, 0, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), c->st));
-	if (c->op_flags) HIPCK(hipMemsetAsync(c->op_flags, 0, OP_FLAG_WORDS * sizeof(uint32_t), c->st)); // stage A raises them: cleared before stage A's stream goes on
-	HIPCK(hipEventRecord(c->evCopy, c->st));
-	HIPCK(hipStreamWaitEvent(c->stA, c->evCopy, 0));
-	HIPCK(hipMemsetAsync(c->B.bloom, 0, c->bloom_bytes, c->st));
-	if (c->B.bloom_hi) HIPCK(hipMemsetAsync(c->B.bloom_hi, 0, c->bloom_bytes, c->st));
+	BFCG_CK(hipMemsetAsync(c->B.stats, 0, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), c->st));
+	if (c->op_flags) BFCG_CK(hipMemsetAsync(c->op_flags, 0, OP_FLAG_WORDS * sizeof(uint32_t), c->st)); // stage A raises them: cleared before stage A's stream goes on
+	BFCG_CK(hipEventRecord(c->evCopy, c->st));
+	BFCG_CK(hipStreamWaitEvent(c->stA, c->evCopy, 0));
+	BFCG_CK(hipMemsetAsync(c->B.bloom, 0, c->bloom_bytes, c->st));
+	if (c->B.bloom_hi) BFCG_CK(hipMemsetAsync(c->B.bloom_hi, 0, c->bloom_bytes, c->st));
 	if (c->seg_ok) { // back to region-owned segments of the initial size (a run that outgrew them, or an export, left the other layout behind)
 		const uint64_t nfine = ((uint64_t)1 << c->P.F) >> c->log2n;
 		if (c->seg_escaped || !c->B.seg_tab) {
-			HIPCK(hipStreamSynchronize(c->st));
-			if (c->B.table) { HIPCK(hipFree(c->B.table)); c->B.table = 0; }
-			if (c->B.seg_tab) { HIPCK(hipFree(c->B.seg_tab)); c->B.seg_tab = 0; }
+			BFCG_CK(hipStreamSynchronize(c->st));
+			if (c->B.table) { BFCG_CK(hipFree(c->B.table)); c->B.table = 0; }
+			if (c->B.seg_tab) { BFCG_CK(hipFree(c->B.seg_tab)); c->B.seg_tab = 0; }
 			set_seg_shift(c->P, c->seg_init_shift, c->seg_blk_max); c->seg_cap_shift = c->seg_init_shift;
-			HIPCK(hipMalloc(&c->B.seg_tab, (nfine << c->P.seg_shift) * 8));
+			BFCG_CK(hipMalloc(&c->B.seg_tab, (nfine << c->P.seg_shift) * 8));
 		} else {
 			set_seg_shift(c->P, c->seg_init_shift, c->seg_blk_max); // start small again inside the allocation the last run grew to (seg_cap_shift says how far it goes)
 			if (c->n_batches && c->seg_spare && c->seg_spare_shift < c->seg_cap_shift && ((nfine << c->seg_cap_shift) * 8) <= (16ULL << 30)) {
 				// second data set on this context: make the spare as large as the segments grew, so that this run's growths find their target ready
-				HIPCK(hipStreamSynchronize(c->st));
-				HIPCK(hipFree(c->seg_spare)); c->seg_spare = 0;
+				BFCG_CK(hipStreamSynchronize(c->st));
+				BFCG_CK(hipFree(c->seg_spare)); c->seg_spare = 0;
 				if (hipMalloc(&c->seg_spare, (nfine << c->seg_cap_shift) * 8) != hipSuccess) { (void)hipGetLastError(); c->seg_spare = 0; }
 				c->seg_spare_shift = c->seg_cap_shift;
 			}
 		}
 		if (c->n_batches) c->reused = 1;
 		c->P.seg = 1; c->P.b3 = c->b3_ok; c->seg_escaped = 0;
-		HIPCK(hipMemsetAsync(c->ho_cur, 0, sizeof(uint32_t) * (size_t)nfine, c->st));
+		BFCG_CK(hipMemsetAsync(c->ho_cur, 0, sizeof(uint32_t) * (size_t)nfine, c->st));
 		c->ho_pending = 0; c->slot_commit[0] = c->slot_commit[1] = 0; c->slot_all_committed[0] = c->slot_all_committed[1] = 0; c->keys_known = 0; c->commit_absorbed = 0;
 		c->keys_per_batch = 0; c->n_commits = 0; c->ho_window = 1;
-		HIPCK(hipMemsetAsync(c->B.seg_tab, 0, (nfine << c->P.seg_shift) * 8, c->st));
+		BFCG_CK(hipMemsetAsync(c->B.seg_tab, 0, (nfine << c->P.seg_shift) * 8, c->st));
 	}
-	if (c->B.table) HIPCK(hipMemsetAsync(c->B.table, 0, 8ULL << (c->P.l_pre + c->P.tab_cshift), c->st));
-	if (c->B.tab_first) { HIPCK(hipMemsetAsync(c->B.tab_first, 0xff, 8ULL << (c->P.l_pre + c->P.tab_cshift), c->st)); HIPCK(hipMemsetAsync(c->B.sub_last, 0, 8ULL << c->P.l_pre, c->st)); }
+	if (c->B.table) BFCG_CK(hipMemsetAsync(c->B.table, 0, 8ULL << (c->P.l_pre + c->P.tab_cshift), c->st));
+	if (c->B.tab_first) { BFCG_CK(hipMemsetAsync(c->B.tab_first, 0xff, 8ULL << (c->P.l_pre + c->P.tab_cshift), c->st)); BFCG_CK(hipMemsetAsync(c->B.sub_last, 0, 8ULL << c->P.l_pre, c->st)); }
 	c->n_batches = 0;
 	c->keys_last = 0; c->grow[0] = c->grow[1] = 0;
 	c->crowded_last = 0; c->stream_mode = c->P.seg ? 1 : 0;
@@ -549,8 +547,8 @@ extern "C" int bfcg_reset(bfcg_ctx_t *c)
 static int fetch_stats_on(bfcg_ctx_t *c, hipStream_t s)
 {
 	unsigned long long *raw = c->h_stats + ST_N;
-	HIPCK(hipMemcpyAsync(raw, c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, s));
-	HIPCK(hipStreamSynchronize(s));
+	BFCG_CK(hipMemcpyAsync(raw, c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, s));
+	BFCG_CK(hipStreamSynchronize(s));
 	for (int i = 0; i < ST_N; ++i) {
 		unsigned long long s = 0;
 		for (int j = 0; j < ST_SLOTS; ++j) s += raw[(size_t)j * ST_N + i];
@@ -594,8 +592,8 @@ static int batch_times(bfcg_ctx_t *c, int b)
 	// stage B's stream has been synchronised by the caller; the stage-A events of this slot sit on stream stA and are long complete when stage A
 	// did work, but an EMPTY stage A (a rank without a share, or the extra pairs of a batch processed in source groups) only records them,
 	// possibly behind that stream's wait for an older stage B: wait for them explicitly
-	for (int i = 0; i < 3; ++i) HIPCK(hipEventSynchronize(c->evt[b][i]));
-	for (int i = 0; i < 5; ++i) HIPCK(hipEventElapsedTime(&c->last_ms[i], c->evt[b][i == 2 ? 6 : i], c->evt[b][i + 1]));
+	for (int i = 0; i < 3; ++i) BFCG_CK(hipEventSynchronize(c->evt[b][i]));
+	for (int i = 0; i < 5; ++i) BFCG_CK(hipEventElapsedTime(&c->last_ms[i], c->evt[b][i == 2 ? 6 : i], c->evt[b][i + 1]));
 	c->last_ms[5] = c->last_ms[0] + c->last_ms[1] + c->last_ms[2] + c->last_ms[3] + c->last_ms[4]; // GPU time of the stages (they overlap across batches)
 	for (int i = 0; i < 6; ++i) c->sum_ms[i] += c->last_ms[i];
 	++c->n_timed;
@@ -603,7 +601,7 @@ static int batch_times(bfcg_ctx_t *c, int b)
 }
 static int check_health(bfcg_ctx_t *c)
 {
-	if (c->h_stats[ST_ERR_POOL]) return set_err("first-setter pool exhausted in %llu bloom regions: batch too large for max_batch_pos", (unsigned long long)c->h_stats[ST_ERR_POOL]);
+	if (c->h_stats[ST_ERR_POOL]) return fail("first-setter pool exhausted in %llu bloom regions: batch too large for max_batch_pos", (unsigned long long)c->h_stats[ST_ERR_POOL]);
 	if (c->P.seg) return seg_maintain(c);
 	if (c->B.table) return table_maintain(c);
 	return 0;
@@ -612,22 +610,22 @@ static int check_health(bfcg_ctx_t *c)
 static int drain(bfcg_ctx_t *c)
 {
 	if (!c->pend) return 0;
-	HIPCK(hipStreamSynchronize(c->stA));
-	HIPCK(hipStreamSynchronize(c->st));
-	HIPCK(hipGetLastError());
+	BFCG_CK(hipStreamSynchronize(c->stA));
+	BFCG_CK(hipStreamSynchronize(c->st));
+	BFCG_CK(hipGetLastError());
 	c->pend = 0;
 	if (batch_times(c, c->cur ^ 1) != 0) return -1;
 	absorb_pages(c, c->cur); absorb_pages(c, c->cur ^ 1); // (older slot first)
 	if (c->n_opq) { // batches that went through the one-pass partition: were their slabs large enough?
 		uint32_t sticky = 0;
-		HIPCK(hipMemcpy(&sticky, c->op_flags + OP_STICKY, sizeof(sticky), hipMemcpyDeviceToHost));
+		BFCG_CK(hipMemcpy(&sticky, c->op_flags + OP_STICKY, sizeof(sticky), hipMemcpyDeviceToHost));
 		if (sticky) return replay_poisoned(c);
 		c->n_opq = 0;
 	}
 	if (c->P.seg && c->ho_pending) { // what still waits in the hand-over log
 		if (commit_pending_pages(c, 0) != 0) return -1;
-		HIPCK(hipStreamSynchronize(c->st));
-		HIPCK(hipGetLastError());
+		BFCG_CK(hipStreamSynchronize(c->st));
+		BFCG_CK(hipGetLastError());
 		absorb_pages(c, 0);
 	}
 	if (fetch_stats(c) != 0) return -1;
@@ -651,10 +649,10 @@ static int replay_poisoned(bfcg_ctx_t *c)
 	c->n_opq = 0; c->onepass = 0; c->mg_op2 = 0;
 	if (getenv("BFCG_DEBUG")) {
 		uint32_t fl[OP_FLAG_WORDS];
-		HIPCK(hipMemcpy(fl, c->op_flags, sizeof(fl), hipMemcpyDeviceToHost));
+		BFCG_CK(hipMemcpy(fl, c->op_flags, sizeof(fl), hipMemcpyDeviceToHost));
 		fprintf(stderr, "[D::replay] %d batches; flags (level-1 slab, -, region slab, -) of slot 0: %u %u %u %u, slot 1: %u %u %u %u, sticky %u\n", n, fl[0], fl[1], fl[2], fl[3], fl[4], fl[5], fl[6], fl[7], fl[OP_STICKY]);
 	}
-	HIPCK(hipMemset(c->op_flags, 0, OP_FLAG_WORDS * sizeof(uint32_t)));
+	BFCG_CK(hipMemset(c->op_flags, 0, OP_FLAG_WORDS * sizeof(uint32_t)));
 	if (fetch_stats(c) != 0) return -1;
 	c->n_batches -= (uint64_t)n; // the batches keep their places in the count (order stamps carry the batch number)
 	std::vector<uint32_t> seg;
@@ -723,33 +721,33 @@ static int table_maintain(bfcg_ctx_t *c)
 		const uint64_t ovf = c->h_stats[ST_TAB_OVF];
 		const int target = table_target_cshift(c);
 		if (ovf == 0 && target == P.tab_cshift) return 0;
-		if (ovf > B.tab_ovf_cap) return set_err("count table overflow list exhausted (%llu parked k-mers)", (unsigned long long)ovf);
-		if (P.l_pre + target > 36) return set_err("count table cannot grow beyond 2^36 slots");
+		if (ovf > B.tab_ovf_cap) return fail("count table overflow list exhausted (%llu parked k-mers)", (unsigned long long)ovf);
+		if (P.l_pre + target > 36) return fail("count table cannot grow beyond 2^36 slots");
 		{
 			size_t free_b = 0, total_b = 0;
 			if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && (8ULL << (P.l_pre + target)) + (1ULL << 30) > (uint64_t)free_b)
-				return set_err("count table of %llu keys cannot grow to 2^%d slots: %.1f GiB of device memory free", (unsigned long long)c->h_stats[ST_KEYS], P.l_pre + target, free_b / 1073741824.0);
+				return fail("count table of %llu keys cannot grow to 2^%d slots: %.1f GiB of device memory free", (unsigned long long)c->h_stats[ST_KEYS], P.l_pre + target, free_b / 1073741824.0);
 		}
 		int old_cshift = P.tab_cshift;
 		unsigned long long *nt = 0;
 		P.tab_cshift = target;
 		unsigned long long *nf = 0;
-		HIPCK(hipMalloc(&nt, 8ULL << (P.l_pre + P.tab_cshift)));
-		HIPCK(hipMemsetAsync(nt, 0, 8ULL << (P.l_pre + P.tab_cshift), c->st));
-		if (B.tab_first) { HIPCK(hipMalloc(&nf, 8ULL << (P.l_pre + P.tab_cshift))); HIPCK(hipMemsetAsync(nf, 0xff, 8ULL << (P.l_pre + P.tab_cshift), c->st)); }
+		BFCG_CK(hipMalloc(&nt, 8ULL << (P.l_pre + P.tab_cshift)));
+		BFCG_CK(hipMemsetAsync(nt, 0, 8ULL << (P.l_pre + P.tab_cshift), c->st));
+		if (B.tab_first) { BFCG_CK(hipMalloc(&nf, 8ULL << (P.l_pre + P.tab_cshift))); BFCG_CK(hipMemsetAsync(nf, 0xff, 8ULL << (P.l_pre + P.tab_cshift), c->st)); }
 		run_table_rehash(P, B.table, old_cshift, nt, B.tab_first, nf, c->st);
-		HIPCK(hipStreamSynchronize(c->st));
-		HIPCK(hipFree(B.table));
+		BFCG_CK(hipStreamSynchronize(c->st));
+		BFCG_CK(hipFree(B.table));
 		B.table = nt;
-		if (B.tab_first) { HIPCK(hipFree(B.tab_first)); B.tab_first = nf; }
+		if (B.tab_first) { BFCG_CK(hipFree(B.tab_first)); B.tab_first = nf; }
 		if (ovf) {
 			uint64_t *tmp = 0;
-			HIPCK(hipMalloc(&tmp, ovf * 40));
-			HIPCK(hipMemcpyAsync(tmp, B.tab_ovf, ovf * 40, hipMemcpyDeviceToDevice, c->st));
-			HIPCK(hipMemsetAsync(&B.stats[(size_t)ST_SLOTS * ST_N], 0, 8, c->st));
+			BFCG_CK(hipMalloc(&tmp, ovf * 40));
+			BFCG_CK(hipMemcpyAsync(tmp, B.tab_ovf, ovf * 40, hipMemcpyDeviceToDevice, c->st));
+			BFCG_CK(hipMemsetAsync(&B.stats[(size_t)ST_SLOTS * ST_N], 0, 8, c->st));
 			run_table_replay(P, B.table, tmp, ovf, B.stats, B.tab_ovf, B.tab_ovf_cap, B.tab_first, B.sub_last, c->st);
 			if (fetch_stats(c) != 0) return -1;
-			HIPCK(hipFree(tmp));
+			BFCG_CK(hipFree(tmp));
 		} else c->h_stats[ST_TAB_OVF] = 0;
 	}
 }
@@ -788,7 +786,7 @@ static int seg_maintain(bfcg_ctx_t *c)
 		const uint64_t ovf = c->h_stats[ST_TAB_OVF];
 		const int target = seg_target_shift(c);
 		if (ovf == 0 && target == P.seg_shift) return 0;
-		if (ovf > B.tab_ovf_cap) return set_err("count table overflow list exhausted (%llu parked k-mers)", (unsigned long long)ovf);
+		if (ovf > B.tab_ovf_cap) return fail("count table overflow list exhausted (%llu parked k-mers)", (unsigned long long)ovf);
 		{ // the old segments live until the new ones are filled.  No room (or no LDS: s > 14) for the next size: run fuller instead while nothing is
 		  // parked and the mean load stays below 85 % (probing happens in LDS: a fuller segment costs probes, not HBM traffic) ...
 			size_t free_b = 0, total_b = 0;
@@ -799,7 +797,7 @@ static int seg_maintain(bfcg_ctx_t *c)
 				// no room for the next segment size, and too full (or k-mers parked) to run on as it is: the host's layout sizes its table to the memory
 				// that IS free (seg_to_legacy) and may well succeed where doubling every segment cannot -- try it before giving up
 				if (seg_to_legacy(c) == 0) return 0;
-				return set_err("count table of %llu keys cannot grow to 2^%d slots per region: %.1f GiB of device memory free", (unsigned long long)c->h_stats[ST_KEYS], target, free_b / 1073741824.0);
+				return fail("count table of %llu keys cannot grow to 2^%d slots per region: %.1f GiB of device memory free", (unsigned long long)c->h_stats[ST_KEYS], target, free_b / 1073741824.0);
 			}
 		}
 		const int old_shift = P.seg_shift, old_blk = P.seg_blk;
@@ -808,29 +806,29 @@ static int seg_maintain(bfcg_ctx_t *c)
 		set_seg_shift(P, target, c->seg_blk_max);
 		if (c->seg_spare && c->seg_spare_shift >= target) { nt = c->seg_spare; nt_shift = c->seg_spare_shift; c->seg_spare = 0; }
 		else {
-			if (c->seg_spare) { HIPCK(hipFree(c->seg_spare)); c->seg_spare = 0; }
-			HIPCK(hipMalloc(&nt, (nfine << target) * 8));
+			if (c->seg_spare) { BFCG_CK(hipFree(c->seg_spare)); c->seg_spare = 0; }
+			BFCG_CK(hipMalloc(&nt, (nfine << target) * 8));
 		}
 		run_seg_rehash(P, B.seg_tab, old_shift, old_blk, nt, (uint32_t)nfine, c->st);
-		HIPCK(hipStreamSynchronize(c->st));
-		HIPCK(hipGetLastError());
+		BFCG_CK(hipStreamSynchronize(c->st));
+		BFCG_CK(hipGetLastError());
 		if (((nfine << nt_shift) * 8) <= (16ULL << 30)) {
 			// the buffer left behind becomes the spare the NEXT growth rehashes into; one that is smaller than its successor could not
 			// take that growth after a reset: replace it now, so that from the second data set on a context never allocates
 			// (a fresh multi-GiB hipMalloc costs ~35 ms per GiB on this box: only contexts that are being reused pay for the second buffer)
-			if (c->seg_cap_shift < nt_shift && c->reused) { HIPCK(hipFree(B.seg_tab)); c->seg_spare = 0; if (hipMalloc(&c->seg_spare, (nfine << nt_shift) * 8) != hipSuccess) { (void)hipGetLastError(); c->seg_spare = 0; } c->seg_spare_shift = nt_shift; }
+			if (c->seg_cap_shift < nt_shift && c->reused) { BFCG_CK(hipFree(B.seg_tab)); c->seg_spare = 0; if (hipMalloc(&c->seg_spare, (nfine << nt_shift) * 8) != hipSuccess) { (void)hipGetLastError(); c->seg_spare = 0; } c->seg_spare_shift = nt_shift; }
 			else { c->seg_spare = B.seg_tab; c->seg_spare_shift = c->seg_cap_shift; }
-		} else HIPCK(hipFree(B.seg_tab));
+		} else BFCG_CK(hipFree(B.seg_tab));
 		B.seg_tab = nt; c->seg_cap_shift = nt_shift;
 		++c->n_seg_grow;
 		if (ovf) {
 			uint64_t *tmp = 0;
-			HIPCK(hipMalloc(&tmp, ovf * 40));
-			HIPCK(hipMemcpyAsync(tmp, B.tab_ovf, ovf * 40, hipMemcpyDeviceToDevice, c->st));
-			HIPCK(hipMemsetAsync(&B.stats[(size_t)ST_SLOTS * ST_N], 0, 8, c->st));
+			BFCG_CK(hipMalloc(&tmp, ovf * 40));
+			BFCG_CK(hipMemcpyAsync(tmp, B.tab_ovf, ovf * 40, hipMemcpyDeviceToDevice, c->st));
+			BFCG_CK(hipMemsetAsync(&B.stats[(size_t)ST_SLOTS * ST_N], 0, 8, c->st));
 			run_seg_replay(P, B.seg_tab, tmp, ovf, B.stats, B.tab_ovf, B.tab_ovf_cap, c->st);
 			if (fetch_stats(c) != 0) return -1;
-			HIPCK(hipFree(tmp));
+			BFCG_CK(hipFree(tmp));
 		} else c->h_stats[ST_TAB_OVF] = 0;
 	}
 }
@@ -846,10 +844,10 @@ static int seg_to_legacy(bfcg_ctx_t *c, int for_export)
 	KParams &P = c->P; BatchBufs &B = c->B;
 	const uint64_t nfine = ((uint64_t)1 << P.F) >> c->log2n;
 	const uint64_t keys = c->h_stats[ST_KEYS];
-	if (c->seg_spare) { HIPCK(hipFree(c->seg_spare)); c->seg_spare = 0; }
+	if (c->seg_spare) { BFCG_CK(hipFree(c->seg_spare)); c->seg_spare = 0; }
 	// a context that counts on in the host's layout needs k_bloom's aggregation buffer (1.6 GB at -b35, 6.4 GB at -b37): taken BEFORE the table is
 	// sized to the memory that is free, not at the next batch when nothing may be left
-	if (!for_export && !P.filter_mode && !B.agg_out) HIPCK(hipMalloc(&B.agg_out, nfine * P.ag_cap * (P.track ? 32 : 24)));
+	if (!for_export && !P.filter_mode && !B.agg_out) BFCG_CK(hipMalloc(&B.agg_out, nfine * P.ag_cap * (P.track ? 32 : 24)));
 	int cs = c->prm.tab_cshift > 0 ? c->prm.tab_cshift : 2;
 	const uint64_t want = for_export ? keys + keys * 3 / 4 : 2 * keys + (c->prm.max_batch_pos / 4);
 	while ((1ULL << (P.l_pre + cs)) < want && P.l_pre + cs < 36) ++cs;
@@ -859,17 +857,17 @@ static int seg_to_legacy(bfcg_ctx_t *c, int for_export)
 			while (cs > 1 && (8ULL << (P.l_pre + cs)) + (2ULL << 30) > (uint64_t)free_b) --cs;
 	}
 	P.tab_cshift = cs;
-	HIPCK(hipMalloc(&B.table, 8ULL << (P.l_pre + cs)));
-	HIPCK(hipMemsetAsync(B.table, 0, 8ULL << (P.l_pre + cs), c->st));
+	BFCG_CK(hipMalloc(&B.table, 8ULL << (P.l_pre + cs)));
+	BFCG_CK(hipMemsetAsync(B.table, 0, 8ULL << (P.l_pre + cs), c->st));
 	// the keys are counted afresh: k-mers the reference's lossy key cannot tell apart (k >= 38) become one key here
-	HIPCK(hipMemset2DAsync(B.stats + ST_KEYS, sizeof(unsigned long long) * ST_N, 0, sizeof(unsigned long long), ST_SLOTS, c->st));
+	BFCG_CK(hipMemset2DAsync(B.stats + ST_KEYS, sizeof(unsigned long long) * ST_N, 0, sizeof(unsigned long long), ST_SLOTS, c->st));
 	run_seg_to_table(P, B.seg_tab, (uint32_t)nfine, B.table, B.stats, B.tab_ovf, B.tab_ovf_cap, c->st);
-	HIPCK(hipStreamSynchronize(c->st));
-	HIPCK(hipGetLastError());
-	HIPCK(hipFree(B.seg_tab));
+	BFCG_CK(hipStreamSynchronize(c->st));
+	BFCG_CK(hipGetLastError());
+	BFCG_CK(hipFree(B.seg_tab));
 	B.seg_tab = 0;
 	P.seg = 0; P.b3 = 0; c->seg_escaped = 1;
-	HIPCK(set_bloom_lds_attr(P)); // the aggregation table is back in the bloom kernel's LDS footprint
+	BFCG_CK(set_bloom_lds_attr(P)); // the aggregation table is back in the bloom kernel's LDS footprint
 	if (fetch_stats(c) != 0) return -1;
 	c->keys_last = c->h_stats[ST_KEYS];
 	if (for_export && c->h_stats[ST_TAB_OVF] == 0) return 0; // (no head room for a forecast batch: the next batch's check_health grows the table if there is one)
@@ -910,10 +908,10 @@ static int mg_scatter2(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qua
 {
 	const int nb1 = 1 << c->P.F1, b = c->cur;
 	const hipStream_t sA = mg_stage_a_stream(c);
-	if (n_pos > c->prm.max_batch_pos) return set_err("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	HIPCK(hipSetDevice(c->prm.device));
+	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
+	BFCG_CK(hipSetDevice(c->prm.device));
 	if (n_pos == 0) { // nothing to contribute to this global batch: keep the timing events defined
-		for (int i = 0; i < 3; ++i) HIPCK(hipEventRecord(c->evt[b][i], sA));
+		for (int i = 0; i < 3; ++i) BFCG_CK(hipEventRecord(c->evt[b][i], sA));
 		memset(counts, 0, sizeof(uint32_t) * nb1); return 0;
 	}
 	BatchBufs Bt = c->B;
@@ -922,11 +920,11 @@ static int mg_scatter2(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qua
 	KParams Pa = c->P;
 	Pa.no_kstats = no_kstats;
 	run_stage_a(Pa, Bt, d_seq, d_qual, (int64_t)n_pos, (uint64_t *)d_send, sA, c->evt[b]);
-	HIPCK(hipGetLastError());
+	BFCG_CK(hipGetLastError());
 	uint32_t *tmp = (uint32_t *)malloc(sizeof(uint32_t) * (nb1 + 1));
 	hipError_t e = hipMemcpyAsync(tmp, Bt.start1, sizeof(uint32_t) * (nb1 + 1), hipMemcpyDeviceToHost, sA);
 	if (e == hipSuccess) e = hipStreamSynchronize(sA);
-	if (e != hipSuccess) { free(tmp); return set_err("reading the level-1 bucket starts failed: %s", hipGetErrorString(e)); }
+	if (e != hipSuccess) { free(tmp); return fail("reading the level-1 bucket starts failed: %s", hipGetErrorString(e)); }
 	for (int i = 0; i < nb1; ++i) counts[i] = tmp[i + 1] - tmp[i];
 	free(tmp);
 	return 0;
@@ -944,11 +942,11 @@ extern "C" int bfcg_mg_scatter_slabs(bfcg_ctx_t *c, const uint8_t *d_seq, const 
 	const int nb1 = 1 << c->P.F1, nb_loc = nb1 >> c->log2n, b = c->cur;
 	const hipStream_t sA = mg_stage_a_stream(c);
 	*overflow = 0;
-	if (!c->mg_slab_ok || !c->op_cursor[b]) return set_err("this context has no slab mode");
-	if (n_pos > c->prm.max_batch_pos) return set_err("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	HIPCK(hipSetDevice(c->prm.device));
+	if (!c->mg_slab_ok || !c->op_cursor[b]) return fail("this context has no slab mode");
+	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
+	BFCG_CK(hipSetDevice(c->prm.device));
 	if (n_pos == 0) { // nothing to contribute to this global batch: keep the timing events defined
-		for (int i = 0; i < 3; ++i) HIPCK(hipEventRecord(c->evt[b][i], sA));
+		for (int i = 0; i < 3; ++i) BFCG_CK(hipEventRecord(c->evt[b][i], sA));
 		memset(fills, 0, sizeof(uint32_t) * (size_t)nb1 * 8); return 0;
 	}
 	BatchBufs Bt = c->B;
@@ -956,12 +954,12 @@ extern "C" int bfcg_mg_scatter_slabs(bfcg_ctx_t *c, const uint8_t *d_seq, const 
 	Bt.op_own_lo = (uint32_t)c->rank * (uint32_t)nb_loc; Bt.op_own_n = (uint32_t)nb_loc; Bt.op_own_delta = own_delta;
 	if (same_block_offset(c, b, d_seq, &d_qual, n_pos, sA) != 0) return -1;
 	run_stage_a_onepass(c->P, Bt, d_seq, d_qual, (int64_t)n_pos, (uint64_t *)d_send, sA, c->evt[b]);
-	HIPCK(hipGetLastError());
+	BFCG_CK(hipGetLastError());
 	std::vector<uint32_t> tmp((size_t)8 * nb1);
 	hipError_t e = hipMemcpyAsync(tmp.data(), Bt.op_seg + (size_t)8 * nb1, sizeof(uint32_t) * (size_t)8 * nb1, hipMemcpyDeviceToHost, sA); // the segments' ends (k_seg_setup)
 	if (e == hipSuccess) e = hipMemcpyAsync(c->h_flags[b], Bt.op_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, sA);
 	if (e == hipSuccess) e = hipStreamSynchronize(sA);
-	if (e != hipSuccess) return set_err("reading the slabs' fill failed: %s", hipGetErrorString(e));
+	if (e != hipSuccess) return fail("reading the slabs' fill failed: %s", hipGetErrorString(e));
 	*overflow = c->h_flags[b][0] != 0;
 	for (int seg = 0; seg < 8 * nb1; ++seg) fills[seg] = *overflow ? 0u : tmp[seg] - (uint32_t)seg * c->op_cap; // (k_seg_setup: the slab of segment seg starts at seg x capacity)
 	return 0;
@@ -977,13 +975,13 @@ extern "C" int bfcg_mg_scatter_slabs_async(bfcg_ctx_t *c, const uint8_t *d_seq, 
 {
 	const int nb1 = 1 << c->P.F1, nb_loc = nb1 >> c->log2n, b = c->cur, row_w = nb_loc * 8 + 2;
 	const hipStream_t sA = mg_stage_a_stream(c);
-	if (!c->mg_slab_ok || !c->op_cursor[b] || !c->h_rows[b]) return set_err("this context has no slab mode");
-	if (n_pos > c->prm.max_batch_pos) return set_err("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	HIPCK(hipSetDevice(c->prm.device));
+	if (!c->mg_slab_ok || !c->op_cursor[b] || !c->h_rows[b]) return fail("this context has no slab mode");
+	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
+	BFCG_CK(hipSetDevice(c->prm.device));
 	const size_t row_bytes = sizeof(uint32_t) * (size_t)c->n_ranks * row_w;
 	if (n_pos == 0) { // nothing to contribute to this global batch: rows of zeros; keep the timing events defined
-		for (int i = 0; i < 3; ++i) HIPCK(hipEventRecord(c->evt[b][i], sA));
-		HIPCK(hipMemsetAsync(d_rows_out, 0, row_bytes, sA));
+		for (int i = 0; i < 3; ++i) BFCG_CK(hipEventRecord(c->evt[b][i], sA));
+		BFCG_CK(hipMemsetAsync(d_rows_out, 0, row_bytes, sA));
 	} else {
 		BatchBufs Bt = c->B;
 		Bt.op_cursor = c->op_cursor[b]; Bt.op_seg = c->op_seg[b]; Bt.op_flags = c->op_flags + 4 * b; Bt.op_cap = c->op_cap; Bt.cap2 = c->cap2;
@@ -991,10 +989,10 @@ extern "C" int bfcg_mg_scatter_slabs_async(bfcg_ctx_t *c, const uint8_t *d_seq, 
 		if (same_block_offset(c, b, d_seq, &d_qual, n_pos, sA) != 0) return -1;
 		run_stage_a_onepass(c->P, Bt, d_seq, d_qual, (int64_t)n_pos, (uint64_t *)d_send, sA, c->evt[b]);
 		run_pack_rows(c->P, Bt, c->n_ranks, (uint32_t)row_w, d_rows_out, sA);
-		HIPCK(hipGetLastError());
+		BFCG_CK(hipGetLastError());
 	}
-	HIPCK(hipMemcpyAsync(c->h_rows[b], d_rows_out, row_bytes, hipMemcpyDeviceToHost, sA));
-	HIPCK(hipEventRecord(c->evA[b], sA));
+	BFCG_CK(hipMemcpyAsync(c->h_rows[b], d_rows_out, row_bytes, hipMemcpyDeviceToHost, sA));
+	BFCG_CK(hipEventRecord(c->evA[b], sA));
 	c->rows_slot = b;
 	*done = c->evA[b];
 	return 0;
@@ -1003,8 +1001,8 @@ extern "C" int bfcg_mg_scatter_slabs_async(bfcg_ctx_t *c, const uint8_t *d_seq, 
 extern "C" int bfcg_mg_scatter_slabs_wait(bfcg_ctx_t *c, uint32_t *fills, int *overflow)
 {
 	const int nb1 = 1 << c->P.F1, nb_loc = nb1 >> c->log2n, b = c->rows_slot, row_w = nb_loc * 8 + 2;
-	HIPCK(hipSetDevice(c->prm.device));
-	HIPCK(hipEventSynchronize(c->evA[b]));
+	BFCG_CK(hipSetDevice(c->prm.device));
+	BFCG_CK(hipEventSynchronize(c->evA[b]));
 	int ovf = 0;
 	for (int p = 0; p < c->n_ranks; ++p) ovf |= c->h_rows[b][(size_t)p * row_w + (size_t)nb_loc * 8] != 0;
 	for (int p = 0; p < c->n_ranks; ++p)
@@ -1028,9 +1026,9 @@ extern "C" int bfcg_mg_process_slabs(bfcg_ctx_t *c, const void *d_recv, const ui
 static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, uint32_t slab_cap, hipEvent_t *wait, int n_wait)
 {
 	const int N = c->n_ranks, nb_loc = (1 << c->P.F1) >> c->log2n, spb = slab_cap ? N * 8 : N, n_seg = nb_loc * spb, b = c->cur;
-	HIPCK(hipSetDevice(c->prm.device));
+	BFCG_CK(hipSetDevice(c->prm.device));
 	const size_t words = (size_t)3 * n_seg + 1 + nb_loc + 1;
-	if (words > c->seg_words) return set_err("internal: %zu segment words, room for %zu", words, c->seg_words);
+	if (words > c->seg_words) return fail("internal: %zu segment words, room for %zu", words, c->seg_words);
 	uint32_t *seg_beg = c->h_seg + (size_t)b * c->seg_words, *seg_end = seg_beg + n_seg, *row_base = seg_end + n_seg, *bucket_start = row_base + n_seg + 1;
 	uint64_t off = 0, rows = 0, tot = 0;
 	if (slab_cap) {
@@ -1040,7 +1038,7 @@ static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg
 					const int seg = (k * N + s) * 8 + x;
 					const uint64_t at = ((uint64_t)((size_t)s * nb_loc + k) * 8 + x) * slab_cap;
 					const uint32_t fill = seg_cnt[((size_t)s * nb_loc + k) * 8 + x];
-					if (fill > slab_cap || at + fill > 0xffffffffULL) return set_err("slab of %u records holds %u", slab_cap, fill);
+					if (fill > slab_cap || at + fill > 0xffffffffULL) return fail("slab of %u records holds %u", slab_cap, fill);
 					seg_beg[seg] = (uint32_t)at; seg_end[seg] = (uint32_t)at + fill; off += fill;
 				}
 	} else
@@ -1049,7 +1047,7 @@ static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg
 			int seg = k * N + s;
 			seg_beg[seg] = (uint32_t)off; off += seg_cnt[s * nb_loc + k]; seg_end[seg] = (uint32_t)off;
 		}
-	if (off > c->recv_cap) return set_err("received %llu records for this rank's buckets, capacity %llu", (unsigned long long)off, (unsigned long long)c->recv_cap);
+	if (off > c->recv_cap) return fail("received %llu records for this rank's buckets, capacity %llu", (unsigned long long)off, (unsigned long long)c->recv_cap);
 	const uint32_t tile2 = (uint32_t)bfcg_tile_of_rw(c->rw / 4);
 	for (int seg = 0; seg < n_seg; ++seg) { row_base[seg] = (uint32_t)rows; rows += (seg_end[seg] - seg_beg[seg] + tile2 - 1) / tile2; }
 	row_base[n_seg] = (uint32_t)rows;
@@ -1059,10 +1057,10 @@ static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg
 	}
 	bucket_start[nb_loc] = (uint32_t)tot;
 	uint32_t *d = c->d_seg + (size_t)b * c->seg_words;
-	for (int i = 0; i < n_wait; ++i) HIPCK(hipStreamWaitEvent(c->st, wait[i], 0));
-	HIPCK(hipEventRecord(c->evt[b][6], c->st));
-	HIPCK(hipMemcpyAsync(d, seg_beg, sizeof(uint32_t) * words, hipMemcpyHostToDevice, c->st));
-	if (c->B.seen_out) HIPCK(hipMemsetAsync(c->B.seen_out, 0, c->prm.max_batch_pos, c->st));
+	for (int i = 0; i < n_wait; ++i) BFCG_CK(hipStreamWaitEvent(c->st, wait[i], 0));
+	BFCG_CK(hipEventRecord(c->evt[b][6], c->st));
+	BFCG_CK(hipMemcpyAsync(d, seg_beg, sizeof(uint32_t) * words, hipMemcpyHostToDevice, c->st));
+	if (c->B.seen_out) BFCG_CK(hipMemsetAsync(c->B.seen_out, 0, c->prm.max_batch_pos, c->st));
 	c->B.batch_hi = (unsigned long long)(c->n_batches + 1) << 32;
 	if (use_stream(c) != 0 || ensure_agg(c) != 0) return -1;
 	c->B.stream = c->stream_mode; c->B.stream_out = c->stream_out;
@@ -1072,7 +1070,7 @@ static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg
 	if (op2_run) Bt.op_sticky = c->op_flags + OP_STICKY;
 	if (op2) {
 		Bt.cnt2 = c->cnt2; Bt.cap2 = c->cap2; Bt.op_flags = c->op_flags + 4 * b;
-		HIPCK(hipMemsetAsync(Bt.op_flags, 0, 4 * sizeof(uint32_t), c->st)); // (no one-pass stage A on a rank: stage B clears its slot's flags itself)
+		BFCG_CK(hipMemsetAsync(Bt.op_flags, 0, 4 * sizeof(uint32_t), c->st)); // (no one-pass stage A on a rank: stage B clears its slot's flags itself)
 	}
 	if (handover_begin(c, Bt, b, op2, c->call_no + 1) != 0) return -1; // (this call's number: assigned below)
 	KParams Pm = c->P;
@@ -1081,18 +1079,18 @@ static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg
 	run_stage_b(Pm, Bt, (const uint64_t *)d_recv, d, d + n_seg, n_seg, spb, d + 2 * n_seg, d + 3 * n_seg + 1, off, c->st, c->evt[b]);
 	if (handover_end(c, Bt, b) != 0) return -1;
 	if (op2_run) { // was every region's slab large enough?  (as for a single GPU: the flag is read with the batch's snapshot, an overflow is replayed -- stage B only)
-		HIPCK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
-		if (c->n_opq == 4) return set_err("internal: one-pass queue overflow");
+		BFCG_CK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
+		if (c->n_opq == 4) return fail("internal: one-pass queue overflow");
 		int free_i = 0;
 		for (;; ++free_i) { int used = 0; for (int i = 0; i < c->n_opq; ++i) used |= c->opq[i].mg == free_i + 1; if (!used) break; }
 		memcpy(c->mg_seg[free_i], seg_cnt, sizeof(uint32_t) * (size_t)N * nb_loc * (slab_cap ? 8 : 1)); c->mg_seg_slab[free_i] = slab_cap != 0;
 		bfcg_ctx::opq_t &q = c->opq[c->n_opq++];
 		q.seq = q.qual = nullptr; q.n_pos = off; q.slot = b; q.recv = d_recv; q.mg = free_i + 1;
 	}
-	HIPCK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
+	BFCG_CK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
 	c->slot_call[b] = ++c->call_no; c->slot_pos[b] = off;
-	HIPCK(hipEventRecord(c->evB[b], c->st));
-	HIPCK(hipGetLastError());
+	BFCG_CK(hipEventRecord(c->evB[b], c->st));
+	BFCG_CK(hipGetLastError());
 	c->used[b] = 1;
 	++c->n_batches;
 	return finalise_previous(c, b);
@@ -1110,14 +1108,14 @@ extern "C" int bfcg_mg_async_ok(bfcg_ctx_t *c) { return c->mg_slab_ok && !c->B.s
 extern "C" int bfcg_mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, const uint32_t *d_rows_in, uint32_t slab_cap, uint64_t rec_bound, int s_lo, int s_hi, hipEvent_t *wait, int n_wait)
 {
 	const int N = c->n_ranks, nb_loc = (1 << c->P.F1) >> c->log2n, spb = N * 8, n_seg = nb_loc * spb, b = c->cur;
-	HIPCK(hipSetDevice(c->prm.device));
+	BFCG_CK(hipSetDevice(c->prm.device));
 	const size_t words = (size_t)3 * n_seg + 1 + nb_loc + 1;
-	if (words > c->seg_words) return set_err("internal: %zu segment words, room for %zu", words, c->seg_words);
-	if (!slab_cap || !bfcg_mg_async_ok(c)) return set_err("internal: bfcg_mg_process_slabs_dev needs slabs and no debug_seen");
+	if (words > c->seg_words) return fail("internal: %zu segment words, room for %zu", words, c->seg_words);
+	if (!slab_cap || !bfcg_mg_async_ok(c)) return fail("internal: bfcg_mg_process_slabs_dev needs slabs and no debug_seen");
 	if (rec_bound > c->recv_cap) rec_bound = c->recv_cap;
 	uint32_t *d = c->d_seg + (size_t)b * c->seg_words;
-	for (int i = 0; i < n_wait; ++i) HIPCK(hipStreamWaitEvent(c->st, wait[i], 0));
-	HIPCK(hipEventRecord(c->evt[b][6], c->st));
+	for (int i = 0; i < n_wait; ++i) BFCG_CK(hipStreamWaitEvent(c->st, wait[i], 0));
+	BFCG_CK(hipEventRecord(c->evt[b][6], c->st));
 	run_seg_setup_mg(c->P, c->rw / 4, d_rows_in, (uint32_t)(nb_loc * 8 + 2), N, s_lo, s_hi, slab_cap, d, nullptr, c->st);
 	c->B.batch_hi = (unsigned long long)(c->n_batches + 1) << 32;
 	if (use_stream(c) != 0 || ensure_agg(c) != 0) return -1;
@@ -1128,7 +1126,7 @@ extern "C" int bfcg_mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, cons
 	if (op2_run) Bt.op_sticky = c->op_flags + OP_STICKY;
 	if (op2) {
 		Bt.cnt2 = c->cnt2; Bt.cap2 = c->cap2; Bt.op_flags = c->op_flags + 4 * b;
-		HIPCK(hipMemsetAsync(Bt.op_flags, 0, 4 * sizeof(uint32_t), c->st));
+		BFCG_CK(hipMemsetAsync(Bt.op_flags, 0, 4 * sizeof(uint32_t), c->st));
 	}
 	if (handover_begin(c, Bt, b, op2, c->call_no + 1) != 0) return -1;
 	KParams Pm = c->P;
@@ -1137,8 +1135,8 @@ extern "C" int bfcg_mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, cons
 	run_stage_b(Pm, Bt, (const uint64_t *)d_recv, d, d + n_seg, n_seg, spb, d + 2 * n_seg, d + 3 * n_seg + 1, rec_bound, c->st, c->evt[b]);
 	if (handover_end(c, Bt, b) != 0) return -1;
 	if (op2_run) {
-		HIPCK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
-		if (c->n_opq == 4) return set_err("internal: one-pass queue overflow");
+		BFCG_CK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
+		if (c->n_opq == 4) return fail("internal: one-pass queue overflow");
 		int free_i = 0;
 		for (;; ++free_i) { int used = 0; for (int i = 0; i < c->n_opq; ++i) used |= c->opq[i].mg == free_i + 1; if (!used) break; }
 		memset(c->mg_seg[free_i], 0, sizeof(uint32_t) * (size_t)N * nb_loc * 8); c->mg_seg_slab[free_i] = 1; // (the sizes follow: bfcg_mg_process_finish)
@@ -1146,10 +1144,10 @@ extern "C" int bfcg_mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, cons
 		q.seq = q.qual = nullptr; q.n_pos = rec_bound; q.slot = b; q.recv = d_recv; q.mg = free_i + 1;
 		c->unfinished_mg = free_i + 1;
 	} else c->unfinished_mg = 0;
-	HIPCK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
+	BFCG_CK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
 	c->slot_call[b] = ++c->call_no; c->slot_pos[b] = rec_bound;
-	HIPCK(hipEventRecord(c->evB[b], c->st));
-	HIPCK(hipGetLastError());
+	BFCG_CK(hipEventRecord(c->evB[b], c->st));
+	BFCG_CK(hipGetLastError());
 	c->used[b] = 1;
 	++c->n_batches;
 	c->unfinished = 1;
@@ -1160,7 +1158,7 @@ extern "C" int bfcg_mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, cons
 // bfcg_mg_process_slabs does.
 extern "C" int bfcg_mg_process_finish(bfcg_ctx_t *c, const uint32_t *fills)
 {
-	if (!c->unfinished) return set_err("internal: no stage B waits for its sizes");
+	if (!c->unfinished) return fail("internal: no stage B waits for its sizes");
 	const int N = c->n_ranks, nb_loc = (1 << c->P.F1) >> c->log2n, b = c->cur;
 	c->unfinished = 0;
 	uint64_t tot = 0;
@@ -1178,7 +1176,7 @@ extern "C" int bfcg_mg_process_finish(bfcg_ctx_t *c, const uint32_t *fills)
 static int use_stream(bfcg_ctx_t *c)
 {
 	if (c->stream_mode) {
-		if (!c->P.seg && !c->stream_out) HIPCK(hipMalloc(&c->stream_out, c->recs2_n * (uint64_t)c->rw)); // (the segment layout hands over through its log)
+		if (!c->P.seg && !c->stream_out) BFCG_CK(hipMalloc(&c->stream_out, c->recs2_n * (uint64_t)c->rw)); // (the segment layout hands over through its log)
 		++c->n_stream_batches;
 	}
 	return 0;
@@ -1189,7 +1187,7 @@ static int finalise_previous(bfcg_ctx_t *c, int b)
 {
 	if (c->pend) {
 		const int pb = b ^ 1;
-		HIPCK(hipEventSynchronize(c->evB[pb]));
+		BFCG_CK(hipEventSynchronize(c->evB[pb]));
 		if (batch_times(c, pb) != 0) return -1;
 		if (c->n_opq && c->opq[0].slot == pb) { // the batch just finished went through the one-pass partition: clean?
 			if (c->h_flags[pb][1]) { c->pend = 1; c->cur = b ^ 1; return drain(c); } // a slab overflowed: drain() replays it and what was enqueued behind it
@@ -1217,9 +1215,9 @@ static int commit_pending_pages(bfcg_ctx_t *c, int b)
 	const uint32_t nfine = (uint32_t)(((uint64_t)1 << c->P.F) >> c->log2n);
 	BatchBufs Bt = c->B;
 	Bt.ho = c->ho; Bt.ho_stride = c->ho_stride; Bt.ho_cur = c->ho_cur; Bt.ho_mark = c->ho_mark; Bt.ho_mark_stride = nfine; Bt.ho_keys = c->ho_keys;
-	HIPCK(hipMemsetAsync(c->ho_keys, 0, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, c->st));
+	BFCG_CK(hipMemsetAsync(c->ho_keys, 0, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, c->st));
 	run_commit_pages(c->P, Bt, nfine, (uint32_t)c->ho_pending, c->st);
-	HIPCK(hipMemcpyAsync(c->h_ho_keys[b], c->ho_keys, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, hipMemcpyDeviceToHost, c->st));
+	BFCG_CK(hipMemcpyAsync(c->h_ho_keys[b], c->ho_keys, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, hipMemcpyDeviceToHost, c->st));
 	c->slot_commit[b] = c->ho_pending;
 	memcpy(c->slot_page_call[b], c->ho_page_call, sizeof(uint64_t) * (size_t)c->ho_pending);
 	c->ho_pending = 0;
@@ -1256,7 +1254,7 @@ static int handover_begin(bfcg_ctx_t *c, BatchBufs &Bt, int b, int slabs, uint64
 	Bt.ho_stride = c->ho_stride; Bt.ho_page = (uint32_t)c->ho_pending;
 	c->ho_page_call[c->ho_pending++] = call;
 	Bt.ho_commit = c->ho_pending >= c->ho_window;
-	if (Bt.ho_commit) HIPCK(hipMemsetAsync(c->ho_keys, 0, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, c->st));
+	if (Bt.ho_commit) BFCG_CK(hipMemsetAsync(c->ho_keys, 0, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, c->st));
 	else c->slot_all_committed[b] = 0;
 	return 0;
 }
@@ -1264,7 +1262,7 @@ static int handover_begin(bfcg_ctx_t *c, BatchBufs &Bt, int b, int slabs, uint64
 static int handover_end(bfcg_ctx_t *c, const BatchBufs &Bt, int b)
 {
 	if (!c->P.seg || Bt.ho_stride == 0 || !Bt.ho_commit) return 0;
-	HIPCK(hipMemcpyAsync(c->h_ho_keys[b], c->ho_keys, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, hipMemcpyDeviceToHost, c->st));
+	BFCG_CK(hipMemcpyAsync(c->h_ho_keys[b], c->ho_keys, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, hipMemcpyDeviceToHost, c->st));
 	c->slot_commit[b] = c->ho_pending;
 	memcpy(c->slot_page_call[b], c->ho_page_call, sizeof(uint64_t) * (size_t)c->ho_pending);
 	c->ho_pending = 0;
@@ -1298,7 +1296,7 @@ static int same_block_offset(bfcg_ctx_t *c, int b, const uint8_t *d_seq, const u
 {
 	if (!*d_qual || ((((uintptr_t)d_seq) ^ ((uintptr_t)*d_qual)) & 15) == 0) return 0;
 	uint8_t *dst = c->d_qual2[b] + (((uintptr_t)d_seq) & 15);
-	HIPCK(hipMemcpyAsync(dst, *d_qual, n_pos, hipMemcpyDeviceToDevice, s));
+	BFCG_CK(hipMemcpyAsync(dst, *d_qual, n_pos, hipMemcpyDeviceToDevice, s));
 	*d_qual = dst;
 	return 0;
 }
@@ -1310,7 +1308,7 @@ static int ensure_agg(bfcg_ctx_t *c)
 {
 	if (c->P.filter_mode || c->P.seg || c->B.agg_out) return 0;
 	const uint64_t nfine = ((uint64_t)1 << c->P.F) >> c->log2n;
-	HIPCK(hipMalloc(&c->B.agg_out, nfine * c->P.ag_cap * (c->P.track ? 32 : 24)));
+	BFCG_CK(hipMalloc(&c->B.agg_out, nfine * c->P.ag_cap * (c->P.track ? 32 : 24)));
 	return 0;
 }
 
@@ -1322,8 +1320,8 @@ static int enqueue_batch(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_q
 	Bt.batch_hi = (unsigned long long)(c->n_batches + 1) << 32;
 	Bt.rows1 = c->rows1[b]; Bt.chunk1 = c->chunk1[b]; Bt.start1 = c->start1[b]; Bt.row_base = Bt.start1 + nb1 + 1; Bt.recs1 = c->recs1[b];
 	hipStream_t sA = c->pipeline ? c->stA : c->st; // one stream: the batches' kernels simply follow each other
-	if (c->used[b]) HIPCK(hipStreamWaitEvent(sA, c->evB[b], 0)); // stage B two batches ago has released this buffer set
-	if (!c->pipeline && wait_copy) HIPCK(hipStreamWaitEvent(sA, c->evCopy, 0)); // the host batch is being copied on stream stA
+	if (c->used[b]) BFCG_CK(hipStreamWaitEvent(sA, c->evB[b], 0)); // stage B two batches ago has released this buffer set
+	if (!c->pipeline && wait_copy) BFCG_CK(hipStreamWaitEvent(sA, c->evCopy, 0)); // the host batch is being copied on stream stA
 	if (use_stream(c) != 0) return -1;
 	Bt.stream = c->stream_mode; Bt.stream_out = c->stream_out;
 	KParams Pt = c->P;
@@ -1348,10 +1346,10 @@ static int enqueue_batch(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_q
 		}
 		run_stage_a_onepass(Pt, Bt, d_seq, d_qual, (int64_t)n_pos, Bt.recs1, sA, c->evt[b]);
 	} else run_stage_a(Pt, Bt, d_seq, d_qual, (int64_t)n_pos, Bt.recs1, sA, c->evt[b]);
-	HIPCK(hipEventRecord(c->evA[b], sA));
-	HIPCK(hipStreamWaitEvent(c->st, c->evA[b], 0));
-	HIPCK(hipEventRecord(c->evt[b][6], c->st));
-	if (c->B.seen_out) HIPCK(hipMemsetAsync(c->B.seen_out, 0, n_pos, c->st));
+	BFCG_CK(hipEventRecord(c->evA[b], sA));
+	BFCG_CK(hipStreamWaitEvent(c->st, c->evA[b], 0));
+	BFCG_CK(hipEventRecord(c->evt[b][6], c->st));
+	if (c->B.seen_out) BFCG_CK(hipMemsetAsync(c->B.seen_out, 0, n_pos, c->st));
 	if (handover_begin(c, Bt, b, op && Bt.cap2, c->call_no) != 0) return -1;
 	if (op) {
 		uint32_t *sg = c->op_seg[b];
@@ -1365,14 +1363,14 @@ static int enqueue_batch(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_q
 	run_stage_b(Pt, Bt, Bt.recs1, Bt.start1, Bt.start1 + 1, nb1, 1, Bt.row_base, Bt.start1, n_pos, c->st, c->evt[b]);
 	if (handover_end(c, Bt, b) != 0) return -1;
 	if (op_run) {
-		HIPCK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st)); // behind k_seal: is the run poisoned up to and including this batch?
-		if (c->n_opq == 4) return set_err("internal: one-pass queue overflow");
+		BFCG_CK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st)); // behind k_seal: is the run poisoned up to and including this batch?
+		if (c->n_opq == 4) return fail("internal: one-pass queue overflow");
 		c->opq[c->n_opq].seq = d_seq; c->opq[c->n_opq].qual = d_qual_given; c->opq[c->n_opq].n_pos = n_pos; c->opq[c->n_opq].slot = b; c->opq[c->n_opq].recv = nullptr; c->opq[c->n_opq].mg = 0; ++c->n_opq;
 	}
-	HIPCK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
+	BFCG_CK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
 	c->slot_call[b] = c->call_no; c->slot_pos[b] = n_pos;
-	HIPCK(hipEventRecord(c->evB[b], c->st));
-	HIPCK(hipGetLastError());
+	BFCG_CK(hipEventRecord(c->evB[b], c->st));
+	BFCG_CK(hipGetLastError());
 	c->used[b] = 1;
 	++c->n_batches;
 	return finalise_previous(c, b);
@@ -1448,10 +1446,10 @@ extern "C" double bfcg_mg_warm_factor(bfcg_ctx_t *c)
 
 extern "C" int bfcg_count_batch_dev(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos)
 {
-	if (c->n_ranks > 1) return set_err("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
+	if (c->n_ranks > 1) return fail("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
 	if (n_pos == 0) return 0;
-	if (n_pos > c->prm.max_batch_pos) return set_err("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	HIPCK(hipSetDevice(c->prm.device));
+	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
+	BFCG_CK(hipSetDevice(c->prm.device));
 	uint64_t from, lim;
 	split_rule(c, &from, &lim);
 	struct depth_guard { bfcg_ctx_t *c; depth_guard(bfcg_ctx_t *c_) : c(c_) { if (c->call_depth++ == 0) ++c->call_no; } ~depth_guard() { --c->call_depth; } } guard(c);
@@ -1473,10 +1471,10 @@ extern "C" int bfcg_count_batch_dev(bfcg_ctx_t *c, const uint8_t *d_seq, const u
 
 extern "C" int bfcg_count_batch_host(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos)
 {
-	if (c->n_ranks > 1) return set_err("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
+	if (c->n_ranks > 1) return fail("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
 	if (n_pos == 0) return 0;
-	if (n_pos > c->prm.max_batch_pos) return set_err("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	HIPCK(hipSetDevice(c->prm.device));
+	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
+	BFCG_CK(hipSetDevice(c->prm.device));
 	uint64_t from, lim;
 	split_rule(c, &from, &lim);
 	struct depth_guard { bfcg_ctx_t *c; depth_guard(bfcg_ctx_t *c_) : c(c_) { if (c->call_depth++ == 0) ++c->call_no; } ~depth_guard() { --c->call_depth; } } guard(c);
@@ -1492,11 +1490,11 @@ extern "C" int bfcg_count_batch_host(bfcg_ctx_t *c, const uint8_t *h_seq, const 
 		if (o) return o < n_pos ? bfcg_count_batch_host(c, h_seq + o, h_qual ? h_qual + o : 0, n_pos - o) : 0;
 	}
 	const int b = c->cur;
-	HIPCK(hipMemcpyAsync(c->d_seq2[b], h_seq, n_pos, hipMemcpyHostToDevice, c->stA)); // ordered behind stage A of two batches ago (same stream)
-	if (h_qual) HIPCK(hipMemcpyAsync(c->d_qual2[b], h_qual, n_pos, hipMemcpyHostToDevice, c->stA));
-	HIPCK(hipEventRecord(c->evCopy, c->stA));
+	BFCG_CK(hipMemcpyAsync(c->d_seq2[b], h_seq, n_pos, hipMemcpyHostToDevice, c->stA)); // ordered behind stage A of two batches ago (same stream)
+	if (h_qual) BFCG_CK(hipMemcpyAsync(c->d_qual2[b], h_qual, n_pos, hipMemcpyHostToDevice, c->stA));
+	BFCG_CK(hipEventRecord(c->evCopy, c->stA));
 	int rc = enqueue_batch(c, c->d_seq2[b], h_qual ? c->d_qual2[b] : NULL, n_pos, 1, 0);
-	HIPCK(hipEventSynchronize(c->evCopy)); // the caller may reuse its host buffers now
+	BFCG_CK(hipEventSynchronize(c->evCopy)); // the caller may reuse its host buffers now
 	if (rc == 0 && (c->B.seen_out || getenv("BFCG_SYNC_BATCHES"))) rc = drain(c);
 	return rc;
 }
@@ -1556,14 +1554,14 @@ static uint64_t find_cut_planes(const uint32_t *np, uint64_t lo, uint64_t hi)
 
 extern "C" int bfcg_count_batch_planes(bfcg_ctx_t *c, const uint32_t *h_planes, uint64_t plane_words, uint64_t first_pos, uint64_t n_pos, int has_qual)
 {
-	if (c->n_ranks > 1) return set_err("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
+	if (c->n_ranks > 1) return fail("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
 	if (n_pos == 0) return 0;
-	if (n_pos > c->prm.max_batch_pos) return set_err("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	if ((first_pos + n_pos + 31) / 32 > plane_words) return set_err("positions [%llu, %llu) lie outside planes of %llu words", (unsigned long long)first_pos, (unsigned long long)(first_pos + n_pos), (unsigned long long)plane_words);
-	HIPCK(hipSetDevice(c->prm.device));
+	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
+	if ((first_pos + n_pos + 31) / 32 > plane_words) return fail("positions [%llu, %llu) lie outside planes of %llu words", (unsigned long long)first_pos, (unsigned long long)(first_pos + n_pos), (unsigned long long)plane_words);
+	BFCG_CK(hipSetDevice(c->prm.device));
 	if (!c->d_planes[0]) { // (first batch of this kind)
 		c->plane_cap = c->prm.max_batch_pos / 32 + 4;
-		for (int b = 0; b < 2; ++b) HIPCK(hipMalloc(&c->d_planes[b], c->plane_cap * 4 * sizeof(uint32_t)));
+		for (int b = 0; b < 2; ++b) BFCG_CK(hipMalloc(&c->d_planes[b], c->plane_cap * 4 * sizeof(uint32_t)));
 	}
 	uint64_t from, lim;
 	split_rule(c, &from, &lim);
@@ -1583,12 +1581,12 @@ extern "C" int bfcg_count_batch_planes(bfcg_ctx_t *c, const uint32_t *h_planes, 
 	const uint64_t w0 = first_pos >> 5, nw = ((first_pos + n_pos + 31) >> 5) - w0 + 1; // (+ the word the expansion reads ahead: a spare one at the planes' end)
 	const uint64_t nw_c = w0 + nw <= plane_words ? nw : plane_words - w0;
 	for (int p = 0; p < (has_qual ? 4 : 3); ++p) // ordered behind stage A of two batches ago (same stream), as the byte streams of bfcg_count_batch_host are
-		HIPCK(hipMemcpyAsync(c->d_planes[b] + (uint64_t)p * c->plane_cap, h_planes + (uint64_t)p * plane_words + w0, nw_c * sizeof(uint32_t), hipMemcpyHostToDevice, c->stA));
+		BFCG_CK(hipMemcpyAsync(c->d_planes[b] + (uint64_t)p * c->plane_cap, h_planes + (uint64_t)p * plane_words + w0, nw_c * sizeof(uint32_t), hipMemcpyHostToDevice, c->stA));
 	hipLaunchKernelGGL(k_expand_planes, dim3((unsigned)((n_pos + 4095) / 4096)), dim3(256), 0, c->stA, c->d_planes[b], c->plane_cap, (uint32_t)(first_pos & 31), n_pos, has_qual,
 	                   c->d_seq2[b], c->d_qual2[b]);
-	HIPCK(hipEventRecord(c->evCopy, c->stA)); // (behind the expansion: where the batches' kernels run on the other stream they wait for this)
+	BFCG_CK(hipEventRecord(c->evCopy, c->stA)); // (behind the expansion: where the batches' kernels run on the other stream they wait for this)
 	int rc = enqueue_batch(c, c->d_seq2[b], has_qual ? c->d_qual2[b] : NULL, n_pos, 1, 0);
-	HIPCK(hipEventSynchronize(c->evCopy)); // the caller may reuse its planes now
+	BFCG_CK(hipEventSynchronize(c->evCopy)); // the caller may reuse its planes now
 	if (rc == 0 && (c->B.seen_out || getenv("BFCG_SYNC_BATCHES"))) rc = drain(c);
 	return rc;
 }
@@ -1596,14 +1594,14 @@ extern "C" int bfcg_count_batch_planes(bfcg_ctx_t *c, const uint32_t *h_planes, 
 extern "C" void *bfcg_dev_alloc(bfcg_ctx_t *c, uint64_t bytes)
 {
 	void *p = 0;
-	if (hipSetDevice(c->prm.device) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess) { set_err("hipMalloc(%llu) failed", (unsigned long long)bytes); return NULL; }
+	if (hipSetDevice(c->prm.device) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess) { fail("hipMalloc(%llu) failed", (unsigned long long)bytes); return NULL; }
 	return p;
 }
 extern "C" void bfcg_dev_free(bfcg_ctx_t *c, void *p) { (void)c; (void)hipFree(p); }
 extern "C" int bfcg_h2d(bfcg_ctx_t *c, void *dst, const void *src, uint64_t bytes)
-{ HIPCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stC)); HIPCK(hipStreamSynchronize(c->stC)); return 0; }
+{ BFCG_CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stC)); BFCG_CK(hipStreamSynchronize(c->stC)); return 0; }
 extern "C" int bfcg_d2h(bfcg_ctx_t *c, void *dst, const void *src, uint64_t bytes)
-{ HIPCK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stC)); HIPCK(hipStreamSynchronize(c->stC)); return 0; }
+{ BFCG_CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stC)); BFCG_CK(hipStreamSynchronize(c->stC)); return 0; }
 
 // Progress WITHOUT draining the pipeline: calls = bfcg_count_batch_* calls made so far (numbered from 1 after a reset), final = the last
 // call all of whose batches are known to be complete, keys_of[final - i], i < n: distinct keys after call final - i (exact: stage B alone
@@ -1652,7 +1650,7 @@ static int d2h_parallel(int device, void *dst, const void *src, uint64_t bytes)
 	int T = env ? atoi(env) : 8;
 	if (T > 32) T = 32;
 	if (T < 2 || bytes < (2ull << 30)) { // below 2 GiB the threads' set-up (pinned buffers, streams: 0.1 s) costs more than it saves
-		HIPCK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+		BFCG_CK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
 		return 0;
 	}
 	if (!getenv("BFC_GPU_NO_THP")) { // fresh destination pages: ask for 2 MiB ones (512x fewer page faults); advisory, ignored where unsupported
@@ -1674,115 +1672,66 @@ static int d2h_parallel(int device, void *dst, const void *src, uint64_t bytes)
 			(void)hipStreamDestroy(st); (void)hipHostFree(stage);
 		});
 	for (auto &x : th) x.join();
-	for (int t = 0; t < T; ++t) if (err[t] != hipSuccess) return set_err("device-to-host copy failed: %s", hipGetErrorString(err[t]));
+	for (int t = 0; t < T; ++t) if (err[t] != hipSuccess) return fail("device-to-host copy failed: %s", hipGetErrorString(err[t]));
 	return 0;
 }
 
 extern "C" int bfcg_bloom_to_host(bfcg_ctx_t *c, int which, uint8_t *dst)
 {
 	unsigned long long *src = which ? c->B.bloom_hi : c->B.bloom;
-	if (!src) return set_err("bloom filter %d does not exist in this mode", which);
+	if (!src) return fail("bloom filter %d does not exist in this mode", which);
 	if (drain(c) != 0) return -1;
-	HIPCK(hipStreamSynchronize(c->st));
+	BFCG_CK(hipStreamSynchronize(c->st));
 	return d2h_parallel(c->prm.device, dst, src, c->bloom_bytes);
 }
 
 extern "C" bfc_bf_t *bfcg_export_bloom(bfcg_ctx_t *c, int which)
 {
-	if (c->n_ranks > 1) { set_err("this context owns 1/%d of the filter: bfcg_bloom_to_host copies the slice, a whole bfc_bf_t cannot come from one rank", c->n_ranks); return NULL; }
+	if (c->n_ranks > 1) { fail("this context owns 1/%d of the filter: bfcg_bloom_to_host copies the slice, a whole bfc_bf_t cannot come from one rank", c->n_ranks); return NULL; }
 	bfc_bf_t *b = bfc_bf_alloc_raw(c->P.bf_shift, c->P.n_hashes); // every byte is overwritten below: no 2^(b-3)-byte memset on the host
-	if (!b) { set_err("host allocation of the bloom filter failed"); return NULL; }
+	if (!b) { fail("host allocation of the bloom filter failed"); return NULL; }
 	if (bfcg_bloom_to_host(c, which, b->b) != 0) { bfc_bf_destroy(b); return NULL; }
 	return b;
 }
 
-// ---- filters that stay in HBM behind their host object.  `bfc -1` counts into bf_high and then queries it for every k-mer again
-// (correct.c:556): bfc_count hands the host copy the reference's API promises (bfc_bf_t.b is public) AND leaves a device copy here,
-// which bfcg_trim_create adopts instead of uploading 2^(b-3) bytes again.  The copy is dropped when the host object is destroyed or
-// written to through this library (bfc_bf_destroy / bfc_bf_insert call bfcg_resident_drop).
-// A count table has the same arrangement (bfcg_export_table_resident -> bfcg_kcov_create, i.e. bfc_count -> bfc_correct): its entry
-// carries k, l_pre and cshift instead of n_shift (k = 0 marks a filter's entry), and the bfc_ch_* functions that write to a table, free
-// one or hand out an address call bfcg_resident_drop as the bfc_bf_* ones do.
-struct resident_t { const void *bf; void *dev; int device, n_shift, k, l_pre, cshift; };
-static resident_t g_res[16];
-static std::atomic<int> g_res_n{0};
-static std::mutex g_res_mu;
-
-extern "C" void bfcg_resident_drop(const void *bf)
-{
-	if (g_res_n.load(std::memory_order_relaxed) == 0) return;
-	for (;;) { // a filter counted on several GPUs has a copy on each of them
-		void *dev = 0; int device = 0;
-		{
-			std::lock_guard<std::mutex> lk(g_res_mu);
-			for (int i = 0; i < 16; ++i) if (g_res[i].dev && g_res[i].bf == bf) { dev = g_res[i].dev; device = g_res[i].device; g_res[i].dev = 0; g_res_n.fetch_sub(1); break; }
-		}
-		if (!dev) return;
-		int cur = 0; (void)hipGetDevice(&cur); (void)hipSetDevice(device); (void)hipFree(dev); (void)hipSetDevice(cur);
-	}
-}
-// a full copy of host filter `bf` that sits at `dev` on `device` (bfcg_mg.hip: gathered from the ranks' slices); 0, or -1 if the registry is full
-extern "C" int bfcg_resident_register(const void *bf, void *dev, int device, int n_shift)
-{
-	std::lock_guard<std::mutex> lk(g_res_mu);
-	for (int i = 0; i < 16; ++i) if (!g_res[i].dev) { g_res[i] = resident_t{bf, dev, device, n_shift}; g_res_n.fetch_add(1); return 0; }
-	return -1;
-}
 // the slice of filter `which` this context owns, in place (device memory), and its size in bytes
 extern "C" void *bfcg_bloom_slice(bfcg_ctx_t *c, int which, uint64_t *bytes)
 {
 	if (bytes) *bytes = c->bloom_bytes;
 	return which ? (void *)c->B.bloom_hi : (void *)c->B.bloom;
 }
-static void *resident_take(const bfc_bf_t *bf, int device)
+// A copy of `bytes` at `src` left in HBM behind the host object r.host, for a trimmer / coverage pass on the same device to adopt instead of
+// uploading the same bytes again (the registry: bfcg_query.hip).  No room, or no free entry: the host copy alone is a complete answer.
+static void leave_resident(bfcg_ctx_t *c, const void *src, uint64_t bytes, resident_t r)
 {
-	if (g_res_n.load(std::memory_order_relaxed) == 0) return 0;
-	std::lock_guard<std::mutex> lk(g_res_mu);
-	for (int i = 0; i < 16; ++i)
-		if (g_res[i].dev && g_res[i].bf == (const void *)bf && g_res[i].device == device && g_res[i].k == 0 && g_res[i].n_shift == bf->n_shift) {
-			void *dev = g_res[i].dev; g_res[i].dev = 0; g_res_n.fetch_sub(1); return dev;
-		}
-	return 0;
-}
-// the same for a count table: the first taker owns the copy (and frees it), a second one finds nothing
-static void *resident_take_table(const bfc_ch_t *ch, int device, int k, int l_pre, int cshift)
-{
-	if (g_res_n.load(std::memory_order_relaxed) == 0) return 0;
-	std::lock_guard<std::mutex> lk(g_res_mu);
-	for (int i = 0; i < 16; ++i)
-		if (g_res[i].dev && g_res[i].bf == (const void *)ch && g_res[i].device == device && g_res[i].k == k && g_res[i].l_pre == l_pre && g_res[i].cshift == cshift) {
-			void *dev = g_res[i].dev; g_res[i].dev = 0; g_res_n.fetch_sub(1); return dev;
-		}
-	return 0;
+	r.device = c->prm.device;
+	if (hipSetDevice(r.device) == hipSuccess && hipMalloc(&r.dev, bytes) == hipSuccess) {
+		if (hipMemcpyAsync(r.dev, src, bytes, hipMemcpyDeviceToDevice, c->st) == hipSuccess && hipStreamSynchronize(c->st) == hipSuccess && resident_put(r) == 0) return;
+		(void)hipFree(r.dev);
+	}
+	(void)hipGetLastError();
 }
 
 extern "C" bfc_bf_t *bfcg_export_bloom_resident(bfcg_ctx_t *c, int which)
 {
 	bfc_bf_t *b = bfcg_export_bloom(c, which);
-	if (!b) return NULL;
-	void *dev = 0;
-	if (hipSetDevice(c->prm.device) != hipSuccess || hipMalloc(&dev, c->bloom_bytes) != hipSuccess) { (void)hipGetLastError(); return b; } // no room: the host copy alone is a complete answer
-	if (hipMemcpyAsync(dev, which ? c->B.bloom_hi : c->B.bloom, c->bloom_bytes, hipMemcpyDeviceToDevice, c->st) != hipSuccess ||
-	    hipStreamSynchronize(c->st) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(dev); return b; }
-	std::lock_guard<std::mutex> lk(g_res_mu);
-	for (int i = 0; i < 16; ++i) if (!g_res[i].dev) { g_res[i] = resident_t{b, dev, c->prm.device, c->P.bf_shift}; g_res_n.fetch_add(1); return b; }
-	(void)hipFree(dev); // registry full
+	if (b) leave_resident(c, which ? c->B.bloom_hi : c->B.bloom, c->bloom_bytes, resident_t{b, 0, 0, c->P.bf_shift});
 	return b;
 }
 
 extern "C" bfc_ch_t *bfcg_export_table(bfcg_ctx_t *c)
 {
-	if (c->P.filter_mode) { set_err("no count table in filter mode"); return NULL; }
+	if (c->P.filter_mode) { fail("no count table in filter mode"); return NULL; }
 	const double t_e0 = dbg_now();
 	if (drain(c) != 0) return NULL;
 	const double t_e1 = dbg_now();
 	if (c->P.seg && seg_to_legacy(c, 1) != 0) return NULL; // the host's (sub-table, key) layout is made now
 	bfc_ch_t *ch = bfc_ch_alloc_raw(c->P.k, c->P.l_pre, c->P.tab_cshift);
-	if (!ch) { set_err("host allocation of the count table failed"); return NULL; }
-	if (hipStreamSynchronize(c->st) != hipSuccess) { set_err("the conversion of the table segments failed"); bfc_ch_destroy(ch); return NULL; }
+	if (!ch) { fail("host allocation of the count table failed"); return NULL; }
+	if (hipStreamSynchronize(c->st) != hipSuccess) { fail("the conversion of the table segments failed"); bfc_ch_destroy(ch); return NULL; }
 	const double t_e2 = dbg_now();
 	if (d2h_parallel(c->prm.device, bfc_ch_raw_slots(ch), c->B.table, 8ULL << (c->P.l_pre + c->P.tab_cshift)) != 0) {
-		set_err("D2H copy of the count table failed"); bfc_ch_destroy(ch); return NULL;
+		fail("D2H copy of the count table failed"); bfc_ch_destroy(ch); return NULL;
 	}
 	if (getenv("BFC_GPU_TIMING")) fprintf(stderr, "[T::bfcg_export_table] batches in flight finished %.3f s, segments -> host layout (2^%d slots) %.3f s, device -> host %.3f s\n",
 	                                      t_e1 - t_e0, c->P.l_pre + c->P.tab_cshift, t_e2 - t_e1, dbg_now() - t_e2);
@@ -1791,59 +1740,49 @@ extern "C" bfc_ch_t *bfcg_export_table(bfcg_ctx_t *c)
 		if (bfc_ch_raw_order(ch, &hf, &hl) != 0 ||
 		    d2h_parallel(c->prm.device, hf, c->B.tab_first, 8ULL << (c->P.l_pre + c->P.tab_cshift)) != 0 ||
 		    hipMemcpyAsync(hl, c->B.sub_last, 8ULL << c->P.l_pre, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
-		    hipStreamSynchronize(c->st) != hipSuccess) { set_err("D2H copy of the order stamps failed"); bfc_ch_destroy(ch); return NULL; }
+		    hipStreamSynchronize(c->st) != hipSuccess) { fail("D2H copy of the order stamps failed"); bfc_ch_destroy(ch); return NULL; }
 	}
 	// the number of keys is the device's own statistic (exact: every test compares it with the oracle's distinct count, and at c4's full
 	// size with a host recount); a recount of a 64 GiB table costs 1.4 s even on 16 threads.  BFC_GPU_RECOUNT=1 recounts and cross-checks.
 	bfc_ch_raw_set_count(ch, c->h_stats[ST_KEYS]);
 	if (getenv("BFC_GPU_RECOUNT")) {
 		bfc_ch_raw_recount(ch);
-		if (bfc_ch_count(ch) != c->h_stats[ST_KEYS]) { set_err("exported table holds %llu keys, the device counted %llu", (unsigned long long)bfc_ch_count(ch), (unsigned long long)c->h_stats[ST_KEYS]); bfc_ch_destroy(ch); return NULL; }
+		if (bfc_ch_count(ch) != c->h_stats[ST_KEYS]) { fail("exported table holds %llu keys, the device counted %llu", (unsigned long long)bfc_ch_count(ch), (unsigned long long)c->h_stats[ST_KEYS]); bfc_ch_destroy(ch); return NULL; }
 	}
 	return ch;
 }
 
 // the host table the reference's API promises AND a copy of c->B.table that stays in HBM behind it, for bfcg_kcov_create (the corrector)
-// on the same device to adopt instead of uploading the same bytes again.  No room, or no free entry: the host copy alone is a complete answer.
 extern "C" bfc_ch_t *bfcg_export_table_resident(bfcg_ctx_t *c)
 {
 	bfc_ch_t *ch = bfcg_export_table(c);
-	if (!ch) return NULL;
-	const uint64_t bytes = 8ULL << (c->P.l_pre + c->P.tab_cshift);
-	void *dev = 0;
-	if (hipSetDevice(c->prm.device) != hipSuccess || hipMalloc(&dev, bytes) != hipSuccess) { (void)hipGetLastError(); return ch; }
-	if (hipMemcpyAsync(dev, c->B.table, bytes, hipMemcpyDeviceToDevice, c->st) != hipSuccess ||
-	    hipStreamSynchronize(c->st) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(dev); return ch; }
-	std::lock_guard<std::mutex> lk(g_res_mu);
-	for (int i = 0; i < 16; ++i)
-		if (!g_res[i].dev) { g_res[i] = resident_t{ch, dev, c->prm.device, 0, c->P.k, c->P.l_pre, c->P.tab_cshift}; g_res_n.fetch_add(1); return ch; }
-	(void)hipFree(dev); // registry full
+	if (ch) leave_resident(c, c->B.table, 8ULL << (c->P.l_pre + c->P.tab_cshift), resident_t{ch, 0, 0, 0, c->P.k, c->P.l_pre, c->P.tab_cshift});
 	return ch;
 }
 
 extern "C" int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out)
 {
-	if (n_pos > c->prm.max_batch_pos) return set_err("too many positions");
+	if (n_pos > c->prm.max_batch_pos) return fail("too many positions");
 	if (drain(c) != 0) return -1;
 	uint64_t *d_out = 0;
-	HIPCK(hipSetDevice(c->prm.device));
-	HIPCK(hipMalloc(&d_out, n_pos * 24));
-	HIPCK(hipMemcpyAsync(c->d_seq, h_seq, n_pos, hipMemcpyHostToDevice, c->st));
-	if (h_qual) HIPCK(hipMemcpyAsync(c->d_qual, h_qual, n_pos, hipMemcpyHostToDevice, c->st));
+	BFCG_CK(hipSetDevice(c->prm.device));
+	BFCG_CK(hipMalloc(&d_out, n_pos * 24));
+	BFCG_CK(hipMemcpyAsync(c->d_seq, h_seq, n_pos, hipMemcpyHostToDevice, c->st));
+	if (h_qual) BFCG_CK(hipMemcpyAsync(c->d_qual, h_qual, n_pos, hipMemcpyHostToDevice, c->st));
 	run_hash_only(c->P, c->d_seq, h_qual ? c->d_qual : NULL, (int64_t)n_pos, d_out, c->st);
-	HIPCK(hipGetLastError());
-	HIPCK(hipMemcpyAsync(out, d_out, n_pos * 24, hipMemcpyDeviceToHost, c->st));
-	HIPCK(hipStreamSynchronize(c->st));
-	HIPCK(hipFree(d_out));
+	BFCG_CK(hipGetLastError());
+	BFCG_CK(hipMemcpyAsync(out, d_out, n_pos * 24, hipMemcpyDeviceToHost, c->st));
+	BFCG_CK(hipStreamSynchronize(c->st));
+	BFCG_CK(hipFree(d_out));
 	return 0;
 }
 
 extern "C" int bfcg_seen_flags(bfcg_ctx_t *c, uint8_t *dst, uint64_t n_pos)
 {
-	if (!c->B.seen_out) return set_err("context was created without debug_seen");
+	if (!c->B.seen_out) return fail("context was created without debug_seen");
 	if (drain(c) != 0) return -1;
-	HIPCK(hipMemcpyAsync(dst, c->B.seen_out, n_pos, hipMemcpyDeviceToHost, c->st));
-	HIPCK(hipStreamSynchronize(c->st));
+	BFCG_CK(hipMemcpyAsync(dst, c->B.seen_out, n_pos, hipMemcpyDeviceToHost, c->st));
+	BFCG_CK(hipStreamSynchronize(c->st));
 	return 0;
 }
 
@@ -1851,194 +1790,21 @@ extern "C" int bfcg_seen_flags(bfcg_ctx_t *c, uint8_t *dst, uint64_t n_pos)
 extern "C" void *bfcg_host_alloc(uint64_t bytes)
 {
 	void *p = 0;
-	if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc(%llu) failed", (unsigned long long)bytes); return NULL; }
+	if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { fail("hipHostMalloc(%llu) failed", (unsigned long long)bytes); return NULL; }
 	return p;
 }
 extern "C" void bfcg_host_free(void *p) { if (p) (void)hipHostFree(p); }
 
 
-// ---------------------------------------------------------------------------------------------------------------
-// trim pass of `bfc -1` on the GPU (config c5): the bloom filter of k-mers seen twice is resident in HBM, every read
-// of a batch gets its longest streak of bloom hits and the keep / trim decision of correct.c:557-569
-
-struct bfcg_trim {
-	KParams P;
-	int device;
-	hipStream_t st;
-	unsigned int *bloom;
-	int adopted;    // the filter was already in HBM (left there by bfc_count), not uploaded
-	uint8_t *d_seq, *d_flags;
-	uint64_t *d_off;
-	int32_t *d_start, *d_end;
-	uint64_t max_pos, max_reads;
-	hipEvent_t e0, e1;
-	float last_ms;
-};
-
-extern "C" bfcg_trim_t *bfcg_trim_create(int k, const bfc_bf_t *bf, int device, uint64_t max_pos, uint64_t max_reads)
-{
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err("no HIP device available: the trim pass has no CPU fallback here"); return NULL; }
-	if (!bf || k < 1 || k > 63 || bf->n_shift < 9 || bf->n_shift > 37 || bf->n_hashes < 1 || bf->n_hashes > 12) { set_err("bad arguments to bfcg_trim_create"); return NULL; }
-	HIPCKN(hipSetDevice(device));
-	bfcg_trim_t *t = (bfcg_trim_t *)calloc(1, sizeof(bfcg_trim_t));
-	memset(&t->P, 0, sizeof(t->P));
-	t->P.k = k; t->P.bf_shift = bf->n_shift; t->P.n_hashes = bf->n_hashes; t->P.q = 0;
-	t->device = device; t->max_pos = max_pos; t->max_reads = max_reads;
-	HIPCKN(hipStreamCreate(&t->st));
-	HIPCKN(hipEventCreate(&t->e0)); HIPCKN(hipEventCreate(&t->e1));
-	t->bloom = (unsigned int *)resident_take(bf, device); // left in HBM by bfc_count (bfcg_export_bloom_resident)?
-	t->adopted = t->bloom != 0;
-	if (!t->bloom) {
-		HIPCKN(hipMalloc(&t->bloom, 1ULL << (bf->n_shift - 3)));
-		HIPCKN(hipMemcpy(t->bloom, bf->b, 1ULL << (bf->n_shift - 3), hipMemcpyHostToDevice));
-	}
-	HIPCKN(hipMalloc(&t->d_seq, max_pos)); HIPCKN(hipMalloc(&t->d_flags, max_pos));
-	HIPCKN(hipMalloc(&t->d_off, (max_reads + 1) * 8));
-	HIPCKN(hipMalloc(&t->d_start, max_reads * 4)); HIPCKN(hipMalloc(&t->d_end, max_reads * 4));
-	return t;
-}
-
-extern "C" void bfcg_trim_destroy(bfcg_trim_t *t)
-{
-	if (!t) return;
-	(void)hipSetDevice(t->device);
-	(void)hipStreamSynchronize(t->st);
-	(void)hipFree(t->bloom); (void)hipFree(t->d_seq); (void)hipFree(t->d_flags); (void)hipFree(t->d_off); (void)hipFree(t->d_start); (void)hipFree(t->d_end);
-	(void)hipEventDestroy(t->e0); (void)hipEventDestroy(t->e1);
-	(void)hipStreamDestroy(t->st);
-	free(t);
-}
-
-// device-resident stream (d_seq may be NULL: then h_seq is copied in).  off[n_reads+1] are stream offsets: read r is
-// [off[r], off[r+1]-1), byte off[r+1]-1 its separator.  start[r] = -1 if the read is dropped, else keep [start, end).
-extern "C" int bfcg_trim_batch(bfcg_trim_t *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos, const uint64_t *h_off, uint64_t n_reads,
-                               float min_frac, int32_t *start, int32_t *end)
-{
-	if (n_pos > t->max_pos || n_reads > t->max_reads) return set_err("trim batch exceeds the capacity given to bfcg_trim_create");
-	if (n_reads == 0) return 0;
-	HIPCK(hipSetDevice(t->device));
-	if (!d_seq) { HIPCK(hipMemcpyAsync(t->d_seq, h_seq, n_pos, hipMemcpyHostToDevice, t->st)); d_seq = t->d_seq; }
-	HIPCK(hipMemcpyAsync(t->d_off, h_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, t->st));
-	HIPCK(hipEventRecord(t->e0, t->st));
-	run_query(t->P, d_seq, (int64_t)n_pos, t->bloom, t->d_flags, t->st);
-	run_streak(t->P.k, min_frac, t->d_flags, t->d_off, n_reads, t->d_start, t->d_end, t->st);
-	HIPCK(hipEventRecord(t->e1, t->st));
-	HIPCK(hipGetLastError());
-	HIPCK(hipMemcpyAsync(start, t->d_start, n_reads * 4, hipMemcpyDeviceToHost, t->st));
-	HIPCK(hipMemcpyAsync(end, t->d_end, n_reads * 4, hipMemcpyDeviceToHost, t->st));
-	HIPCK(hipStreamSynchronize(t->st));
-	HIPCK(hipEventElapsedTime(&t->last_ms, t->e0, t->e1));
-	return 0;
-}
-extern "C" float bfcg_trim_last_ms(bfcg_trim_t *t) { return t->last_ms; }
-extern "C" int bfcg_trim_adopted(bfcg_trim_t *t) { return t->adopted; }
-extern "C" void *bfcg_trim_dev_seq(bfcg_trim_t *t) { return t->d_seq; }
-
-// ---------------------------------------------------------------------------------------------------------------
-// k-mer coverage for the corrector: bfc_ec_kcov (correct.c:96-117) for a whole batch of reads against the count
-// table resident in HBM -- either uploaded from a host bfc_ch_t or borrowed from a counting context that still holds it
-
-struct bfcg_kcov {
-	KParams P;
-	int device, owns_table;
-	int adopted;    // the table was already in HBM (left there by bfc_count), not uploaded
-	hipStream_t st;
-	unsigned long long *table;
-	uint8_t *d_seq, *d_flags;
-	uint16_t *d_out;
-	uint64_t max_pos;
-	hipEvent_t e0, e1;
-	float last_ms;
-};
-
-static bfcg_kcov_t *kcov_new(int k, int l_pre, int cshift, int device, uint64_t max_pos)
-{
-	HIPCKN(hipSetDevice(device));
-	bfcg_kcov_t *t = (bfcg_kcov_t *)calloc(1, sizeof(bfcg_kcov_t));
-	memset(&t->P, 0, sizeof(t->P));
-	t->P.k = k; t->P.l_pre = l_pre; t->P.tab_cshift = cshift; t->P.q = 0;
-	t->device = device; t->max_pos = max_pos;
-	HIPCKN(hipStreamCreate(&t->st));
-	HIPCKN(hipEventCreate(&t->e0)); HIPCKN(hipEventCreate(&t->e1));
-	HIPCKN(hipMalloc(&t->d_seq, max_pos)); HIPCKN(hipMalloc(&t->d_flags, max_pos)); HIPCKN(hipMalloc(&t->d_out, max_pos * 2));
-	return t;
-}
-
-extern "C" bfcg_kcov_t *bfcg_kcov_create(const bfc_ch_t *ch, int device, uint64_t max_pos)
-{
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err("no HIP device available: the k-mer coverage pass has no CPU fallback here"); return NULL; }
-	if (!ch || max_pos == 0) { set_err("bad arguments to bfcg_kcov_create"); return NULL; }
-	bfcg_kcov_t *t = kcov_new(bfc_ch_get_k(ch), bfc_ch_get_lpre(ch), bfc_ch_raw_cshift(ch), device, max_pos);
-	if (!t) return NULL;
-	const uint64_t bytes = 8ULL << (t->P.l_pre + t->P.tab_cshift);
-	t->owns_table = 1;
-	t->table = (unsigned long long *)resident_take_table(ch, device, t->P.k, t->P.l_pre, t->P.tab_cshift); // left in HBM by bfc_count (bfcg_export_table_resident)?
-	t->adopted = t->table != 0;
-	if (!t->table) {
-		HIPCKN(hipMalloc(&t->table, bytes));
-		HIPCKN(hipMemcpy(t->table, bfc_ch_raw_slots((bfc_ch_t *)ch), bytes, hipMemcpyHostToDevice));
-	}
-	return t;
-}
-
-// the table stays where the count kernels built it; the context must outlive the returned object and must not count meanwhile
-extern "C" bfcg_kcov_t *bfcg_kcov_attach(bfcg_ctx_t *c, uint64_t max_pos)
-{
-	if (!c || c->P.filter_mode || max_pos == 0) { set_err("bfcg_kcov_attach needs a table-mode context"); return NULL; }
-	if (drain(c) != 0) return NULL;
-	if (c->P.seg && seg_to_legacy(c) != 0) return NULL; // bfc_ch_kmer_occ probes the host's layout
-	bfcg_kcov_t *t = kcov_new(c->P.k, c->P.l_pre, c->P.tab_cshift, c->prm.device, max_pos);
-	if (!t) return NULL;
-	t->table = c->B.table;
-	return t;
-}
-
-extern "C" void bfcg_kcov_destroy(bfcg_kcov_t *t)
-{
-	if (!t) return;
-	(void)hipSetDevice(t->device);
-	(void)hipStreamSynchronize(t->st);
-	if (t->owns_table) (void)hipFree(t->table);
-	(void)hipFree(t->d_seq); (void)hipFree(t->d_flags); (void)hipFree(t->d_out);
-	(void)hipEventDestroy(t->e0); (void)hipEventDestroy(t->e1);
-	(void)hipStreamDestroy(t->st);
-	free(t);
-}
-
-// stream = batch format of PART 2; out[p] (host, may be NULL) / the device buffer of bfcg_kcov_dev_out() get one packed u16 per position
-extern "C" int bfcg_kcov_batch(bfcg_kcov_t *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos, int min_occ, uint16_t *out)
-{
-	if (n_pos > t->max_pos) return set_err("k-mer coverage batch exceeds the capacity given at creation");
-	if (n_pos == 0) return 0;
-	HIPCK(hipSetDevice(t->device));
-	if (!d_seq) { HIPCK(hipMemcpyAsync(t->d_seq, h_seq, n_pos, hipMemcpyHostToDevice, t->st)); d_seq = t->d_seq; }
-	HIPCK(hipEventRecord(t->e0, t->st));
-	run_kcov(t->P, d_seq, (int64_t)n_pos, min_occ, t->table, t->d_flags, t->d_out, t->st);
-	HIPCK(hipEventRecord(t->e1, t->st));
-	HIPCK(hipGetLastError());
-	if (out) HIPCK(hipMemcpyAsync(out, t->d_out, n_pos * 2, hipMemcpyDeviceToHost, t->st));
-	HIPCK(hipStreamSynchronize(t->st));
-	HIPCK(hipEventElapsedTime(&t->last_ms, t->e0, t->e1));
-	return 0;
-}
-extern "C" float bfcg_kcov_last_ms(bfcg_kcov_t *t) { return t->last_ms; }
-// the corrector (bfcg_ec.hip) runs behind a coverage context: its table in HBM, the probe parameters, the device it lives on
-namespace bfcg {
-const unsigned long long *kcov_table(bfcg_kcov_t *t, KParams *P, int *device) { *P = t->P; *device = t->device; return t->table; }
-int kcov_adopted(bfcg_kcov_t *t) { return t->adopted; }
+// what the objects of bfcg_query.hip, bfcg_ec.hip and bfcg_kmers.hip borrow from a context (bfcg_internal.h)
 // k of a table-mode context, -1 for a filter-mode one: what bfcg_ec_attach checks before anything is drained or converted
-int ctx_table_k(bfcg_ctx_t *c) { return c->P.filter_mode ? -1 : c->P.k; }
-// the table read-out (bfcg_kmers.hip) borrows a counting context's table as bfcg_kcov_attach does: drained, in the host's layout, not exported
-const unsigned long long *ctx_borrow_table(bfcg_ctx_t *c, KParams *P, int *device)
+int bfcg::ctx_table_k(bfcg_ctx_t *c) { return c->P.filter_mode ? -1 : c->P.k; }
+// the table where the count kernels built it: drained, in the host's layout (bfc_ch_kmer_occ probes that one), not exported
+const unsigned long long *bfcg::ctx_borrow_table(bfcg_ctx_t *c, KParams *P, int *device)
 {
-	if (!c || c->P.filter_mode) { set_err("bfcg_kmers_attach needs a table-mode context"); return NULL; }
+	if (!c || c->P.filter_mode) { fail("bfcg_kmers_attach needs a table-mode context"); return NULL; }
 	if (drain(c) != 0) return NULL;
 	if (c->P.seg && seg_to_legacy(c) != 0) return NULL;
 	*P = c->P; *device = c->prm.device;
 	return c->B.table;
 }
-}
-extern "C" void *bfcg_kcov_dev_seq(bfcg_kcov_t *t) { return t->d_seq; }
-extern "C" void *bfcg_kcov_dev_out(bfcg_kcov_t *t) { return t->d_out; }

@@ -21,29 +21,12 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <stdarg.h>
 #include "bfc_gpu.h"
 #include "bfcg_internal.h"
 #include "kmer_dev.h"
 #include "bfcg_ec1.h"
 
 using namespace ec1k;
-
-extern "C" void bfcg_set_error(const char *msg);
-namespace bfcg {
-const unsigned long long *kcov_table(bfcg_kcov_t *t, KParams *P, int *device);
-int kcov_adopted(bfcg_kcov_t *t);
-int ctx_table_k(bfcg_ctx_t *c);
-}
-
-static int ec_err(const char *fmt, ...)
-{
-	char buf[512];
-	va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-	bfcg_set_error(buf);
-	return -1;
-}
-#define ECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return ec_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 static Opt ec_opt(const bfc_opt_t *opt, int mode)
 {
@@ -85,8 +68,8 @@ static void host_ec1(const bfc_ch_t *ch, const Opt &o, uint8_t *seq, uint8_t *qu
 
 extern "C" int bfcg_ec1_host(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t *aux, uint32_t *aux2)
 {
-	if (!ch || !opt || !seq || opt->k != bfc_ch_get_k(ch)) return ec_err("bad arguments to bfcg_ec1_host");
-	if (opt->refine_ec) return ec_err("bfcg_ec1_host: refine_ec is set (bfcg_ec1_host_refine corrects with a read's earlier stats)");
+	if (!ch || !opt || !seq || opt->k != bfc_ch_get_k(ch)) return bfcg::fail("bad arguments to bfcg_ec1_host");
+	if (opt->refine_ec) return bfcg::fail("bfcg_ec1_host: refine_ec is set (bfcg_ec1_host_refine corrects with a read's earlier stats)");
 	const Opt o = ec_opt(opt, mode);
 	host_ec1<false>(ch, o, (uint8_t *)seq, (uint8_t *)qual, (int)strlen(seq), Result(), aux, aux2);
 	return 0;
@@ -95,7 +78,7 @@ extern "C" int bfcg_ec1_host(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode,
 extern "C" int bfcg_ec1_host_refine(const bfc_ch_t *ch, const bfc_opt_t *opt, int mode, char *seq, char *qual, uint32_t ori_aux, uint32_t ori_aux2,
                                     uint32_t *aux, uint32_t *aux2)
 {
-	if (!ch || !opt || !seq || opt->k != bfc_ch_get_k(ch)) return ec_err("bad arguments to bfcg_ec1_host_refine");
+	if (!ch || !opt || !seq || opt->k != bfc_ch_get_k(ch)) return bfcg::fail("bad arguments to bfcg_ec1_host_refine");
 	const Opt o = ec_opt(opt, mode);
 	Result ori; ori.aux = ori_aux; ori.aux2 = ori_aux2;
 	host_ec1<true>(ch, o, (uint8_t *)seq, (uint8_t *)qual, (int)strlen(seq), ori, aux, aux2);
@@ -229,8 +212,6 @@ extern "C" void bfcg_ec_destroy(bfcg_ec_t *e)
 	free(e);
 }
 
-#define ECN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ec_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); bfcg_ec_destroy(e); return NULL; } } while (0)
-
 // what both kinds of corrector share, once e->kc (and e->ch) are set: options, capacities, buffers
 static bfcg_ec_t *ec_setup(bfcg_ec_t *e, const bfc_opt_t *opt, int mode, uint64_t max_pos, uint64_t max_reads)
 {
@@ -244,20 +225,20 @@ static bfcg_ec_t *ec_setup(bfcg_ec_t *e, const bfc_opt_t *opt, int mode, uint64_
 	const uint64_t lanes_max = (uint64_t)env_int("BFCG_EC_LANES", 1 << 17, EC_BT, 1 << 20);
 	e->lanes = (max_reads + EC_BT - 1) / EC_BT * EC_BT;
 	if (e->lanes > lanes_max) e->lanes = lanes_max / EC_BT * EC_BT;
-	ECN(hipSetDevice(e->device));
-	ECN(hipStreamCreate(&e->st));
-	ECN(hipEventCreate(&e->e0)); ECN(hipEventCreate(&e->e1));
-	ECN(hipMalloc(&e->d_qual, max_pos));
-	ECN(hipMalloc(&e->d_off, (max_reads + 1) * 8));
-	ECN(hipMalloc(&e->d_aux, max_reads * 4)); ECN(hipMalloc(&e->d_aux2, max_reads * 4));
-	ECN(hipMalloc(&e->d_heap, sizeof(Heap1) * e->lanes * (uint64_t)e->hcap));
-	ECN(hipMalloc(&e->d_stack, sizeof(Stack1) * e->lanes * (uint64_t)e->scap));
+	BFCG_CKN(bfcg_ec_destroy(e), hipSetDevice(e->device));
+	BFCG_CKN(bfcg_ec_destroy(e), hipStreamCreate(&e->st));
+	BFCG_CKN(bfcg_ec_destroy(e), hipEventCreate(&e->e0)); BFCG_CKN(bfcg_ec_destroy(e), hipEventCreate(&e->e1));
+	BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_qual, max_pos));
+	BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_off, (max_reads + 1) * 8));
+	BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_aux, max_reads * 4)); BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_aux2, max_reads * 4));
+	BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_heap, sizeof(Heap1) * e->lanes * (uint64_t)e->hcap));
+	BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_stack, sizeof(Stack1) * e->lanes * (uint64_t)e->scap));
 	e->ec_bytes = e->lanes * 2 * (uint64_t)e->lmax;
-	ECN(hipMalloc(&e->d_ec, e->ec_bytes));
-	ECN(hipMalloc(&e->d_ctr, 3 * sizeof(unsigned long long)));
+	BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_ec, e->ec_bytes));
+	BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_ctr, 3 * sizeof(unsigned long long)));
 	if (e->refine) {
-		ECN(hipMalloc(&e->d_oseq, max_pos));
-		ECN(hipMalloc(&e->d_oaux, max_reads * 4)); ECN(hipMalloc(&e->d_oaux2, max_reads * 4));
+		BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_oseq, max_pos));
+		BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_oaux, max_reads * 4)); BFCG_CKN(bfcg_ec_destroy(e), hipMalloc(&e->d_oaux2, max_reads * 4));
 	}
 	return e;
 }
@@ -265,10 +246,11 @@ static bfcg_ec_t *ec_setup(bfcg_ec_t *e, const bfc_opt_t *opt, int mode, uint64_
 extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, int device, uint64_t max_pos, uint64_t max_reads)
 {
 	if (!ch || !opt || opt->k != bfc_ch_get_k(ch) || max_pos == 0 || max_reads == 0 || opt->filter_mode) {
-		ec_err("bad arguments to bfcg_ec_create (a table-mode bfc_opt_t whose k is the table's)");
+		bfcg::fail("bad arguments to bfcg_ec_create (a table-mode bfc_opt_t whose k is the table's)");
 		return NULL;
 	}
 	bfcg_ec_t *e = (bfcg_ec_t *)calloc(1, sizeof(bfcg_ec_t));
+	if (!e) { bfcg::fail("out of host memory"); return NULL; }
 	e->kc = bfcg_kcov_create(ch, device, max_pos);                 // uploads the table once, or adopts the copy bfc_count left (and says so if there is no GPU)
 	if (!e->kc) { free(e); return NULL; }
 	uint64_t hist[256], hist_high[64];
@@ -282,12 +264,12 @@ extern "C" bfcg_ec_t *bfcg_ec_create(const bfc_ch_t *ch, const bfc_opt_t *opt, i
 extern "C" bfcg_ec_t *bfcg_ec_attach(bfcg_ctx_t *ctx, const bfc_opt_t *opt, uint64_t max_pos, uint64_t max_reads)
 {
 	if (!ctx || !opt || max_pos == 0 || max_reads == 0 || opt->filter_mode) {
-		ec_err("bad arguments to bfcg_ec_attach (a counting context and a table-mode bfc_opt_t)");
+		bfcg::fail("bad arguments to bfcg_ec_attach (a counting context and a table-mode bfc_opt_t)");
 		return NULL;
 	}
 	const int k = bfcg::ctx_table_k(ctx);
-	if (k < 0) { ec_err("bfcg_ec_attach needs a table-mode context"); return NULL; }
-	if (opt->k != k) { ec_err("bfcg_ec_attach: opt->k is %d, the context counts %d-mers", opt->k, k); return NULL; }
+	if (k < 0) { bfcg::fail("bfcg_ec_attach needs a table-mode context"); return NULL; }
+	if (opt->k != k) { bfcg::fail("bfcg_ec_attach: opt->k is %d, the context counts %d-mers", opt->k, k); return NULL; }
 	bfcg_kmers_t *km = bfcg_kmers_attach(ctx);                     // drains the context and converts its segments
 	if (!km) return NULL;
 	uint64_t hist[256], hist_high[64];
@@ -295,6 +277,7 @@ extern "C" bfcg_ec_t *bfcg_ec_attach(bfcg_ctx_t *ctx, const bfc_opt_t *opt, uint
 	bfcg_kmers_destroy(km);
 	if (mode < -1) return NULL;
 	bfcg_ec_t *e = (bfcg_ec_t *)calloc(1, sizeof(bfcg_ec_t));
+	if (!e) { bfcg::fail("out of host memory"); return NULL; }
 	e->kc = bfcg_kcov_attach(ctx, max_pos);
 	if (!e->kc) { free(e); return NULL; }
 	return ec_setup(e, opt, mode, max_pos, max_reads);
@@ -315,7 +298,7 @@ static int ec_retry_rounds(bfcg_ec_t *e, const char *fn, int rf, uint8_t *d_seq,
 	const uint64_t n_first = n_list;
 	if (n_list > e->list_cap) {
 		(void)hipFree(e->d_list); e->d_list = nullptr; e->list_cap = 0;
-		ECK(hipMalloc(&e->d_list, n_list * 8));
+		BFCG_CK(hipMalloc(&e->d_list, n_list * 8));
 		e->list_cap = n_list;
 	}
 	uint64_t lanes = e->lanes, hcap = (uint64_t)e->hcap, scap = (uint64_t)e->scap;
@@ -323,7 +306,7 @@ static int ec_retry_rounds(bfcg_ec_t *e, const char *fn, int rf, uint8_t *d_seq,
 	while (n_list) {
 		hcap *= 4; scap *= 4;
 		if (hcap > EC_RETRY_MAX_CAP || scap > EC_RETRY_MAX_CAP)
-			return ec_err("%s: read %llu does not fit a search of 2^28 heap or stack entries", fn, (unsigned long long)list[0]);
+			return bfcg::fail("%s: read %llu does not fit a search of 2^28 heap or stack entries", fn, (unsigned long long)list[0]);
 		int lmax = e->lmax;
 		for (uint64_t i = 0; i < n_list; ++i) {
 			const int n = (int)(off[list[i] + 1] - off[list[i]] - 1);
@@ -340,7 +323,7 @@ static int ec_retry_rounds(bfcg_ec_t *e, const char *fn, int rf, uint8_t *d_seq,
 				if (hipMalloc(big_heap, sizeof(Heap1) * lanes * hcap) == hipSuccess && hipMalloc(big_stack, sizeof(Stack1) * lanes * scap) == hipSuccess) break;
 				(void)hipGetLastError();
 				if (lanes == 1)
-					return ec_err("%s: read %llu needs %llu heap and %llu stack entries, which the device cannot allocate", fn, (unsigned long long)list[0],
+					return bfcg::fail("%s: read %llu needs %llu heap and %llu stack entries, which the device cannot allocate", fn, (unsigned long long)list[0],
 					              (unsigned long long)hcap, (unsigned long long)scap);
 			}
 			heap = *big_heap; stack = *big_stack;
@@ -350,30 +333,30 @@ static int ec_retry_rounds(bfcg_ec_t *e, const char *fn, int rf, uint8_t *d_seq,
 			uint8_t *d = nullptr;
 			if (hipMalloc(&d, n_lanes * 2 * (uint64_t)lmax) != hipSuccess) {
 				(void)hipGetLastError();
-				return ec_err("%s: read %llu: no room for the results of %llu lanes of %d bases", fn, (unsigned long long)list[0], (unsigned long long)n_lanes, lmax);
+				return bfcg::fail("%s: read %llu: no room for the results of %llu lanes of %d bases", fn, (unsigned long long)list[0], (unsigned long long)n_lanes, lmax);
 			}
 			(void)hipFree(e->d_ec);
 			e->d_ec = d; e->ec_bytes = n_lanes * 2 * (uint64_t)lmax;
 		}
 		unsigned long long ctr[3];
-		ECK(hipMemsetAsync(e->d_ctr, 0, 3 * sizeof(unsigned long long), e->st));
-		ECK(hipMemcpyAsync(e->d_list, list, n_list * 8, hipMemcpyHostToDevice, e->st));
-		ECK(hipEventRecord(e->e0, e->st));
+		BFCG_CK(hipMemsetAsync(e->d_ctr, 0, 3 * sizeof(unsigned long long), e->st));
+		BFCG_CK(hipMemcpyAsync(e->d_list, list, n_list * 8, hipMemcpyHostToDevice, e->st));
+		BFCG_CK(hipEventRecord(e->e0, e->st));
 		hipLaunchKernelGGL(rf ? k_ec_retry<true> : k_ec_retry<false>, dim3((unsigned)((n_lanes + EC_BT - 1) / EC_BT)), dim3(EC_BT), 0, e->st, e->o, e->P.l_pre,
 		                   e->P.tab_cshift, e->tab, d_seq, d_qual, d_cov, (const uint64_t *)e->d_off, (const uint64_t *)e->d_list, n_list, e->d_aux, e->d_aux2,
 		                   heap, stack, e->d_ec, (int)hcap, (int)scap, lmax, n_lanes, e->d_ctr, (const uint32_t *)e->d_oaux, (const uint32_t *)e->d_oaux2);
-		ECK(hipGetLastError());
-		ECK(hipEventRecord(e->e1, e->st));
-		ECK(hipMemcpyAsync(aux2, e->d_aux2, n_reads * 4, hipMemcpyDeviceToHost, e->st));
-		ECK(hipMemcpyAsync(ctr, e->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->st));
-		ECK(hipStreamSynchronize(e->st));
+		BFCG_CK(hipGetLastError());
+		BFCG_CK(hipEventRecord(e->e1, e->st));
+		BFCG_CK(hipMemcpyAsync(aux2, e->d_aux2, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+		BFCG_CK(hipMemcpyAsync(ctr, e->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->st));
+		BFCG_CK(hipStreamSynchronize(e->st));
 		float ms = 0;
-		ECK(hipEventElapsedTime(&ms, e->e0, e->e1));
+		BFCG_CK(hipEventElapsedTime(&ms, e->e0, e->e1));
 		e->last_ms += ms;
 		e->last_lookups += ctr[1];
 		uint64_t m = 0;
 		for (uint64_t i = 0; i < n_list; ++i) if (aux2[list[i]] == BFCG_EC_FALLBACK) list[m++] = list[i];
-		if (m != ctr[2]) return ec_err("%s: the retry kernel left %llu reads, their marks say %llu", fn, ctr[2], (unsigned long long)m);
+		if (m != ctr[2]) return bfcg::fail("%s: the retry kernel left %llu reads, their marks say %llu", fn, ctr[2], (unsigned long long)m);
 		n_list = m;
 	}
 	e->retry_reads += n_first;
@@ -384,7 +367,7 @@ static int ec_retry(bfcg_ec_t *e, const char *fn, int rf, uint8_t *d_seq, uint8_
                     uint32_t *aux2, uint64_t n_left)
 {
 	uint64_t *list = (uint64_t *)malloc(n_left * 8);
-	if (!list) return ec_err("%s: out of host memory", fn);
+	if (!list) return bfcg::fail("%s: out of host memory", fn);
 	Heap1 *big_heap = nullptr;
 	Stack1 *big_stack = nullptr;
 	const int rc = ec_retry_rounds(e, fn, rf, d_seq, d_qual, d_cov, off, n_reads, aux2, list, &big_heap, &big_stack);
@@ -399,72 +382,72 @@ static int ec_batch(bfcg_ec_t *e, const char *fn, uint8_t *seq, uint8_t *qual, u
                     const uint32_t *ori_aux, const uint32_t *ori_aux2, uint32_t *aux, uint32_t *aux2)
 {
 	const int rf = ori_aux != nullptr;
-	if (!e || !seq || !off || !aux || !aux2 || (rf && !ori_aux2)) return ec_err("bad arguments to %s", fn);
+	if (!e || !seq || !off || !aux || !aux2 || (rf && !ori_aux2)) return bfcg::fail("bad arguments to %s", fn);
 	if (rf != e->refine)
-		return ec_err(rf ? "%s: the corrector was made without refine_ec (bfcg_ec_batch corrects in table mode)"
+		return bfcg::fail(rf ? "%s: the corrector was made without refine_ec (bfcg_ec_batch corrects in table mode)"
 		                 : "%s: the corrector was made with refine_ec (bfcg_ec_batch_refine takes the reads' earlier stats)", fn);
-	if (n_pos > e->max_pos || n_reads > e->max_reads) return ec_err("correction batch exceeds the capacity given to bfcg_ec_create");
-	if (n_reads && off[n_reads] != n_pos) return ec_err("%s: off[n_reads] must be n_pos", fn);
+	if (n_pos > e->max_pos || n_reads > e->max_reads) return bfcg::fail("correction batch exceeds the capacity given to bfcg_ec_create");
+	if (n_reads && off[n_reads] != n_pos) return bfcg::fail("%s: off[n_reads] must be n_pos", fn);
 	e->last_ms = 0; e->last_lookups = 0; e->last_host = 0;
 	if (n_reads == 0) return 0;
 	for (uint64_t r = 0; r < n_reads; ++r)                       // every read ends in its separator inside the batch
-		if (off[r + 1] <= off[r]) return ec_err("%s: read %llu has no separator", fn, (unsigned long long)r);
+		if (off[r + 1] <= off[r]) return bfcg::fail("%s: read %llu has no separator", fn, (unsigned long long)r);
 	uint8_t *d_seq = (uint8_t *)bfcg_kcov_dev_seq(e->kc);
 	const uint16_t *d_cov = (const uint16_t *)bfcg_kcov_dev_out(e->kc);
 	uint8_t *d_ec_seq = rf ? e->d_oseq : d_seq;                   // the bytes k_ec rewrites
 	float ms_dec = 0;
-	ECK(hipSetDevice(e->device));
-	if (!rf) ECK(hipMemcpy(d_seq, seq, n_pos, hipMemcpyHostToDevice));
+	BFCG_CK(hipSetDevice(e->device));
+	if (!rf) BFCG_CK(hipMemcpy(d_seq, seq, n_pos, hipMemcpyHostToDevice));
 	else {                                                       // the coverage pass sees the decoded bases (k_decode into its input buffer)
-		ECK(hipMemcpyAsync(e->d_oseq, seq, n_pos, hipMemcpyHostToDevice, e->st));
-		if (qual) ECK(hipMemcpyAsync(e->d_qual, qual, n_pos, hipMemcpyHostToDevice, e->st));
-		ECK(hipMemcpyAsync(e->d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice, e->st));
-		ECK(hipMemcpyAsync(e->d_oaux, ori_aux, n_reads * 4, hipMemcpyHostToDevice, e->st));
-		ECK(hipMemcpyAsync(e->d_oaux2, ori_aux2, n_reads * 4, hipMemcpyHostToDevice, e->st));
+		BFCG_CK(hipMemcpyAsync(e->d_oseq, seq, n_pos, hipMemcpyHostToDevice, e->st));
+		if (qual) BFCG_CK(hipMemcpyAsync(e->d_qual, qual, n_pos, hipMemcpyHostToDevice, e->st));
+		BFCG_CK(hipMemcpyAsync(e->d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice, e->st));
+		BFCG_CK(hipMemcpyAsync(e->d_oaux, ori_aux, n_reads * 4, hipMemcpyHostToDevice, e->st));
+		BFCG_CK(hipMemcpyAsync(e->d_oaux2, ori_aux2, n_reads * 4, hipMemcpyHostToDevice, e->st));
 		const uint64_t per = DEC_BT / DEC_W;
-		ECK(hipEventRecord(e->e0, e->st));
+		BFCG_CK(hipEventRecord(e->e0, e->st));
 		hipLaunchKernelGGL(k_decode, dim3((unsigned)((n_reads + per - 1) / per)), dim3(DEC_BT), 0, e->st, e->d_oseq, qual ? e->d_qual : nullptr,
 		                   (const uint64_t *)e->d_off, n_reads, d_seq);
-		ECK(hipGetLastError());
-		ECK(hipEventRecord(e->e1, e->st));
-		ECK(hipStreamSynchronize(e->st));                         // bfcg_kcov_batch runs on a stream of its own
-		ECK(hipEventElapsedTime(&ms_dec, e->e0, e->e1));
+		BFCG_CK(hipGetLastError());
+		BFCG_CK(hipEventRecord(e->e1, e->st));
+		BFCG_CK(hipStreamSynchronize(e->st));                         // bfcg_kcov_batch runs on a stream of its own
+		BFCG_CK(hipEventElapsedTime(&ms_dec, e->e0, e->e1));
 	}
 	if (bfcg_kcov_batch(e->kc, nullptr, d_seq, n_pos, e->o.min_cov, nullptr) != 0) return -1;
 	const float ms_cov = bfcg_kcov_last_ms(e->kc) + ms_dec;
 	if (!rf) {
-		if (qual) ECK(hipMemcpyAsync(e->d_qual, qual, n_pos, hipMemcpyHostToDevice, e->st));
-		ECK(hipMemcpyAsync(e->d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice, e->st));
+		if (qual) BFCG_CK(hipMemcpyAsync(e->d_qual, qual, n_pos, hipMemcpyHostToDevice, e->st));
+		BFCG_CK(hipMemcpyAsync(e->d_off, off, (n_reads + 1) * 8, hipMemcpyHostToDevice, e->st));
 	}
-	ECK(hipMemsetAsync(e->d_ctr, 0, 3 * sizeof(unsigned long long), e->st));
+	BFCG_CK(hipMemsetAsync(e->d_ctr, 0, 3 * sizeof(unsigned long long), e->st));
 	uint64_t lanes = (n_reads + EC_BT - 1) / EC_BT * EC_BT;
 	if (lanes > e->lanes) lanes = e->lanes;
-	ECK(hipEventRecord(e->e0, e->st));
+	BFCG_CK(hipEventRecord(e->e0, e->st));
 	hipLaunchKernelGGL(rf ? k_ec<true> : k_ec<false>, dim3((unsigned)(lanes / EC_BT)), dim3(EC_BT), 0, e->st, e->o, e->P.l_pre, e->P.tab_cshift, e->tab,
 	                   d_ec_seq, qual ? e->d_qual : nullptr, d_cov, (const uint64_t *)e->d_off, n_reads, e->d_aux, e->d_aux2, e->d_heap, e->d_stack,
 	                   e->d_ec, e->hcap, e->scap, e->lmax, e->d_ctr, (const uint32_t *)e->d_oaux, (const uint32_t *)e->d_oaux2);
-	ECK(hipGetLastError());
-	ECK(hipEventRecord(e->e1, e->st));
+	BFCG_CK(hipGetLastError());
+	BFCG_CK(hipEventRecord(e->e1, e->st));
 	unsigned long long ctr[3];
 	const int attached = e->ch == nullptr;                       // the streams leave the device behind the retry rounds, if there are any
 	if (!attached) {
-		ECK(hipMemcpyAsync(seq, d_ec_seq, n_pos, hipMemcpyDeviceToHost, e->st));
-		if (qual) ECK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
-		ECK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+		BFCG_CK(hipMemcpyAsync(seq, d_ec_seq, n_pos, hipMemcpyDeviceToHost, e->st));
+		if (qual) BFCG_CK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
+		BFCG_CK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
 	}
-	ECK(hipMemcpyAsync(aux2, e->d_aux2, n_reads * 4, hipMemcpyDeviceToHost, e->st));
-	ECK(hipMemcpyAsync(ctr, e->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->st));
-	ECK(hipStreamSynchronize(e->st));
+	BFCG_CK(hipMemcpyAsync(aux2, e->d_aux2, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+	BFCG_CK(hipMemcpyAsync(ctr, e->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, e->st));
+	BFCG_CK(hipStreamSynchronize(e->st));
 	float ms = 0;
-	ECK(hipEventElapsedTime(&ms, e->e0, e->e1));
+	BFCG_CK(hipEventElapsedTime(&ms, e->e0, e->e1));
 	e->last_ms = ms_cov + ms;
 	e->last_lookups = ctr[1];
 	if (attached) {                                              // no host table: the reads k_ec left are corrected on the device too
 		if (ctr[2] && ec_retry(e, fn, rf, d_ec_seq, qual ? e->d_qual : nullptr, d_cov, off, n_reads, aux2, ctr[2]) != 0) return -1;
-		ECK(hipMemcpyAsync(seq, d_ec_seq, n_pos, hipMemcpyDeviceToHost, e->st));
-		if (qual) ECK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
-		ECK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
-		ECK(hipStreamSynchronize(e->st));
+		BFCG_CK(hipMemcpyAsync(seq, d_ec_seq, n_pos, hipMemcpyDeviceToHost, e->st));
+		if (qual) BFCG_CK(hipMemcpyAsync(qual, e->d_qual, n_pos, hipMemcpyDeviceToHost, e->st));
+		BFCG_CK(hipMemcpyAsync(aux, e->d_aux, n_reads * 4, hipMemcpyDeviceToHost, e->st));
+		BFCG_CK(hipStreamSynchronize(e->st));
 		return 0;
 	}
 	for (uint64_t r = 0; r < n_reads; ++r) {                     // the reads the device left to the host instance
@@ -488,7 +471,7 @@ extern "C" int bfcg_ec_batch(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t
 extern "C" int bfcg_ec_batch_refine(bfcg_ec_t *e, uint8_t *seq, uint8_t *qual, uint64_t n_pos, const uint64_t *off, uint64_t n_reads,
                                     const uint32_t *ori_aux, const uint32_t *ori_aux2, uint32_t *aux, uint32_t *aux2)
 {
-	if (!ori_aux) return ec_err("bad arguments to bfcg_ec_batch_refine");
+	if (!ori_aux) return bfcg::fail("bad arguments to bfcg_ec_batch_refine");
 	return ec_batch(e, "bfcg_ec_batch_refine", seq, qual, n_pos, off, n_reads, ori_aux, ori_aux2, aux, aux2);
 }
 

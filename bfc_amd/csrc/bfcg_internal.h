@@ -1,4 +1,5 @@
-// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip) and the host context (bfcg_ctx.hip)
+// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_ec.hip, bfcg_kmers.hip):
+// kernel parameters and launchers, the one error channel, the resident registry, what the satellites borrow from a context
 #pragma once
 #include <hip/hip_runtime.h>
 #define BFCG_TILE1 4096
@@ -21,6 +22,7 @@ static constexpr int bfcg_tile1_of_rw(int rw) { return rw == 3 ? 4096 : 3072; }
 #define BFCG_ABL(P, bits) 0
 #endif
 #include <stdint.h>
+struct bfcg_ctx; struct bfcg_kcov; /* include/bfc_gpu.h: bfcg_ctx_t, bfcg_kcov_t */
 
 namespace bfcg {
 
@@ -121,5 +123,29 @@ void run_commit_pages(const KParams &P, const BatchBufs &B, uint32_t n_fine, uin
 #define BFCG_SEG_TOTAL_MAX 24 /* slots per region at most (seg_home has 26 bits): 2^10 blocks */
 void run_table_rehash(const KParams &P, const unsigned long long *old_tab, int cshift_old, unsigned long long *new_tab,
                       const unsigned long long *old_first, unsigned long long *new_first, hipStream_t st);
+
+// ---- the one error channel of the host files (bfcg_mg.hip's GHIP / grp_err mark a group failed instead and do not return)
+// the thread's message (bfcg_last_error) and the [E::bfcg] line on stderr; returns -1.  Defined in bfcg_ctx.hip.
+#define BFCG_LOCAL __attribute__((visibility("hidden"))) /* shared between the library's files, not exported from it */
+BFCG_LOCAL int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+// a HIP call in a function that returns int
+#define BFCG_CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bfcg::fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+// ... and in a creator: `cleanup` releases what was made so far (the object's destroy function, which takes a half-built object; (void)0 before
+// there is one), HIP's per-thread last error is cleared -- a failed hipMalloc leaves it set, and the next object's check behind a launch would
+// report it as its own --, the creator returns NULL
+#define BFCG_CKN(cleanup, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { bfcg::fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); cleanup; (void)hipGetLastError(); return NULL; } } while (0)
+
+// ---- device copies left in HBM behind host filters and tables (bfcg_query.hip): k == 0 marks a filter's entry (n_shift says which), a table's carries k, l_pre, cshift
+struct resident_t { const void *host; void *dev; int device, n_shift, k, l_pre, cshift; };
+BFCG_LOCAL int resident_put(const resident_t &r); // -1: the registry is full (the caller keeps r.dev)
+BFCG_LOCAL void *resident_take(const void *host, int device, int n_shift, int k, int l_pre, int cshift); // the copy and its ownership, or NULL
+
+// ---- what the satellites borrow
+// a counting context's table (bfcg_ctx.hip): drained, in the host's layout, not exported; k of a table-mode context, -1 for a filter-mode one
+const unsigned long long *ctx_borrow_table(::bfcg_ctx *c, KParams *P, int *device);
+int ctx_table_k(::bfcg_ctx *c);
+// a coverage pass's table, probe parameters and device, for the corrector behind it (bfcg_query.hip)
+const unsigned long long *kcov_table(::bfcg_kcov *t, KParams *P, int *device);
+int kcov_adopted(::bfcg_kcov *t);
 
 } // namespace bfcg

@@ -13,25 +13,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <stdarg.h>
 #include "bfc_gpu.h"
 #include "bfcg_internal.h"
 #include "bfc_host.h"
 #include "bfcg_kdec.h"
-
-extern "C" void bfcg_set_error(const char *msg);
-namespace bfcg { const unsigned long long *ctx_borrow_table(bfcg_ctx_t *c, KParams *P, int *device); }
-
-static int set_err(const char *fmt, ...)
-{
-	char buf[512];
-	va_list ap;
-	va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-	bfcg_set_error(buf);
-	return -1;
-}
-#define HIPCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return set_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define HIPCKN(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return NULL; } } while (0)
 
 namespace {
 
@@ -222,34 +207,33 @@ struct bfcg_kmers {
 };
 
 // a failure after the calloc frees what was made so far (bfcg_kmers_destroy takes a half-built object)
-#define KM_CKN(t, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); bfcg_kmers_destroy(t); return NULL; } } while (0)
 
 static bfcg_kmers_t *kmers_new(int k, int l_pre, int cshift, int device)
 {
-	if (l_pre + cshift < 1 || l_pre + cshift > 40) { set_err("a count table of 2^%d slots cannot be read out", l_pre + cshift); return NULL; }
-	HIPCKN(hipSetDevice(device));
+	if (l_pre + cshift < 1 || l_pre + cshift > 40) { bfcg::fail("a count table of 2^%d slots cannot be read out", l_pre + cshift); return NULL; }
+	BFCG_CKN((void)0, hipSetDevice(device));
 	bfcg_kmers_t *t = (bfcg_kmers_t *)calloc(1, sizeof(bfcg_kmers_t));
-	if (!t) { set_err("out of host memory"); return NULL; }
+	if (!t) { bfcg::fail("out of host memory"); return NULL; }
 	t->k = k; t->l_pre = l_pre; t->cshift = cshift; t->device = device;
-	KM_CKN(t, hipStreamCreate(&t->st));
-	KM_CKN(t, hipEventCreate(&t->e0)); KM_CKN(t, hipEventCreate(&t->e1));
-	KM_CKN(t, hipMalloc(&t->d_hist, HIST_BINS * 8));
-	KM_CKN(t, hipMalloc(&t->d_sizes, 4ULL << l_pre));
+	BFCG_CKN(bfcg_kmers_destroy(t), hipStreamCreate(&t->st));
+	BFCG_CKN(bfcg_kmers_destroy(t), hipEventCreate(&t->e0)); BFCG_CKN(bfcg_kmers_destroy(t), hipEventCreate(&t->e1));
+	BFCG_CKN(bfcg_kmers_destroy(t), hipMalloc(&t->d_hist, HIST_BINS * 8));
+	BFCG_CKN(bfcg_kmers_destroy(t), hipMalloc(&t->d_sizes, 4ULL << l_pre));
 	return t;
 }
 
 extern "C" bfcg_kmers_t *bfcg_kmers_create(const bfc_ch_t *ch, int device)
 {
 	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { set_err("no HIP device available: the table read-out has no CPU fallback here"); return NULL; }
-	if (!ch || device < 0 || device >= ndev) { set_err("bad arguments to bfcg_kmers_create"); return NULL; }
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { bfcg::fail("no HIP device available: the table read-out has no CPU fallback here"); return NULL; }
+	if (!ch || device < 0 || device >= ndev) { bfcg::fail("bad arguments to bfcg_kmers_create"); return NULL; }
 	bfcg_kmers_t *t = kmers_new(bfc_ch_get_k(ch), bfc_ch_get_lpre(ch), bfc_ch_raw_cshift(ch), device);
 	if (!t) return NULL;
 	const uint64_t bytes = 8ULL << (t->l_pre + t->cshift);
 	unsigned long long *tab = NULL;
-	KM_CKN(t, hipMalloc(&tab, bytes));
+	BFCG_CKN(bfcg_kmers_destroy(t), hipMalloc(&tab, bytes));
 	t->table = tab; t->owns_table = 1;
-	KM_CKN(t, hipMemcpy(tab, bfc_ch_raw_slots((bfc_ch_t *)ch), bytes, hipMemcpyHostToDevice));
+	BFCG_CKN(bfcg_kmers_destroy(t), hipMemcpy(tab, bfc_ch_raw_slots((bfc_ch_t *)ch), bytes, hipMemcpyHostToDevice));
 	return t;
 }
 
@@ -280,7 +264,7 @@ extern "C" void bfcg_kmers_destroy(bfcg_kmers_t *t)
 
 extern "C" int bfcg_kmers_info(bfcg_kmers_t *t, int out[3])
 {
-	if (!t || !out) return set_err("bad arguments to bfcg_kmers_info");
+	if (!t || !out) return bfcg::fail("bad arguments to bfcg_kmers_info");
 	out[0] = t->k; out[1] = t->l_pre; out[2] = t->cshift;
 	return 0;
 }
@@ -288,31 +272,31 @@ extern "C" int bfcg_kmers_info(bfcg_kmers_t *t, int out[3])
 // one pass of k_tab_hist: the bins and the sizes land in d_hist / d_sizes
 static int run_hist(bfcg_kmers_t *t)
 {
-	HIPCK(hipSetDevice(t->device));
+	BFCG_CK(hipSetDevice(t->device));
 	const uint64_t n_pairs = 1ULL << (t->l_pre + t->cshift - 1), step = 64 * HIST_UNROLL;
 	uint64_t grid = (n_pairs + step * WAVES - 1) / (step * WAVES);
 	if (grid > 1024) grid = 1024; // four workgroups on each of the 256 CUs
 	const uint64_t waves = grid * WAVES, span = ((n_pairs + waves - 1) / waves + step - 1) / step * step;
-	HIPCK(hipMemsetAsync(t->d_hist, 0, HIST_BINS * 8, t->st));
-	HIPCK(hipMemsetAsync(t->d_sizes, 0, 4ULL << t->l_pre, t->st));
-	HIPCK(hipEventRecord(t->e0, t->st));
+	BFCG_CK(hipMemsetAsync(t->d_hist, 0, HIST_BINS * 8, t->st));
+	BFCG_CK(hipMemsetAsync(t->d_sizes, 0, 4ULL << t->l_pre, t->st));
+	BFCG_CK(hipEventRecord(t->e0, t->st));
 	hipLaunchKernelGGL(k_tab_hist, dim3((unsigned)grid), dim3(BT), 0, t->st, (const ulonglong2 *)t->table, n_pairs, span, t->cshift, t->d_hist, t->d_sizes);
-	HIPCK(hipEventRecord(t->e1, t->st));
-	HIPCK(hipGetLastError());
+	BFCG_CK(hipEventRecord(t->e1, t->st));
+	BFCG_CK(hipGetLastError());
 	return 0;
 }
 
 // k_tab_hist fills the bins and the sizes in the same pass: one call hands out both (cnt / high together, or sizes, may be NULL)
 extern "C" int bfcg_kmers_hist_sizes(bfcg_kmers_t *t, uint64_t cnt[256], uint64_t high[64], uint32_t *sizes)
 {
-	if (!t || !cnt != !high || (!cnt && !sizes)) { set_err("bad arguments to bfcg_kmers_hist_sizes"); return -2; }
+	if (!t || !cnt != !high || (!cnt && !sizes)) { bfcg::fail("bad arguments to bfcg_kmers_hist_sizes"); return -2; }
 	uint64_t h[HIST_BINS];
 	if (run_hist(t) != 0) return -2;
 	hipError_t e = cnt ? hipMemcpyAsync(h, t->d_hist, sizeof(h), hipMemcpyDeviceToHost, t->st) : hipSuccess;
 	if (e == hipSuccess && sizes) e = hipMemcpyAsync(sizes, t->d_sizes, 4ULL << t->l_pre, hipMemcpyDeviceToHost, t->st);
 	if (e == hipSuccess) e = hipStreamSynchronize(t->st);
 	if (e == hipSuccess) e = hipEventElapsedTime(&t->last_ms, t->e0, t->e1);
-	if (e != hipSuccess) { set_err("reading the histogram and the sub-table sizes back failed: %s", hipGetErrorString(e)); return -2; }
+	if (e != hipSuccess) { bfcg::fail("reading the histogram and the sub-table sizes back failed: %s", hipGetErrorString(e)); return -2; }
 	if (!cnt) return -1;
 	memcpy(cnt, h, 256 * 8); memcpy(high, h + 256, 64 * 8);
 	uint64_t max = 0; int mode = -1; // bfc_ch_hist: the largest bin with i >= 3, the first on ties
@@ -322,63 +306,63 @@ extern "C" int bfcg_kmers_hist_sizes(bfcg_kmers_t *t, uint64_t cnt[256], uint64_
 
 extern "C" int bfcg_kmers_hist(bfcg_kmers_t *t, uint64_t cnt[256], uint64_t high[64])
 {
-	if (!cnt || !high) { set_err("bad arguments to bfcg_kmers_hist"); return -2; }
+	if (!cnt || !high) { bfcg::fail("bad arguments to bfcg_kmers_hist"); return -2; }
 	return bfcg_kmers_hist_sizes(t, cnt, high, NULL);
 }
 
 extern "C" int bfcg_kmers_sub_sizes(bfcg_kmers_t *t, uint32_t *sizes)
 {
-	if (!sizes) return set_err("bad arguments to bfcg_kmers_sub_sizes");
+	if (!sizes) return bfcg::fail("bad arguments to bfcg_kmers_sub_sizes");
 	return bfcg_kmers_hist_sizes(t, NULL, NULL, sizes) == -2 ? -1 : 0;
 }
 
 extern "C" int bfcg_kmers_list(bfcg_kmers_t *t, int min_cnt, int min_diff, uint32_t sub_lo, uint32_t sub_hi, uint64_t *y, uint16_t *cnt_high, uint64_t cap, uint64_t *n)
 {
-	if (!t || !n) return set_err("bad arguments to bfcg_kmers_list");
-	if (!kdec::decodable(t->k)) return set_err("k-mers cannot be listed for k=%d: the table's key is lossless only for k <= %d (sizes and histogram work for any k)", t->k, (int)kdec::MAX_K);
-	if (sub_lo > sub_hi || (uint64_t)sub_hi > 1ULL << t->l_pre) return set_err("sub-table range [%u, %u) outside [0, 2^%d]", sub_lo, sub_hi, t->l_pre);
-	if (cap && (!y || !cnt_high)) return set_err("bfcg_kmers_list needs output buffers for cap=%llu", (unsigned long long)cap);
+	if (!t || !n) return bfcg::fail("bad arguments to bfcg_kmers_list");
+	if (!kdec::decodable(t->k)) return bfcg::fail("k-mers cannot be listed for k=%d: the table's key is lossless only for k <= %d (sizes and histogram work for any k)", t->k, (int)kdec::MAX_K);
+	if (sub_lo > sub_hi || (uint64_t)sub_hi > 1ULL << t->l_pre) return bfcg::fail("sub-table range [%u, %u) outside [0, 2^%d]", sub_lo, sub_hi, t->l_pre);
+	if (cap && (!y || !cnt_high)) return bfcg::fail("bfcg_kmers_list needs output buffers for cap=%llu", (unsigned long long)cap);
 	*n = 0; t->last_ms = 0;
 	if (sub_lo == sub_hi) return 0;
-	HIPCK(hipSetDevice(t->device));
+	BFCG_CK(hipSetDevice(t->device));
 	ListGeom G;
 	G.s_lo = (uint64_t)sub_lo << t->cshift; G.s_hi = (uint64_t)sub_hi << t->cshift; G.base = G.s_lo & ~1ULL;
 	G.k = t->k; G.l_pre = t->l_pre; G.cshift = t->cshift; G.min_cnt = min_cnt; G.min_diff = min_diff;
 	const uint64_t n_blk = (G.s_hi - G.base + LIST_BLK - 1) / LIST_BLK, per = SCAN_BT * SCAN_PER, n_pad = (n_blk + per - 1) / per * per;
-	if (n_blk >= 1ULL << 24) return set_err("sub-table range of %llu slots is too large for one listing: walk it in pieces", (unsigned long long)(G.s_hi - G.s_lo)); // a launch has fewer than 2^32 threads
+	if (n_blk >= 1ULL << 24) return bfcg::fail("sub-table range of %llu slots is too large for one listing: walk it in pieces", (unsigned long long)(G.s_hi - G.s_lo)); // a launch has fewer than 2^32 threads
 	if (n_pad > t->blk_cap) {
 		(void)hipFree(t->d_cnt); (void)hipFree(t->d_off); t->d_cnt = NULL; t->d_off = NULL; t->blk_cap = 0;
-		HIPCK(hipMalloc(&t->d_cnt, n_pad * 4)); HIPCK(hipMalloc(&t->d_off, (n_pad + 1) * 8));
+		BFCG_CK(hipMalloc(&t->d_cnt, n_pad * 4)); BFCG_CK(hipMalloc(&t->d_off, (n_pad + 1) * 8));
 		t->blk_cap = n_pad;
 	}
 	float ms1 = 0, ms2 = 0;
-	if (n_pad > n_blk) HIPCK(hipMemsetAsync(t->d_cnt + n_blk, 0, (n_pad - n_blk) * 4, t->st)); // the scan's padding
-	HIPCK(hipEventRecord(t->e0, t->st));
+	if (n_pad > n_blk) BFCG_CK(hipMemsetAsync(t->d_cnt + n_blk, 0, (n_pad - n_blk) * 4, t->st)); // the scan's padding
+	BFCG_CK(hipEventRecord(t->e0, t->st));
 	hipLaunchKernelGGL(k_list_count, dim3((unsigned)n_blk), dim3(BT), 0, t->st, (const ulonglong2 *)t->table, G, t->d_cnt);
 	hipLaunchKernelGGL(k_list_scan, dim3(1), dim3(SCAN_BT), 0, t->st, t->d_cnt, n_pad, t->d_off);
-	HIPCK(hipEventRecord(t->e1, t->st));
-	HIPCK(hipGetLastError());
+	BFCG_CK(hipEventRecord(t->e1, t->st));
+	BFCG_CK(hipGetLastError());
 	unsigned long long total = 0;
-	HIPCK(hipMemcpyAsync(&total, t->d_off + n_pad, 8, hipMemcpyDeviceToHost, t->st));
-	HIPCK(hipStreamSynchronize(t->st));
-	HIPCK(hipEventElapsedTime(&ms1, t->e0, t->e1));
+	BFCG_CK(hipMemcpyAsync(&total, t->d_off + n_pad, 8, hipMemcpyDeviceToHost, t->st));
+	BFCG_CK(hipStreamSynchronize(t->st));
+	BFCG_CK(hipEventElapsedTime(&ms1, t->e0, t->e1));
 	t->last_ms = ms1;
 	*n = total;
 	if (total > cap) return 1; // nothing is written: the caller comes back with room for *n
 	if (total == 0) return 0;
 	if (total > t->out_cap) {
 		(void)hipFree(t->d_y); (void)hipFree(t->d_ch); t->d_y = NULL; t->d_ch = NULL; t->out_cap = 0;
-		HIPCK(hipMalloc(&t->d_y, total * 16)); HIPCK(hipMalloc(&t->d_ch, total * 2));
+		BFCG_CK(hipMalloc(&t->d_y, total * 16)); BFCG_CK(hipMalloc(&t->d_ch, total * 2));
 		t->out_cap = total;
 	}
-	HIPCK(hipEventRecord(t->e0, t->st));
+	BFCG_CK(hipEventRecord(t->e0, t->st));
 	hipLaunchKernelGGL(k_list_emit, dim3((unsigned)n_blk), dim3(BT), 0, t->st, (const ulonglong2 *)t->table, G, t->d_off, t->d_y, t->d_ch, (uint64_t)total);
-	HIPCK(hipEventRecord(t->e1, t->st));
-	HIPCK(hipGetLastError());
-	HIPCK(hipMemcpyAsync(y, t->d_y, total * 16, hipMemcpyDeviceToHost, t->st));
-	HIPCK(hipMemcpyAsync(cnt_high, t->d_ch, total * 2, hipMemcpyDeviceToHost, t->st));
-	HIPCK(hipStreamSynchronize(t->st));
-	HIPCK(hipEventElapsedTime(&ms2, t->e0, t->e1));
+	BFCG_CK(hipEventRecord(t->e1, t->st));
+	BFCG_CK(hipGetLastError());
+	BFCG_CK(hipMemcpyAsync(y, t->d_y, total * 16, hipMemcpyDeviceToHost, t->st));
+	BFCG_CK(hipMemcpyAsync(cnt_high, t->d_ch, total * 2, hipMemcpyDeviceToHost, t->st));
+	BFCG_CK(hipStreamSynchronize(t->st));
+	BFCG_CK(hipEventElapsedTime(&ms2, t->e0, t->e1));
 	t->last_ms = ms1 + ms2;
 	return 0;
 }
