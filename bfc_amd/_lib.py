@@ -157,6 +157,14 @@ SYMBOLS = {
     "bfcg_kmer_2str": (None, [C.c_int, u64p, C.c_char_p]),
     "bfcg_kmers_format": (C.c_uint64, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "bfcg_kmers_format_sizes": (C.c_uint64, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_kmers_lookup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, u64p]),
+    "bfcg_kmers_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_kmer_from_str": (C.c_int, [C.c_int, C.c_char_p, u64p]),
+    "bfcg_kmer_occ_host": (C.c_int, [C.c_void_p, u64p]),
+    "bfcg_kmers_occ_host": (None, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_kmers_parse": (C.c_uint64, [C.c_int, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
+    "bfcg_lookup_format": (C.c_uint64, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_profile_format": (C.c_uint64, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "bfcg_hash_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_seen_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
 }

@@ -107,6 +107,14 @@ class HostTable:
             z.x[i] = int(x[i])
         return self.L.bfc_ch_kmer_occ(self.ptr, C.byref(z))
 
+    def occ_planes(self, y):
+        """bfc_ch_kmer_occ of k-mers given as listing-style planes, y (n, 2) u64, of either strand: int16 (n), -1 = absent.  The host
+        twin of GpuKmers.lookup (bfcg_kmers_occ_host)."""
+        y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 2)
+        out = np.empty(len(y), dtype=np.int16)
+        self.L.bfcg_kmers_occ_host(self.ptr, y.ctypes.data, len(y), out.ctypes.data)
+        return out
+
     def insert(self, y0, y1, is_high, forced=1):
         return self.L.bfc_ch_insert(self.ptr, (C.c_uint64 * 2)(y0, y1), int(is_high), forced)
 
@@ -556,7 +564,8 @@ class GpuKcov:
 
 class GpuKmers:
     """The count table read out on the GPU (bfcg_kmers_*): what the reference's hash2cnt prints from a dump -- the spectrum, the sub-table
-    sizes and the k-mers with their counts.  `table` is a HostTable (uploaded once) or a GpuCounter whose device table is read in place
+    sizes and the k-mers with their counts -- and asked by k-mer (bfcg_lookup.hip): the counts of given k-mers, the count under every
+    position of a sequence.  `table` is a HostTable (uploaded once) or a GpuCounter whose device table is read in place
     (it must outlive this object and must not count meanwhile)."""
 
     def __init__(self, table, device=0):
@@ -572,6 +581,7 @@ class GpuKmers:
         self.L.bfcg_kmers_info(self.t, info)
         self.k, self.l_pre, self.cshift = info[0], info[1], info[2]
         self._ms = 0.0
+        self.n_found = 0
 
     def close(self):
         if self.t:
@@ -662,8 +672,42 @@ class GpuKmers:
         n = self.L.bfcg_kmers_format(self.k, y.ctypes.data, cnt_high.ctypes.data, len(cnt_high), buf)
         return buf.raw[:n]
 
+    def lookup(self, y):
+        """The counts of given k-mers: y (n, 2) u64 as list() hands them out, on either strand (bits at and above k are ignored) ->
+        int16 (n), high << 8 | count as bfc_ch_kmer_occ, -1 = the table does not hold it.  `n_found` then is the number found."""
+        y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 2)
+        out, nf = np.empty(len(y), dtype=np.int16), C.c_uint64()
+        if self.L.bfcg_kmers_lookup(self.t, y.ctypes.data, len(y), out.ctypes.data, C.byref(nf)) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self.n_found = int(nf.value)
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return out
+
+    def lookup_strings(self, strs):
+        """lookup() of k-mers given as text (bfcg_kmers_parse); raises BfcGpuError naming the first entry that is not k bytes of ACGTacgt."""
+        strs = list(strs)
+        text = "\n".join(strs).encode()
+        y, bad = np.zeros((len(strs), 2), dtype=np.uint64), C.c_uint64()
+        n = self.L.bfcg_kmers_parse(self.k, text, len(text), y.ctypes.data, len(strs), C.byref(bad))
+        if n != len(strs):  # a malformed entry, or one that the line grammar skips or splits
+            one = (C.c_uint64 * 2)()
+            i = next(i for i, v in enumerate(strs) if self.L.bfcg_kmer_from_str(self.k, v.encode(), one) != 0)
+            raise BfcGpuError("entry %d is not a %d-mer of ACGT: %r" % (i, self.k, strs[i]))
+        return self.lookup(y)
+
+    def profile(self, seq_stream, d_seq=None, n_pos=None):
+        """The count under every position of a batch stream (host array, or d_seq / n_pos on the device): int16 per position for the
+        k-mer ENDING there -- high << 8 | count, -1 = absent from the table, -2 = no k-mer ends here."""
+        s = np.ascontiguousarray(seq_stream, dtype=np.uint8) if seq_stream is not None else None
+        n = len(s) if s is not None else int(n_pos)
+        out = np.empty(n, dtype=np.int16)
+        if self.L.bfcg_kmers_profile(self.t, s.ctypes.data if s is not None else None, None if s is not None else d_seq, n, out.ctypes.data) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return out
+
     def last_ms(self):
-        """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() one pass, list() all its pieces."""
+        """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces."""
         return self._ms
 
 

@@ -553,3 +553,110 @@ void bfcg_pack_planes(const uint8_t *seq, const uint8_t *qual, uint64_t lo, uint
 		if (qual) planes[3 * plane_words + w] = mq;
 	}
 }
+
+/* ---- look-ups by k-mer on the host (include/bfc_gpu.h: the twins of bfcg_kmers_lookup / bfcg_kmers_profile, and their text forms) ----
+ * A k-mer is the two bit planes a listing hands out: bit l = the base l from the 3' end, low / high code bit (kmer.h:97-104). */
+static inline uint64_t brev_k(uint64_t v, int k) /* the low k bits reversed */
+{
+	v = (v >> 1 & 0x5555555555555555ULL) | (v & 0x5555555555555555ULL) << 1;
+	v = (v >> 2 & 0x3333333333333333ULL) | (v & 0x3333333333333333ULL) << 2;
+	v = (v >> 4 & 0x0f0f0f0f0f0f0f0fULL) | (v & 0x0f0f0f0f0f0f0f0fULL) << 4;
+	return __builtin_bswap64(v) >> (64 - k);
+}
+int bfcg_kmer_occ_host(const bfc_ch_t *ch, const uint64_t y[2])
+{
+	const int k = ch->k;
+	const uint64_t m = (1ULL << k) - 1;
+	bfc_kmer_t z; /* kmer.h:13-16: the given strand with its newest base at bit 0, the other one complemented with the oldest base there */
+	z.x[0] = y[0] & m; z.x[1] = y[1] & m;
+	z.x[2] = ~brev_k(y[0], k) & m; z.x[3] = ~brev_k(y[1], k) & m;
+	return bfc_ch_kmer_occ(ch, &z);
+}
+void bfcg_kmers_occ_host(const bfc_ch_t *ch, const uint64_t *y, uint64_t n, int16_t *out)
+{
+	uint64_t i;
+	for (i = 0; i < n; ++i) out[i] = (int16_t)bfcg_kmer_occ_host(ch, y + 2 * i);
+}
+
+static inline int base_code(char c) /* A C G T in either case -> 0..3, anything else -1 */
+{
+	switch (c & 0xDF) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; }
+	return -1;
+}
+static int kmer_from_field(int k, const char *s, uint64_t n, uint64_t y[2])
+{
+	uint64_t a = 0, b = 0;
+	int l;
+	if (k < 1 || k > 63 || n != (uint64_t)k) return -1;
+	for (l = 0; l < k; ++l) {
+		const int c = base_code(s[k - 1 - l]);
+		if (c < 0) return -1;
+		a |= (uint64_t)(c & 1) << l; b |= (uint64_t)(c >> 1) << l;
+	}
+	y[0] = a; y[1] = b;
+	return 0;
+}
+int bfcg_kmer_from_str(int k, const char *s, uint64_t y[2]) { return s ? kmer_from_field(k, s, strlen(s), y) : -1; }
+
+/* the next line of text[*pos, len): its first field (up to tab / space / CR) as [*beg, *beg + *n); 0 at the end of the text */
+static int next_field(const char *text, uint64_t len, uint64_t *pos, uint64_t *beg, uint64_t *n)
+{
+	uint64_t p = *pos, e;
+	if (p >= len) return 0;
+	*beg = p;
+	while (p < len && text[p] != '\n' && text[p] != '\t' && text[p] != ' ' && text[p] != '\r') ++p;
+	*n = p - *beg;
+	for (e = p; e < len && text[e] != '\n'; ++e) {}
+	*pos = e < len ? e + 1 : len;
+	return 1;
+}
+static inline int skipped_line(const char *text, uint64_t beg, uint64_t n) { return n == 0 || text[beg] == '>'; }
+
+uint64_t bfcg_kmers_parse(int k, const char *text, uint64_t len, uint64_t *y, uint64_t cap, uint64_t *bad_line)
+{
+	uint64_t pos = 0, beg, n, line = 0, got = 0;
+	if (bad_line) *bad_line = 0;
+	while (got < cap && next_field(text, len, &pos, &beg, &n)) {
+		++line;
+		if (skipped_line(text, beg, n)) continue;
+		if (kmer_from_field(k, text + beg, n, y + 2 * got) != 0) { if (bad_line) *bad_line = line; break; }
+		++got;
+	}
+	return got;
+}
+
+static inline char *put_dec(char *p, uint32_t v)
+{
+	char tmp[10]; int n = 0;
+	do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+	while (n) *p++ = tmp[--n];
+	return p;
+}
+/* the answer lines of the first n k-mer lines of `text` (bfcg_kmers_parse's grammar): the k-mer as given, count, high; an absent k-mer has 0 0 */
+uint64_t bfcg_lookup_format(const char *text, uint64_t len, const int16_t *occ, uint64_t n, char *buf)
+{
+	uint64_t pos = 0, beg, m, i = 0;
+	char *p = buf;
+	while (i < n && next_field(text, len, &pos, &beg, &m)) {
+		const int v = occ[i];
+		if (skipped_line(text, beg, m)) continue;
+		memcpy(p, text + beg, m); p += m; *p++ = '\t';
+		p = put_dec(p, v >= 0 ? v & 0xff : 0); *p++ = '\t';
+		p = put_dec(p, v >= 0 ? v >> 8 & 0x3f : 0); *p++ = '\n';
+		++i;
+	}
+	return (uint64_t)(p - buf);
+}
+/* one line of a count profile: the counts of n positions, space-separated; '.' where no k-mer ends (-2), 0 for an absent k-mer (-1) */
+uint64_t bfcg_profile_format(const int16_t *occ, uint64_t n, char *buf)
+{
+	uint64_t i;
+	char *p = buf;
+	for (i = 0; i < n; ++i) {
+		if (i) *p++ = ' ';
+		if (occ[i] == -2) *p++ = '.';
+		else p = put_dec(p, occ[i] >= 0 ? occ[i] & 0xff : 0);
+	}
+	*p++ = '\n';
+	return (uint64_t)(p - buf);
+}

@@ -1,8 +1,9 @@
-// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_ec.hip, bfcg_kmers.hip):
+// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip):
 // kernel parameters and launchers, the one error channel, the resident registry, what the satellites borrow from a context
 #pragma once
 #include <hip/hip_runtime.h>
 #define BFCG_TILE1 4096
+#define BFCG_BT1 256 /* threads of a workgroup that walks a tile of BFCG_TILE1 positions (k_occ, k_query, ...; k_profile in bfcg_lookup.hip) */
 #define BFCG_SCAN_CH 64
 /* records per scatter tile: 20-byte records (k > 47) take 3072 so that two workgroups' stages fit a CU's LDS */
 /* dwords per k-mer record: y0 (minus rec_n bucket bits), y1, the quality flag and the 32-bit file index in 96 or 128 bits, else 20 bytes */
@@ -23,6 +24,21 @@ static constexpr int bfcg_tile1_of_rw(int rw) { return rw == 3 ? 4096 : 3072; }
 #endif
 #include <stdint.h>
 struct bfcg_ctx; struct bfcg_kcov; /* include/bfc_gpu.h: bfcg_ctx_t, bfcg_kcov_t */
+
+/* the table read-out's object (include/bfc_gpu.h: bfcg_kmers_t): made and destroyed in bfcg_kmers.hip, which lists the table; bfcg_lookup.hip probes it */
+struct bfcg_kmers {
+	int k, l_pre, cshift, device, owns_table;
+	hipStream_t st;
+	hipEvent_t e0, e1;
+	const unsigned long long *table;
+	unsigned long long *d_hist;      // 256 + 64
+	uint32_t *d_sizes;               // 2^l_pre
+	uint32_t *d_cnt; unsigned long long *d_off; uint64_t blk_cap;   // per-block counts / offsets of a listing (grown on demand)
+	ulonglong2 *d_y; uint16_t *d_ch; uint64_t out_cap;              // a listing's device result (grown on demand)
+	ulonglong2 *d_qy; int16_t *d_qout; uint64_t q_cap;              // a lookup's staging, q_cap k-mers a piece (BFCG_LOOKUP_CAP at creation), allocated by the first lookup
+	uint8_t *d_pseq; uint64_t pseq_cap; int16_t *d_pout; uint64_t pout_cap; // a profile's stream and result (grown on demand)
+	float last_ms;
+};
 
 namespace bfcg {
 
@@ -147,5 +163,7 @@ int ctx_table_k(::bfcg_ctx *c);
 // a coverage pass's table, probe parameters and device, for the corrector behind it (bfcg_query.hip)
 const unsigned long long *kcov_table(::bfcg_kcov *t, KParams *P, int *device);
 int kcov_adopted(::bfcg_kcov *t);
+// k-mers a lookup stages per piece (bfcg_lookup.hip): a few million, or what BFCG_LOOKUP_CAP says
+BFCG_LOCAL uint64_t lookup_cap();
 
 } // namespace bfcg

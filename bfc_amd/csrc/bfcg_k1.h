@@ -64,6 +64,74 @@ __device__ __forceinline__ void bases4x(uint32_t w, int sh, uint32_t &m0, uint32
 __device__ __forceinline__ void quals4x(uint32_t w, int sh, uint32_t add, uint32_t &mq)
 { mq |= gather4(((((w & 0x7F7F7F7Fu) + add) & ~w) >> 7) & 0x01010101u) << sh; }
 
+// K1: tile of positions -> bit planes in LDS
+
+// 16 positions from `pos` on at the ragged ends of a batch (positions outside it read as separators), byte by byte
+// (a real call, results by value: met by two tiles of a batch, and inlined its 16 byte loads would cost every tile's path registers)
+static __device__ __noinline__ uint4 ragged16(const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual, int64_t n_pos, int64_t pos, int q)
+{
+	uint32_t m0 = 0, m1 = 0, mn = 0, mq = 0;
+#pragma unroll 1
+	for (int b = 0; b < 16; ++b) {
+		const int64_t pb = pos + b;
+		const bool in = pb >= 0 && pb < n_pos;
+		uint32_t w = in ? seq[pb] : (uint32_t)'\n', t0m = 0, t1m = 0, tnm = 0;
+		bases16(w | 0x0a0a0a00u, 0, t0m, t1m, tnm);
+		m0 |= (t0m & 1u) << b; m1 |= (t1m & 1u) << b; mn |= (tnm & 1u) << b;
+		mq |= (uint32_t)(qual ? (in && ((int)(int8_t)qual[pb] - 33 >= q)) : 1) << b;
+	}
+	return make_uint4(m0, m1, mn, mq);
+}
+
+template <int TILE, int BT>
+__device__ __forceinline__ void build_planes(const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual,
+                                             int64_t n_pos, int64_t t0, int q, uint32_t *planes)
+{
+	constexpr int PW = (TILE + 64) / 32 + 2;
+	const bool aligned = ((((uintptr_t)seq) | ((uintptr_t)qual)) & 15) == 0;
+	if (aligned) {
+		constexpr int NC16 = (TILE + 64) / 16;
+		unsigned short *p16 = reinterpret_cast<unsigned short *>(planes);
+		for (int c = threadIdx.x; c < NC16; c += BT) {
+			const int64_t pos = t0 - 64 + (int64_t)c * 16;
+			uint32_t m0 = 0, m1 = 0, mn = 0, mq = 0;
+			if (pos >= 0 && pos + 16 <= n_pos) {
+				uint4 s = *reinterpret_cast<const uint4 *>(seq + pos);
+				bases4x(s.x, 0, m0, m1, mn); bases4x(s.y, 4, m0, m1, mn); bases4x(s.z, 8, m0, m1, mn); bases4x(s.w, 12, m0, m1, mn);
+				if (qual) {
+					uint4 v = *reinterpret_cast<const uint4 *>(qual + pos);
+					const int T = q + 33;
+					if (T >= 1 && T <= 127) {
+						const uint32_t add = (uint32_t)(128 - T) * 0x01010101u;
+						quals4x(v.x, 0, add, mq); quals4x(v.y, 4, add, mq); quals4x(v.z, 8, add, mq); quals4x(v.w, 12, add, mq);
+					} else { quals16(v.x, 0, q, mq); quals16(v.y, 4, q, mq); quals16(v.z, 8, q, mq); quals16(v.w, 12, q, mq); }
+				} else mq = 0xffffu;
+			} else { const uint4 r = ragged16(seq, qual, n_pos, pos, q); m0 = r.x; m1 = r.y; mn = r.z; mq = r.w; } // ragged ends of the batch
+			p16[0 * PW * 2 + c] = (unsigned short)m0; p16[1 * PW * 2 + c] = (unsigned short)m1;
+			p16[2 * PW * 2 + c] = (unsigned short)mn; p16[3 * PW * 2 + c] = (unsigned short)mq;
+		}
+	} else {
+		const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+		constexpr int NCH = (TILE + 64) / 64;
+		for (int c = wave; c < NCH; c += BT / WAVE) {
+			int64_t pos = t0 - 64 + (int64_t)c * 64 + lane;
+			bool in = pos >= 0 && pos < n_pos;
+			uint32_t ch = in ? seq[pos] : (uint32_t)'\n';
+			uint32_t u = ch & 0xDFu; // fold case
+			uint32_t code = (u == 'A') ? 0u : (u == 'C') ? 1u : (u == 'G') ? 2u : (u == 'T') ? 3u : 4u;
+			bool hq = qual ? (in && ((int)(int8_t)qual[pos] - 33 >= q)) : true; // count.c:85 (signed char)
+			uint64_t b0 = __ballot(code & 1u), b1 = __ballot((code >> 1) & 1u), bn = __ballot(code >> 2), bq = __ballot(hq);
+			if (lane == 0) {
+				planes[0 * PW + 2 * c] = (uint32_t)b0; planes[0 * PW + 2 * c + 1] = (uint32_t)(b0 >> 32);
+				planes[1 * PW + 2 * c] = (uint32_t)b1; planes[1 * PW + 2 * c + 1] = (uint32_t)(b1 >> 32);
+				planes[2 * PW + 2 * c] = (uint32_t)bn; planes[2 * PW + 2 * c + 1] = (uint32_t)(bn >> 32);
+				planes[3 * PW + 2 * c] = (uint32_t)bq; planes[3 * PW + 2 * c + 1] = (uint32_t)(bq >> 32);
+			}
+		}
+	}
+	if (threadIdx.x < 8) planes[(threadIdx.x >> 1) * PW + PW - 2 + (threadIdx.x & 1)] = 0;
+}
+
 // k-mer ending at tile-relative position r (0 <= r < TILE), 32 < k < 64, on 32-bit halves (kmer_dev.h); KC > 0: k at compile time.
 // Returns false if there is none.
 template <int TILE, int KC>
@@ -103,6 +171,34 @@ __device__ __forceinline__ bool kmer_at(const uint32_t *planes, int r, int k, W 
 	is_high = window<W>(planes + 3 * PW, bit, m) == m;
 	kmer_hash_from_windows<W>(k, wl, wh, m, y0, y1);
 	return true;
+}
+
+// ---- the count under every position of a tile
+// K1 + bfc_ch_kmer_occ (htab.c:85-99) for the k-mer ENDING at every position of this workgroup's tile, against the count table in the host's
+// layout in HBM: put(e, occ) is called once for every position e < n_pos of the tile, occ = high << 8 | count, -1 for a k-mer the table
+// does not hold, -2 where no k-mer ends (a separator, the first k - 1 bases of a read, a window with a base that is not ACGT).  `planes`
+// is the workgroup's 4 * ((TILE + 64) / 32 + 2) words of LDS.  k_occ (bfcg_kernels.hip) keeps two threshold bits, k_profile
+// (bfcg_lookup.hip) the value.
+template <typename W, int TILE, int BT, typename Put>
+__device__ __forceinline__ void occ_tile(const KParams &P, const uint8_t *__restrict__ seq, int64_t n_pos, const unsigned long long *__restrict__ tab,
+                                         uint32_t *planes, Put put)
+{
+	const W m = kmask<W>(P.k);
+	const int64_t n_tiles = (n_pos + TILE - 1) / TILE;
+	const int64_t tile = xcd_tile(blockIdx.x, n_tiles);
+	if (tile >= n_tiles) return;
+	build_planes<TILE, BT>(seq, nullptr, n_pos, tile * TILE, P.q, planes);
+	__syncthreads();
+#pragma unroll 4
+	for (int j = 0; j < TILE / BT; ++j) {
+		const int r = j * BT + threadIdx.x;
+		const int64_t e = tile * TILE + r;
+		if (e >= n_pos) continue;
+		W y0, y1; bool hi;
+		int occ = -2;
+		if (kmer_at<W, TILE>(planes, r, P.k, m, y0, y1, hi)) occ = ch_get_dev(P.k, P.l_pre, P.tab_cshift, tab, (uint64_t)y0, (uint64_t)y1);
+		put(e, occ);
+	}
 }
 
 // ---- records

@@ -38,71 +38,7 @@ using namespace bfcg;
 // K1: tile of positions -> bit planes in LDS
 
 
-// 16 positions from `pos` on at the ragged ends of a batch (positions outside it read as separators), byte by byte
-// (a real call, results by value: met by two tiles of a batch, and inlined its 16 byte loads would cost every tile's path registers)
-__device__ __noinline__ uint4 ragged16(const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual, int64_t n_pos, int64_t pos, int q)
-{
-	uint32_t m0 = 0, m1 = 0, mn = 0, mq = 0;
-#pragma unroll 1
-	for (int b = 0; b < 16; ++b) {
-		const int64_t pb = pos + b;
-		const bool in = pb >= 0 && pb < n_pos;
-		uint32_t w = in ? seq[pb] : (uint32_t)'\n', t0m = 0, t1m = 0, tnm = 0;
-		bases16(w | 0x0a0a0a00u, 0, t0m, t1m, tnm);
-		m0 |= (t0m & 1u) << b; m1 |= (t1m & 1u) << b; mn |= (tnm & 1u) << b;
-		mq |= (uint32_t)(qual ? (in && ((int)(int8_t)qual[pb] - 33 >= q)) : 1) << b;
-	}
-	return make_uint4(m0, m1, mn, mq);
-}
-
-template <int TILE, int BT>
-__device__ __forceinline__ void build_planes(const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual,
-                                             int64_t n_pos, int64_t t0, int q, uint32_t *planes)
-{
-	constexpr int PW = (TILE + 64) / 32 + 2;
-	const bool aligned = ((((uintptr_t)seq) | ((uintptr_t)qual)) & 15) == 0;
-	if (aligned) {
-		constexpr int NC16 = (TILE + 64) / 16;
-		unsigned short *p16 = reinterpret_cast<unsigned short *>(planes);
-		for (int c = threadIdx.x; c < NC16; c += BT) {
-			const int64_t pos = t0 - 64 + (int64_t)c * 16;
-			uint32_t m0 = 0, m1 = 0, mn = 0, mq = 0;
-			if (pos >= 0 && pos + 16 <= n_pos) {
-				uint4 s = *reinterpret_cast<const uint4 *>(seq + pos);
-				bases4x(s.x, 0, m0, m1, mn); bases4x(s.y, 4, m0, m1, mn); bases4x(s.z, 8, m0, m1, mn); bases4x(s.w, 12, m0, m1, mn);
-				if (qual) {
-					uint4 v = *reinterpret_cast<const uint4 *>(qual + pos);
-					const int T = q + 33;
-					if (T >= 1 && T <= 127) {
-						const uint32_t add = (uint32_t)(128 - T) * 0x01010101u;
-						quals4x(v.x, 0, add, mq); quals4x(v.y, 4, add, mq); quals4x(v.z, 8, add, mq); quals4x(v.w, 12, add, mq);
-					} else { quals16(v.x, 0, q, mq); quals16(v.y, 4, q, mq); quals16(v.z, 8, q, mq); quals16(v.w, 12, q, mq); }
-				} else mq = 0xffffu;
-			} else { const uint4 r = ragged16(seq, qual, n_pos, pos, q); m0 = r.x; m1 = r.y; mn = r.z; mq = r.w; } // ragged ends of the batch
-			p16[0 * PW * 2 + c] = (unsigned short)m0; p16[1 * PW * 2 + c] = (unsigned short)m1;
-			p16[2 * PW * 2 + c] = (unsigned short)mn; p16[3 * PW * 2 + c] = (unsigned short)mq;
-		}
-	} else {
-		const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-		constexpr int NCH = (TILE + 64) / 64;
-		for (int c = wave; c < NCH; c += BT / WAVE) {
-			int64_t pos = t0 - 64 + (int64_t)c * 64 + lane;
-			bool in = pos >= 0 && pos < n_pos;
-			uint32_t ch = in ? seq[pos] : (uint32_t)'\n';
-			uint32_t u = ch & 0xDFu; // fold case
-			uint32_t code = (u == 'A') ? 0u : (u == 'C') ? 1u : (u == 'G') ? 2u : (u == 'T') ? 3u : 4u;
-			bool hq = qual ? (in && ((int)(int8_t)qual[pos] - 33 >= q)) : true; // count.c:85 (signed char)
-			uint64_t b0 = __ballot(code & 1u), b1 = __ballot((code >> 1) & 1u), bn = __ballot(code >> 2), bq = __ballot(hq);
-			if (lane == 0) {
-				planes[0 * PW + 2 * c] = (uint32_t)b0; planes[0 * PW + 2 * c + 1] = (uint32_t)(b0 >> 32);
-				planes[1 * PW + 2 * c] = (uint32_t)b1; planes[1 * PW + 2 * c + 1] = (uint32_t)(b1 >> 32);
-				planes[2 * PW + 2 * c] = (uint32_t)bn; planes[2 * PW + 2 * c + 1] = (uint32_t)(bn >> 32);
-				planes[3 * PW + 2 * c] = (uint32_t)bq; planes[3 * PW + 2 * c + 1] = (uint32_t)(bq >> 32);
-			}
-		}
-	}
-	if (threadIdx.x < 8) planes[(threadIdx.x >> 1) * PW + PW - 2 + (threadIdx.x & 1)] = 0;
-}
+// (ragged16 and build_planes are in bfcg_k1.h: k_profile of bfcg_lookup.hip builds the same planes)
 
 
 // ------------------------------------------------------------------------------------------
@@ -2078,16 +2014,10 @@ __global__ __launch_bounds__(256) void k_streak(int k, float min_frac, const uns
 
 // ------------------------------------------------------------------------------------------
 // k-mer coverage of the corrector, bfc_ec_kcov (correct.c:96-117), for every read of a batch against the count table in HBM
-//   k_occ : K1 + bfc_ch_kmer_occ (htab.c:85-99) for the k-mer ENDING at every position -> flag byte: bit0 solid_end
+//   k_occ : K1 + bfc_ch_kmer_occ (htab.c:85-99) for the k-mer ENDING at every position (occ_tile, bfcg_k1.h) -> flag byte: bit0 solid_end
 //           (count >= min_occ), bit1 high_end (high count >= min_occ+1) ; absent k-mers and non-k-mer positions give 0
 //   k_cov : lcov / hcov of every base = number of solid (solid and high) k-mers covering it = the k flags that follow it;
 //           packed like ecbase_t's bit-fields (correct.c:14-19): lcov | hcov<<6 | solid_end<<12 | high_end<<13
-
-// bfc_ch_get on the device layout (kmer_dev.h: ch_get_dev)
-__device__ __forceinline__ int table_get(const KParams &P, const unsigned long long *__restrict__ tab, uint64_t y0, uint64_t y1)
-{
-	return ch_get_dev(P.k, P.l_pre, P.tab_cshift, tab, y0, y1);
-}
 
 template <typename W, int TILE, int BT>
 __global__ __launch_bounds__(BT) void k_occ(KParams P, const uint8_t *__restrict__ seq, int64_t n_pos, int min_occ,
@@ -2095,25 +2025,9 @@ __global__ __launch_bounds__(BT) void k_occ(KParams P, const uint8_t *__restrict
 {
 	constexpr int PW = (TILE + 64) / 32 + 2;
 	__shared__ uint32_t planes[4 * PW];
-	const W m = kmask<W>(P.k);
-	const int64_t n_tiles = (n_pos + TILE - 1) / TILE;
-	const int64_t tile = xcd_tile(blockIdx.x, n_tiles);
-	if (tile >= n_tiles) return;
-	build_planes<TILE, BT>(seq, nullptr, n_pos, tile * TILE, P.q, planes);
-	__syncthreads();
-#pragma unroll 4
-	for (int j = 0; j < TILE / BT; ++j) {
-		const int r = j * BT + threadIdx.x;
-		const int64_t e = tile * TILE + r;
-		if (e >= n_pos) continue;
-		W y0, y1; bool hi;
-		uint8_t fl = 0;
-		if (kmer_at<W, TILE>(planes, r, P.k, m, y0, y1, hi)) {
-			const int occ = table_get(P, tab, (uint64_t)y0, (uint64_t)y1);
-			if (occ >= 0) fl = (uint8_t)(((occ & 0xff) >= min_occ ? 1 : 0) | ((occ >> 8 & 0x3f) >= min_occ + 1 ? 2 : 0));
-		}
-		flags[e] = fl;
-	}
+	occ_tile<W, TILE, BT>(P, seq, n_pos, tab, planes, [&](int64_t e, int occ) {
+		flags[e] = occ >= 0 ? (uint8_t)(((occ & 0xff) >= min_occ ? 1 : 0) | ((occ >> 8 & 0x3f) >= min_occ + 1 ? 2 : 0)) : (uint8_t)0;
+	});
 }
 
 // TILE positions per workgroup; the flags of the TILE+64 positions from the tile's start become two bit rows in LDS
@@ -2154,7 +2068,7 @@ namespace bfcg {
 static inline int grid_for(int64_t n_tiles, int cap) { return (int)(n_tiles < cap ? (n_tiles > 0 ? n_tiles : 1) : cap); }
 
 #define TILE1 BFCG_TILE1
-#define BT1 256
+#define BT1 BFCG_BT1
 // k_scatter1's tile by record size: 4096 positions, 3072 for 20-byte records -- two workgroups of 512 threads per CU (56 / 73 / 68 KiB of LDS).
 // (Three workgroups of 3584 positions, 768 threads on 4608, 1024 threads, one memory-in wave beside seven hashing waves: all measured, none
 // faster -- the kernel's floor is its skeleton of LDS ranks, scan, staging and barriers, not the hashing: DESIGN.md section 6b.)

@@ -194,17 +194,7 @@ __global__ __launch_bounds__(BT) void k_list_emit(const ulonglong2 *__restrict__
 
 // ---- the context ------------------------------------------------------------------------------------------------------------------
 
-struct bfcg_kmers {
-	int k, l_pre, cshift, device, owns_table;
-	hipStream_t st;
-	hipEvent_t e0, e1;
-	const unsigned long long *table;
-	unsigned long long *d_hist;      // 256 + 64
-	uint32_t *d_sizes;               // 2^l_pre
-	uint32_t *d_cnt; unsigned long long *d_off; uint64_t blk_cap;   // per-block counts / offsets of a listing (grown on demand)
-	ulonglong2 *d_y; uint16_t *d_ch; uint64_t out_cap;              // a listing's device result (grown on demand)
-	float last_ms;
-};
+// (struct bfcg_kmers: bfcg_internal.h -- bfcg_lookup.hip works on the same object)
 
 // a failure after the calloc frees what was made so far (bfcg_kmers_destroy takes a half-built object)
 
@@ -215,6 +205,7 @@ static bfcg_kmers_t *kmers_new(int k, int l_pre, int cshift, int device)
 	bfcg_kmers_t *t = (bfcg_kmers_t *)calloc(1, sizeof(bfcg_kmers_t));
 	if (!t) { bfcg::fail("out of host memory"); return NULL; }
 	t->k = k; t->l_pre = l_pre; t->cshift = cshift; t->device = device;
+	t->q_cap = bfcg::lookup_cap();
 	BFCG_CKN(bfcg_kmers_destroy(t), hipStreamCreate(&t->st));
 	BFCG_CKN(bfcg_kmers_destroy(t), hipEventCreate(&t->e0)); BFCG_CKN(bfcg_kmers_destroy(t), hipEventCreate(&t->e1));
 	BFCG_CKN(bfcg_kmers_destroy(t), hipMalloc(&t->d_hist, HIST_BINS * 8));
@@ -256,6 +247,7 @@ extern "C" void bfcg_kmers_destroy(bfcg_kmers_t *t)
 	if (t->st) (void)hipStreamSynchronize(t->st);
 	if (t->owns_table) (void)hipFree((void *)t->table);
 	(void)hipFree(t->d_hist); (void)hipFree(t->d_sizes); (void)hipFree(t->d_cnt); (void)hipFree(t->d_off); (void)hipFree(t->d_y); (void)hipFree(t->d_ch);
+	(void)hipFree(t->d_qy); (void)hipFree(t->d_qout); (void)hipFree(t->d_pseq); (void)hipFree(t->d_pout);
 	if (t->e0) (void)hipEventDestroy(t->e0);
 	if (t->e1) (void)hipEventDestroy(t->e1);
 	if (t->st) (void)hipStreamDestroy(t->st);

@@ -360,7 +360,26 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *   bfcg_kmer_decode_host one slot of sub-table `sub` decoded on the host by the same code (bfcg_kdec.h), checked against the forward
  *                         hash; -1 for k > 37
  *   bfcg_kmer_2str        the planes as text (k + 1 bytes), kmer.h:97
- *   bfcg_kmers_format / _format_sizes   hash2cnt's lines "%s\t%d\t%d\n" (at most k + 8 bytes each) / "%d\n" (at most 11): bytes written */
+ *   bfcg_kmers_format / _format_sizes   hash2cnt's lines "%s\t%d\t%d\n" (at most k + 8 bytes each) / "%d\n" (at most 11): bytes written
+ * The other direction (bfcg_lookup.hip): the table asked by k-mer, on either form of the object, for every k up to 63 (a lookup needs the
+ * forward hash only).  A k-mer is given as a listing hands it out, y[2 i], y[2 i + 1], on either strand; bits at and above k are ignored.
+ *   bfcg_kmers_lookup     out[i] = bfc_ch_kmer_occ (htab.c:94) of k-mer i: high << 8 | count, -1 if the table does not hold it; *n_found
+ *                         (may be NULL) = the k-mers found.  y / out are host memory; n above the object's staging capacity (2^22 k-mers,
+ *                         or BFCG_LOOKUP_CAP in the environment when the object is made) is cut into pieces inside the call, and
+ *                         bfcg_kmers_last_ms then is the time of all its kernels.  For even k the reference's strand rule (kmer.h:81)
+ *                         does not always choose the same strand from both sides: a k-mer and its reverse complement may then differ
+ *   bfcg_kmers_profile    the stream is the batch format of PART 2, exactly one of h_seq / d_seq as in bfcg_kcov_batch; out[p] (host) for
+ *                         the k-mer ENDING at position p: its bfc_ch_kmer_occ value, -1 if absent, -2 where no k-mer ends (separators,
+ *                         the first k - 1 bases of a read, a window holding a byte that is not ACGTacgt)
+ * Their host twins and the text forms use no GPU:
+ *   bfcg_kmer_from_str    the inverse of bfcg_kmer_2str; -1 unless s has exactly k bytes of ACGTacgt
+ *   bfcg_kmer_occ_host    bfc_ch_kmer_occ on listing-style planes of either strand (the four planes of bfc_kmer_t built from the two)
+ *   bfcg_kmers_occ_host   the same for n k-mers
+ *   bfcg_kmers_parse      one k-mer per line (its first field, up to tab / space / CR), '>' lines and empty lines skipped: returns the
+ *                         k-mers written to y (at most cap); *bad_line = the 1-based number of the first malformed line, 0 if none
+ *   bfcg_lookup_format    the answers to the first n k-mer lines of the same text, "%s\t%d\t%d\n": the k-mer as given, count, high
+ *                         (0 0 for an absent one); at most the line's length + 8 bytes each
+ *   bfcg_profile_format   n positions of a profile as one line, space-separated counts, '.' for -2, 0 for -1 (at most 4 n + 1 bytes) */
 typedef struct bfcg_kmers bfcg_kmers_t;
 bfcg_kmers_t *bfcg_kmers_create(const bfc_ch_t *ch, int device);
 bfcg_kmers_t *bfcg_kmers_attach(bfcg_ctx_t *ctx);
@@ -375,6 +394,14 @@ int   bfcg_kmer_decode_host(int k, int l_pre, uint32_t sub, uint64_t slot, uint6
 void  bfcg_kmer_2str(int k, const uint64_t y[2], char *buf);
 uint64_t bfcg_kmers_format(int k, const uint64_t *y, const uint16_t *cnt_high, uint64_t n, char *buf);
 uint64_t bfcg_kmers_format_sizes(const uint32_t *sizes, uint64_t n, char *buf);
+int   bfcg_kmers_lookup(bfcg_kmers_t *t, const uint64_t *y, uint64_t n, int16_t *out, uint64_t *n_found);
+int   bfcg_kmers_profile(bfcg_kmers_t *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos, int16_t *out);
+int   bfcg_kmer_from_str(int k, const char *s, uint64_t y[2]);
+int   bfcg_kmer_occ_host(const bfc_ch_t *ch, const uint64_t y[2]);
+void  bfcg_kmers_occ_host(const bfc_ch_t *ch, const uint64_t *y, uint64_t n, int16_t *out);
+uint64_t bfcg_kmers_parse(int k, const char *text, uint64_t len, uint64_t *y, uint64_t cap, uint64_t *bad_line);
+uint64_t bfcg_lookup_format(const char *text, uint64_t len, const int16_t *occ, uint64_t n, char *buf);
+uint64_t bfcg_profile_format(const int16_t *occ, uint64_t n, char *buf);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);

@@ -2,7 +2,11 @@
 from the attached context, kernels only, against the path it replaces for the spectrum -- bfcg_export_table followed by the host's
 bfc_ch_hist.  Not the headline bench; numbers quoted in profiles/kmers_rate.md.
 
-    python scripts/kmers_rate.py [k] [bf_shift] [genome size] [coverage]
+    python scripts/kmers_rate.py [--lookup] [k] [bf_shift] [genome size] [coverage]
+
+--lookup measures the other direction instead (bfcg_lookup.hip): lookup() of every listed k-mer in shuffled order, and profile() over a
+prefix of the reads that built the table, each next to the host's loop over bfc_ch_kmer_occ on the same input (bfcg_kmers_occ_host,
+one thread) and to the chip's rate of independent 8-byte gathers from HBM (scripts/probes/gather_probe.hip).
 """
 import os
 import sys
@@ -14,6 +18,10 @@ import bfc_amd  # noqa: E402
 from bfc_amd import gen  # noqa: E402
 
 COPY_TBS = 6.3  # HBM rate a streaming kernel reaches on this chip (8 TB/s peak)
+GATHER_G = 48.8  # G random 8-byte gathers per second (profiles/round5_gather_probe.txt)
+LOOKUP = "--lookup" in sys.argv
+if LOOKUP:
+    sys.argv.remove("--lookup")
 arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
 k, b, G, cov = arg(1, 31), arg(2, 33), arg(3, 4_600_000), arg(4, 100)
 rs = gen.ReadSet(seed=2, G=G, cov=cov)
@@ -30,6 +38,71 @@ print("counted: k=%d -b%d, %d k-mers, %d distinct keys" % (k, b, st["n_kmers"], 
 km = bfc_amd.GpuKmers(g)
 slots = 1 << (km.l_pre + km.cshift)
 print("table: 2^%d sub-tables of 2^%d slots = %.1f MiB, %.1f %% full" % (km.l_pre, km.cshift, slots * 8 / 2**20, 100.0 * st["n_keys"] / slots))
+
+
+def lookup_rates():
+    y, c, h = km.list()
+    n = len(c)
+    perm = np.random.default_rng(1).permutation(n)
+    ys, want = np.ascontiguousarray(y[perm]), ((h.astype(np.int16) << 8) | c)[perm]
+    ms, wall = [], []
+    for rep in range(4):
+        t0 = time.perf_counter()
+        out = km.lookup(ys)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(km.last_ms())
+    assert np.array_equal(out, want) and km.n_found == n
+    best = min(ms)
+    print("lookup (all %d listed k-mers, shuffled; %d pieces), 4 runs, kernels only (ms): %s; wall with the copies: %s"
+          % (n, -(-n // (1 << 22)), " ".join("%.3f" % v for v in ms), " ".join("%.1f" % v for v in wall)))
+    print("lookup best: %.3f ms = %.2f G lookups/s = %.3f of the %.1f G gathers/s ceiling" % (best, n / best / 1e6, n / best / 1e6 / GATHER_G, GATHER_G))
+    # a prefix of the reads that built the table: whole reads, about 2^26 positions
+    n_pos = min(len(s_seq), (1 << 26) // stride * stride)
+    pms = []
+    for rep in range(4):
+        prof = km.profile(s_seq[:n_pos])
+        pms.append(km.last_ms())
+    n_k = int((prof != -2).sum())
+    best_p = min(pms)
+    print("profile (%d positions of the reads, %d k-mers, %d present), 4 runs, kernel only (ms): %s" % (n_pos, n_k, int((prof >= 0).sum()), " ".join("%.3f" % v for v in pms)))
+    print("profile best: %.3f ms = %.2f G positions/s, %.2f G probes/s = %.3f of the gather ceiling" % (best_p, n_pos / best_p / 1e6, n_k / best_p / 1e6, n_k / best_p / 1e6 / GATHER_G))
+    t = g.export_table()
+    t0 = time.perf_counter()
+    hout = t.occ_planes(ys)
+    dt = time.perf_counter() - t0
+    assert np.array_equal(hout, out)
+    print("host loop over bfc_ch_kmer_occ, the same shuffled k-mers, one thread: %.1f ms = %.4f G lookups/s (the GPU kernels: %.0fx)" % (dt * 1e3, n / dt / 1e9, dt * 1e3 / best))
+    # the profile's input on the host: the planes of the k-mer ending at every position of the first 2^22 (numpy, not timed), then the same loop
+    m = min(n_pos, (1 << 22) // stride * stride)
+    st = s_seq[:m]
+    code = np.full(256, 4, dtype=np.uint8)
+    for i, ch in enumerate(b"ACGT"):
+        code[ch] = code[ch | 0x20] = i
+    cd = code[st]
+    ok = cd < 4
+    idx = np.arange(m)
+    run = idx - np.maximum.accumulate(np.where(ok, -1, idx))
+    ends = run >= k
+    cc = np.where(ok, cd, 0).astype(np.uint64)
+    yy = np.zeros((m, 2), dtype=np.uint64)
+    for l in range(k):
+        yy[l:, 0] |= (cc[:m - l] & np.uint64(1)) << np.uint64(l)
+        yy[l:, 1] |= (cc[:m - l] >> np.uint64(1)) << np.uint64(l)
+    yq = np.ascontiguousarray(yy[ends])
+    t0 = time.perf_counter()
+    hp = t.occ_planes(yq)
+    dt = time.perf_counter() - t0
+    assert np.array_equal(hp, prof[:m][ends]) and (prof[:m][~ends] == -2).all()
+    print("host loop over bfc_ch_kmer_occ, the k-mers of the first %d positions in read order (%d): %.1f ms = %.4f G lookups/s (k_profile per k-mer: %.0fx)"
+          % (m, len(yq), dt * 1e3, len(yq) / dt / 1e9, (dt / len(yq)) / (best_p * 1e-3 / n_k)))
+    t.close()
+
+
+if LOOKUP:
+    lookup_rates()
+    km.close()
+    g.close()
+    sys.exit(0)
 
 
 def rate(ms, passes):
