@@ -165,6 +165,9 @@ SYMBOLS = {
     "bfcg_kmers_parse": (C.c_uint64, [C.c_int, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_lookup_format": (C.c_uint64, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "bfcg_profile_format": (C.c_uint64, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_kmers_read_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "bfcg_read_stats_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
+    "bfcg_read_stats_format": (C.c_uint64, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "bfcg_hash_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_seen_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
 }

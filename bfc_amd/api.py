@@ -70,6 +70,23 @@ def to_stream(seq, off):
     return out
 
 
+def _read_stats_args(seq_stream, off):
+    """(stream or None, offsets u64, the result's array) of a read_stats() call"""
+    s = np.ascontiguousarray(seq_stream, dtype=np.uint8) if seq_stream is not None else None
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    if off.ndim != 1 or len(off) < 1:
+        raise BfcGpuError("read_stats needs off[n_reads + 1], the reads' stream offsets")
+    return s, off, np.zeros((len(off) - 1, 8), dtype=np.int32)
+
+
+def format_read_stats(out):
+    """bfcg_read_stats_format's lines for an (n, 8) result, formatted in C: bytes."""
+    out = np.ascontiguousarray(out, dtype=np.int32).reshape(-1, 8)
+    buf = C.create_string_buffer(max(1, 110 * len(out)))
+    n = _lib.load().bfcg_read_stats_format(out.ctypes.data, len(out), buf)
+    return buf.raw[:n]
+
+
 class HostTable:
     """A host-resident ``bfc_ch_t`` (opaque, htab.h:10-23)."""
 
@@ -113,6 +130,14 @@ class HostTable:
         y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 2)
         out = np.empty(len(y), dtype=np.int16)
         self.L.bfcg_kmers_occ_host(self.ptr, y.ctypes.data, len(y), out.ctypes.data)
+        return out
+
+    def read_stats(self, seq_stream, off, min_cov=3):
+        """Per-read statistics of a batch stream against this table, int32 (n_reads, 8) as GpuKmers.read_stats gives them: its host
+        twin (bfcg_read_stats_host)."""
+        s, off, out = _read_stats_args(seq_stream, off)
+        if self.L.bfcg_read_stats_host(self.ptr, s.ctypes.data, len(s), off.ctypes.data, len(off) - 1, int(min_cov), out.ctypes.data) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
         return out
 
     def insert(self, y0, y1, is_high, forced=1):
@@ -706,8 +731,21 @@ class GpuKmers:
         self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
         return out
 
+    def read_stats(self, seq_stream, off, min_cov=3, d_seq=None):
+        """A read set screened against the table: the stream (host array, or d_seq on the device) and off[n_reads + 1], the reads'
+        stream offsets as GpuTrimmer.trim takes them -> int32 (n_reads, 8): n_kmers, n_present, n_solid (count >= min_cov), the sum
+        of the counts, min | median << 8 | max << 16, and the longest run of solid k-mers: its length, and the bases [start, end) it
+        covers (-1, -1 if there is none).  The profile is reduced on the device: 32 bytes per read come back."""
+        s, off, out = _read_stats_args(seq_stream, off)
+        if self.L.bfcg_kmers_read_stats(self.t, s.ctypes.data if s is not None else None, None if s is not None else d_seq, int(off[-1]) if s is None else len(s),
+                                        off.ctypes.data, len(off) - 1, int(min_cov), out.ctypes.data) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return out
+
     def last_ms(self):
-        """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces."""
+        """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces,
+        read_stats() its two kernels."""
         return self._ms
 
 

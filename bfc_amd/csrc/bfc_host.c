@@ -660,3 +660,106 @@ uint64_t bfcg_profile_format(const int16_t *occ, uint64_t n, char *buf)
 	*p++ = '\n';
 	return (uint64_t)(p - buf);
 }
+
+/* ---- per-read statistics of a count profile (include/bfc_gpu.h: the twin of bfcg_kmers_read_stats, the check both share, the text form) ---- */
+void bfcg_set_error(const char *msg) __attribute__((weak)); /* the library's error channel (bfcg_ctx.hip); this file also links without it */
+static int refuse(const char *fmt, unsigned long long a, unsigned long long b, unsigned long long c)
+{
+	char msg[256];
+	snprintf(msg, sizeof(msg), fmt, a, b, c);
+	if (bfcg_set_error) bfcg_set_error(msg);
+	else fprintf(stderr, "[E::bfcg] %s\n", msg);
+	return -1;
+}
+int bfcg_read_stats_check(uint64_t n_pos, const uint64_t *off, uint64_t n_reads, int min_cov)
+{
+	uint64_t r;
+	if (min_cov < 1 || min_cov > 255) return refuse("min_cov %lld is outside [1, 255]: a count is 8 bits, and 0 would call absent k-mers solid", (unsigned long long)(long long)min_cov, 0, 0);
+	if (n_reads == 0 || n_pos == 0) return 0;
+	if (!off) return refuse("per-read statistics need the reads' offsets", 0, 0, 0);
+	if (n_reads >> 32) return refuse("%llu reads are too many for one call: walk them in pieces", n_reads, 0, 0);
+	for (r = 0; r < n_reads; ++r) {
+		if (off[r + 1] <= off[r]) return refuse("read %llu: its offsets [%llu, %llu) do not ascend (a read's span holds at least its separator)", r, off[r], off[r + 1]);
+		if (off[r + 1] - off[r] - 1 >= 1ULL << 24) return refuse("read %llu has %llu positions: one read is held to fewer than 2^24 (its sum of counts is a 32-bit word)", r, off[r + 1] - off[r] - 1, 0);
+	}
+	if (off[n_reads] != n_pos) return refuse("read %llu, the last, ends at offset %llu, but the stream has %llu positions", n_reads - 1, off[n_reads], n_pos);
+	return 0;
+}
+
+/* the eight words of one read from its profile v[0, len): bfc_gpu.h says what they are */
+static void read_stats_1(const int16_t *v, int len, int k, int min_cov, int32_t o[8])
+{
+	uint32_t hist[256], n_def = 0, n_present = 0, n_solid = 0, sum = 0, cum;
+	uint64_t t = 0, mx = 0; /* max_streak's pair (correct.c:483-495): run length << 32 | the run's first position; of equal runs the later is larger */
+	int p, b;
+	memset(hist, 0, sizeof(hist));
+	for (p = 0; p < len; ++p) {
+		const int c = v[p] >= 0 ? v[p] & 0xff : 0;
+		if (v[p] != -2) { ++n_def; ++hist[c]; sum += (uint32_t)c; }
+		n_present += v[p] >= 0;
+		if (v[p] >= 0 && c >= min_cov) { ++n_solid; t += 1ULL << 32; if (t > mx) mx = t; }
+		else t = (uint64_t)(p + 1);
+	}
+	o[0] = (int32_t)n_def; o[1] = (int32_t)n_present; o[2] = (int32_t)n_solid; o[3] = (int32_t)sum; o[4] = 0;
+	if (n_def) {
+		int lo = 0, hi = 255, med = 0;
+		while (!hist[lo]) ++lo;
+		while (!hist[hi]) --hi;
+		for (b = 0, cum = 0; b < 256; ++b) { cum += hist[b]; if ((n_def - 1) >> 1 < cum) { med = b; break; } }
+		o[4] = lo | med << 8 | hi << 16;
+	}
+	o[5] = (int32_t)(mx >> 32);
+	o[6] = o[5] ? (int32_t)(uint32_t)mx - (k - 1) : -1;
+	o[7] = o[5] ? o[6] + o[5] + k - 1 : -1;
+}
+
+int bfcg_read_stats_host(const bfc_ch_t *ch, const uint8_t *seq, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, int min_cov, int32_t *out)
+{
+	uint64_t r, max_len = 0;
+	int16_t *v;
+	if (!ch) return refuse("bad arguments to bfcg_read_stats_host", 0, 0, 0);
+	if (bfcg_read_stats_check(n_pos, off, n_reads, min_cov) != 0) return -1;
+	if (n_reads == 0 || n_pos == 0) return 0;
+	if (!seq || !out) return refuse("bad arguments to bfcg_read_stats_host (the stream and a result buffer)", 0, 0, 0);
+	for (r = 0; r < n_reads; ++r) if (off[r + 1] - off[r] - 1 > max_len) max_len = off[r + 1] - off[r] - 1;
+	v = (int16_t*)malloc((max_len + 1) * sizeof(int16_t));
+	if (!v) return refuse("out of host memory", 0, 0, 0);
+	for (r = 0; r < n_reads; ++r) {
+		const int k = ch->k, len = (int)(off[r + 1] - off[r] - 1);
+		const uint64_t m = (1ULL << k) - 1;
+		const uint8_t *s = seq + off[r];
+		bfc_kmer_t z = {{0, 0, 0, 0}}; /* kmer.h:13-16: the read's strand with its newest base at bit 0, the other one complemented with the oldest base there */
+		int p, n = 0;
+		for (p = 0; p < len; ++p) {
+			const int c = base_code((char)s[p]);
+			v[p] = -2;
+			if (c < 0) { n = 0; continue; }
+			z.x[0] = (z.x[0] << 1 | (uint64_t)(c & 1)) & m; z.x[1] = (z.x[1] << 1 | (uint64_t)(c >> 1)) & m;
+			z.x[2] = z.x[2] >> 1 | (uint64_t)(1 ^ (c & 1)) << (k - 1); z.x[3] = z.x[3] >> 1 | (uint64_t)(1 ^ (c >> 1)) << (k - 1);
+			if (++n >= k) v[p] = (int16_t)bfc_ch_kmer_occ(ch, &z);
+		}
+		read_stats_1(v, len, k, min_cov, out + 8 * r);
+	}
+	free(v);
+	return 0;
+}
+
+static inline char *put_int(char *p, int32_t v)
+{
+	if (v < 0) { *p++ = '-'; return put_dec(p, (uint32_t)0 - (uint32_t)v); }
+	return put_dec(p, (uint32_t)v);
+}
+/* one line per read, "%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n": n_kmers n_present n_solid sum min median max streak start end (at most 110 bytes) */
+uint64_t bfcg_read_stats_format(const int32_t *out, uint64_t n_reads, char *buf)
+{
+	uint64_t r;
+	char *p = buf;
+	for (r = 0; r < n_reads; ++r) {
+		const int32_t *o = out + 8 * r;
+		int i;
+		for (i = 0; i < 4; ++i) { p = put_int(p, o[i]); *p++ = '\t'; }
+		for (i = 0; i < 3; ++i) { p = put_dec(p, (uint32_t)o[4] >> (8 * i) & 0xff); *p++ = '\t'; }
+		for (i = 5; i < 8; ++i) { p = put_int(p, o[i]); *p++ = i < 7 ? '\t' : '\n'; }
+	}
+	return (uint64_t)(p - buf);
+}

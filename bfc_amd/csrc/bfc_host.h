@@ -13,6 +13,9 @@ void bfc_ch_raw_set_count(bfc_ch_t *ch, uint64_t n_keys);
 int bfc_ch_raw_cshift(const bfc_ch_t *ch); /* log2 of a sub-table's slot count */
 /* attach order stamps (first[slots], sub_last[2^l_pre]); returns their buffers to fill */
 int bfc_ch_raw_order(bfc_ch_t *ch, uint64_t **first, uint64_t **sub_last);
+/* what bfcg_kmers_read_stats and bfcg_read_stats_host refuse, with the message set: min_cov outside [1, 255], offsets that do not ascend or do
+ * not end at n_pos, a read of 2^24 or more positions.  0 if the call may go ahead (also for n_reads == 0 or n_pos == 0: nothing to check) */
+int bfcg_read_stats_check(uint64_t n_pos, const uint64_t *off, uint64_t n_reads, int min_cov);
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip):
+// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip):
 // kernel parameters and launchers, the one error channel, the resident registry, what the satellites borrow from a context
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,7 +25,8 @@ static constexpr int bfcg_tile1_of_rw(int rw) { return rw == 3 ? 4096 : 3072; }
 #include <stdint.h>
 struct bfcg_ctx; struct bfcg_kcov; /* include/bfc_gpu.h: bfcg_ctx_t, bfcg_kcov_t */
 
-/* the table read-out's object (include/bfc_gpu.h: bfcg_kmers_t): made and destroyed in bfcg_kmers.hip, which lists the table; bfcg_lookup.hip probes it */
+/* the table read-out's object (include/bfc_gpu.h: bfcg_kmers_t): made and destroyed in bfcg_kmers.hip, which lists the table; bfcg_lookup.hip probes it,
+   bfcg_readstats.hip reduces a profile per read */
 struct bfcg_kmers {
 	int k, l_pre, cshift, device, owns_table;
 	hipStream_t st;
@@ -37,6 +38,7 @@ struct bfcg_kmers {
 	ulonglong2 *d_y; uint16_t *d_ch; uint64_t out_cap;              // a listing's device result (grown on demand)
 	ulonglong2 *d_qy; int16_t *d_qout; uint64_t q_cap;              // a lookup's staging, q_cap k-mers a piece (BFCG_LOOKUP_CAP at creation), allocated by the first lookup
 	uint8_t *d_pseq; uint64_t pseq_cap; int16_t *d_pout; uint64_t pout_cap; // a profile's stream and result (grown on demand)
+	unsigned long long *d_roff; uint64_t roff_cap; int32_t *d_rout; uint64_t rout_cap; // the reads' offsets and eight words per read of bfcg_kmers_read_stats (bfcg_readstats.hip; grown on demand)
 	float last_ms;
 };
 
@@ -165,5 +167,18 @@ const unsigned long long *kcov_table(::bfcg_kcov *t, KParams *P, int *device);
 int kcov_adopted(::bfcg_kcov *t);
 // k-mers a lookup stages per piece (bfcg_lookup.hip): a few million, or what BFCG_LOOKUP_CAP says
 BFCG_LOCAL uint64_t lookup_cap();
+// a profile's first half (bfcg_lookup.hip): the stream staged in d_pseq if it is the host's, d_pout grown, t->e0 recorded and k_profile launched
+// into d_pout on t->st.  The caller records t->e1 behind the last kernel of its call and checks hipGetLastError.
+BFCG_LOCAL int profile_launch(::bfcg_kmers *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos);
+// a buffer of an object grown to `need` bytes (`what` names it in the message); on failure it is gone and its capacity 0
+template <typename T> int grow(T *&buf, uint64_t &cap, uint64_t need, const char *what)
+{
+	if (need <= cap) return 0;
+	(void)hipFree(buf); buf = NULL; cap = 0;
+	hipError_t e = hipMalloc(&buf, need);
+	if (e != hipSuccess) { buf = NULL; (void)hipGetLastError(); return fail("no room for %s of %llu bytes: %s", what, (unsigned long long)need, hipGetErrorString(e)); }
+	cap = need;
+	return 0;
+}
 
 } // namespace bfcg

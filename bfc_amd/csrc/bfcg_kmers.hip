@@ -247,7 +247,7 @@ extern "C" void bfcg_kmers_destroy(bfcg_kmers_t *t)
 	if (t->st) (void)hipStreamSynchronize(t->st);
 	if (t->owns_table) (void)hipFree((void *)t->table);
 	(void)hipFree(t->d_hist); (void)hipFree(t->d_sizes); (void)hipFree(t->d_cnt); (void)hipFree(t->d_off); (void)hipFree(t->d_y); (void)hipFree(t->d_ch);
-	(void)hipFree(t->d_qy); (void)hipFree(t->d_qout); (void)hipFree(t->d_pseq); (void)hipFree(t->d_pout);
+	(void)hipFree(t->d_qy); (void)hipFree(t->d_qout); (void)hipFree(t->d_pseq); (void)hipFree(t->d_pout); (void)hipFree(t->d_roff); (void)hipFree(t->d_rout);
 	if (t->e0) (void)hipEventDestroy(t->e0);
 	if (t->e1) (void)hipEventDestroy(t->e1);
 	if (t->st) (void)hipStreamDestroy(t->st);

@@ -68,17 +68,6 @@ int lookup_stage(bfcg_kmers_t *t)
 	return 0;
 }
 
-// a buffer of the object grown to `need` bytes; on failure it is gone and its capacity 0
-template <typename T> int grow(T *&buf, uint64_t &cap, uint64_t need)
-{
-	if (need <= cap) return 0;
-	(void)hipFree(buf); buf = NULL; cap = 0;
-	hipError_t e = hipMalloc(&buf, need);
-	if (e != hipSuccess) { buf = NULL; (void)hipGetLastError(); return bfcg::fail("no room for a profile of %llu bytes: %s", (unsigned long long)need, hipGetErrorString(e)); }
-	cap = need;
-	return 0;
-}
-
 } // namespace
 
 uint64_t bfcg::lookup_cap()
@@ -123,16 +112,13 @@ extern "C" int bfcg_kmers_lookup(bfcg_kmers_t *t, const uint64_t *y, uint64_t n,
 	return 0;
 }
 
-// the stream is the batch format of PART 2, on the host or on the device; out[p] (host) describes the k-mer ending at position p
-extern "C" int bfcg_kmers_profile(bfcg_kmers_t *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos, int16_t *out)
+// the first half of a profile, shared with bfcg_kmers_read_stats (bfcg_readstats.hip): everything up to and including k_profile's launch
+int bfcg::profile_launch(bfcg_kmers_t *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos)
 {
-	if (!t || !h_seq == !d_seq || (n_pos && !out)) return bfcg::fail("bad arguments to bfcg_kmers_profile (exactly one of h_seq / d_seq, and a result buffer)");
-	t->last_ms = 0;
-	if (n_pos == 0) return 0;
 	if (n_pos >= 1ULL << 40) return bfcg::fail("a stream of %llu positions is too long for one profile: walk it in pieces that overlap by k - 1", (unsigned long long)n_pos);
 	BFCG_CK(hipSetDevice(t->device));
-	if (h_seq && grow(t->d_pseq, t->pseq_cap, n_pos) != 0) return -1;
-	if (grow(t->d_pout, t->pout_cap, n_pos * 2) != 0) return -1;
+	if (h_seq && bfcg::grow(t->d_pseq, t->pseq_cap, n_pos, "a profile") != 0) return -1;
+	if (bfcg::grow(t->d_pout, t->pout_cap, n_pos * 2, "a profile") != 0) return -1;
 	if (h_seq) { BFCG_CK(hipMemcpyAsync(t->d_pseq, h_seq, n_pos, hipMemcpyHostToDevice, t->st)); d_seq = t->d_pseq; }
 	bfcg::KParams P = {};
 	P.k = t->k; P.l_pre = t->l_pre; P.tab_cshift = t->cshift;
@@ -141,6 +127,16 @@ extern "C" int bfcg_kmers_profile(bfcg_kmers_t *t, const uint8_t *h_seq, const u
 	BFCG_CK(hipEventRecord(t->e0, t->st));
 	if (t->k <= 32) hipLaunchKernelGGL((k_profile<uint32_t, BFCG_TILE1, BFCG_BT1>), dim3(g), dim3(BFCG_BT1), 0, t->st, P, d_seq, (int64_t)n_pos, t->table, t->d_pout);
 	else hipLaunchKernelGGL((k_profile<uint64_t, BFCG_TILE1, BFCG_BT1>), dim3(g), dim3(BFCG_BT1), 0, t->st, P, d_seq, (int64_t)n_pos, t->table, t->d_pout);
+	return 0;
+}
+
+// the stream is the batch format of PART 2, on the host or on the device; out[p] (host) describes the k-mer ending at position p
+extern "C" int bfcg_kmers_profile(bfcg_kmers_t *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos, int16_t *out)
+{
+	if (!t || !h_seq == !d_seq || (n_pos && !out)) return bfcg::fail("bad arguments to bfcg_kmers_profile (exactly one of h_seq / d_seq, and a result buffer)");
+	t->last_ms = 0;
+	if (n_pos == 0) return 0;
+	if (bfcg::profile_launch(t, h_seq, d_seq, n_pos) != 0) return -1;
 	BFCG_CK(hipEventRecord(t->e1, t->st));
 	BFCG_CK(hipGetLastError());
 	BFCG_CK(hipMemcpyAsync(out, t->d_pout, n_pos * 2, hipMemcpyDeviceToHost, t->st));

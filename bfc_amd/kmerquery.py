@@ -16,6 +16,8 @@ import sys
 
 import numpy as np
 
+from ._fastx import records
+
 USAGE = """Usage: kmerquery [options] <dump.hash> [queries|-]
 Options:
   -p       queries are FASTA/FASTQ: print the count under every base of each record
@@ -42,26 +44,6 @@ def _lookup_lines(km, f, out):
         line0 += len(lines)
 
 
-def _records(f):
-    """(name, sequence) of every FASTA / FASTQ record (kseq's grammar: multi-line sequences, '+' starts as many quality bytes)"""
-    name, seq, n_qual = None, [], -1   # n_qual >= 0: inside a quality string, bytes still missing
-    for line in f:
-        line = line.rstrip(b"\r\n")
-        if n_qual > 0:
-            n_qual -= len(line)
-            continue
-        if line[:1] in (b">", b"@"):
-            if name is not None:
-                yield name, b"".join(seq)
-            name, seq, n_qual = (line[1:].split() or [b""])[0], [], -1
-        elif line[:1] == b"+" and name is not None and n_qual < 0:
-            n_qual = sum(len(s) for s in seq)
-        elif name is not None and n_qual < 0:
-            seq.append(line)
-    if name is not None:
-        yield name, b"".join(seq)
-
-
 def _profile_piece(km, recs, out):
     if not recs:
         return
@@ -78,9 +60,9 @@ def _profile_piece(km, recs, out):
 
 def _profile_records(km, f, out):
     recs, n = [], 0
-    for rec in _records(f):
-        recs.append(rec)
-        n += len(rec[1]) + 1
+    for name, seq, _ in records(f):
+        recs.append((name, seq))
+        n += len(seq) + 1
         if n >= PIECE:
             _profile_piece(km, recs, out)
             recs, n = [], 0

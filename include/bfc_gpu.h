@@ -371,6 +371,26 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *   bfcg_kmers_profile    the stream is the batch format of PART 2, exactly one of h_seq / d_seq as in bfcg_kcov_batch; out[p] (host) for
  *                         the k-mer ENDING at position p: its bfc_ch_kmer_occ value, -1 if absent, -2 where no k-mer ends (separators,
  *                         the first k - 1 bases of a read, a window holding a byte that is not ACGTacgt)
+ * A read set screened against the table (bfcg_readstats.hip): the profile reduced per read on the device, 32 bytes per read of output
+ * instead of 2 bytes per base.
+ *   bfcg_kmers_read_stats the stream and off[n_reads + 1] as bfcg_trim_batch / bfcg_ec_batch take them (exactly one of h_seq / d_seq;
+ *                         read r is positions [off[r], off[r + 1] - 1), the last byte of its span the separator; off[n_reads] = n_pos);
+ *                         out (host) gets eight int32 per read.  With v the profile's value at a position and c = v & 0xff if v >= 0,
+ *                         else 0, a position is DEFINED if v != -2 and SOLID if v >= 0 and c >= min_cov:
+ *                           0 n_kmers    defined positions          1 n_present  positions with v >= 0       2 n_solid
+ *                           3 the sum of c over the defined positions (a 32-bit word: int32_t holds its bits)
+ *                           4 min | median << 8 | max << 16 of c over the defined positions, the median the element (n_kmers - 1) >> 1
+ *                             of the sorted values (the lower median); 0 if n_kmers = 0
+ *                           5 streak     the k-mers of the longest run of consecutive solid positions (anything else ends a run), of
+ *                                        equally long runs the LAST, as max_streak keeps it (correct.c:494)
+ *                           6 start, 7 end   that run's bases [start, end) counted from the read's first: its first k-mer ends at
+ *                                        position start + k - 1, end = start + streak + k - 1; both -1 if streak = 0
+ *                         This is `bfc -1`'s question (correct.c:478-497) asked of the exact table with a coverage threshold.  Refused
+ *                         before anything is launched, out untouched, the message naming the read: min_cov outside [1, 255], offsets
+ *                         that do not ascend, off[n_reads] != n_pos, a read of 2^24 or more positions (word 3 stays inside 32 bits).
+ *                         n_reads = 0 or n_pos = 0: 0, nothing written.  On either form of the object, for every k up to 63;
+ *                         bfcg_kmers_last_ms covers both kernels.  One wavefront walks one read: made for reads of 50 to 300 bases; a
+ *                         megabase contig comes out right, at the pace of one wave.
  * Their host twins and the text forms use no GPU:
  *   bfcg_kmer_from_str    the inverse of bfcg_kmer_2str; -1 unless s has exactly k bytes of ACGTacgt
  *   bfcg_kmer_occ_host    bfc_ch_kmer_occ on listing-style planes of either strand (the four planes of bfc_kmer_t built from the two)
@@ -379,7 +399,11 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *                         k-mers written to y (at most cap); *bad_line = the 1-based number of the first malformed line, 0 if none
  *   bfcg_lookup_format    the answers to the first n k-mer lines of the same text, "%s\t%d\t%d\n": the k-mer as given, count, high
  *                         (0 0 for an absent one); at most the line's length + 8 bytes each
- *   bfcg_profile_format   n positions of a profile as one line, space-separated counts, '.' for -2, 0 for -1 (at most 4 n + 1 bytes) */
+ *   bfcg_profile_format   n positions of a profile as one line, space-separated counts, '.' for -2, 0 for -1 (at most 4 n + 1 bytes)
+ *   bfcg_read_stats_host  bfcg_kmers_read_stats's eight words per read from bfc_ch_kmer_occ on the k-mers rolled from the stream's bytes;
+ *                         the same refusals
+ *   bfcg_read_stats_format one line per read, "%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n": n_kmers n_present n_solid sum min median max
+ *                         streak start end (at most 110 bytes each) */
 typedef struct bfcg_kmers bfcg_kmers_t;
 bfcg_kmers_t *bfcg_kmers_create(const bfc_ch_t *ch, int device);
 bfcg_kmers_t *bfcg_kmers_attach(bfcg_ctx_t *ctx);
@@ -402,6 +426,10 @@ void  bfcg_kmers_occ_host(const bfc_ch_t *ch, const uint64_t *y, uint64_t n, int
 uint64_t bfcg_kmers_parse(int k, const char *text, uint64_t len, uint64_t *y, uint64_t cap, uint64_t *bad_line);
 uint64_t bfcg_lookup_format(const char *text, uint64_t len, const int16_t *occ, uint64_t n, char *buf);
 uint64_t bfcg_profile_format(const int16_t *occ, uint64_t n, char *buf);
+int   bfcg_kmers_read_stats(bfcg_kmers_t *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos, const uint64_t *h_off, uint64_t n_reads,
+                            int min_cov, int32_t *out);
+int   bfcg_read_stats_host(const bfc_ch_t *ch, const uint8_t *seq, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, int min_cov, int32_t *out);
+uint64_t bfcg_read_stats_format(const int32_t *out, uint64_t n_reads, char *buf);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);

@@ -2,11 +2,13 @@
 from the attached context, kernels only, against the path it replaces for the spectrum -- bfcg_export_table followed by the host's
 bfc_ch_hist.  Not the headline bench; numbers quoted in profiles/kmers_rate.md.
 
-    python scripts/kmers_rate.py [--lookup] [k] [bf_shift] [genome size] [coverage]
+    python scripts/kmers_rate.py [--lookup | --readstats] [k] [bf_shift] [genome size] [coverage]
 
 --lookup measures the other direction instead (bfcg_lookup.hip): lookup() of every listed k-mer in shuffled order, and profile() over a
 prefix of the reads that built the table, each next to the host's loop over bfc_ch_kmer_occ on the same input (bfcg_kmers_occ_host,
 one thread) and to the chip's rate of independent 8-byte gathers from HBM (scripts/probes/gather_probe.hip).
+--readstats measures read_stats() (bfcg_readstats.hip) over a prefix of the reads of about 2^25 positions: its two kernels, the call's
+wall time with its D2H, and next to them the way to the same numbers without it -- profile() and a numpy reduction per read.
 """
 import os
 import sys
@@ -22,6 +24,9 @@ GATHER_G = 48.8  # G random 8-byte gathers per second (profiles/round5_gather_pr
 LOOKUP = "--lookup" in sys.argv
 if LOOKUP:
     sys.argv.remove("--lookup")
+READSTATS = "--readstats" in sys.argv
+if READSTATS:
+    sys.argv.remove("--readstats")
 arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
 k, b, G, cov = arg(1, 31), arg(2, 33), arg(3, 4_600_000), arg(4, 100)
 rs = gen.ReadSet(seed=2, G=G, cov=cov)
@@ -97,6 +102,64 @@ def lookup_rates():
           % (m, len(yq), dt * 1e3, len(yq) / dt / 1e9, (dt / len(yq)) / (best_p * 1e-3 / n_k)))
     t.close()
 
+
+def reduce_numpy(prof, n, min_cov):
+    """the eight words per read from a profile of n reads of equal length, in numpy"""
+    v = prof.reshape(n, stride)[:, :rs.L].astype(np.int32)
+    defined, present = v != -2, v >= 0
+    c = np.where(present, v & 0xff, 0)
+    solid = present & (c >= min_cov)
+    out = np.zeros((n, 8), dtype=np.int32)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3] = defined.sum(1), present.sum(1), solid.sum(1), c.sum(1)
+    srt = np.sort(np.where(defined, c, 256), axis=1)
+    nd = out[:, 0]
+    pick = lambda i: np.take_along_axis(srt, np.maximum(i, 0)[:, None], 1)[:, 0]  # noqa: E731
+    out[:, 4] = np.where(nd > 0, pick(np.zeros_like(nd)) | pick((nd - 1) >> 1) << 8 | pick(nd - 1) << 16, 0)
+    idx = np.arange(rs.L)[None, :]
+    run = idx - np.maximum.accumulate(np.where(solid, -1, idx), axis=1)   # the solid run ending at every position
+    best = run.max(1)
+    last = rs.L - 1 - np.argmax(run[:, ::-1], axis=1)                       # of equally long runs the last
+    start = last - best + 1 - (k - 1)
+    out[:, 5], out[:, 6], out[:, 7] = best, np.where(best > 0, start, -1), np.where(best > 0, start + best + k - 1, -1)
+    return out
+
+
+def readstats_rates(min_cov=3):
+    n = min(rs.n_reads, (1 << 25) // stride)
+    stream, roff = s_seq[:n * stride], np.arange(n + 1, dtype=np.uint64) * np.uint64(stride)
+    ms, wall, pms, pwall, hwall = [], [], [], [], []
+    for rep in range(4):
+        t0 = time.perf_counter()
+        got = km.read_stats(stream, roff, min_cov)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(km.last_ms())
+    for rep in range(4):
+        t0 = time.perf_counter()
+        prof = km.profile(stream)
+        t1 = time.perf_counter()
+        want = reduce_numpy(prof, n, min_cov)
+        t2 = time.perf_counter()
+        pms.append(km.last_ms()); pwall.append((t1 - t0) * 1e3); hwall.append((t2 - t1) * 1e3)
+    assert np.array_equal(got, want), np.flatnonzero((got != want).any(axis=1))[:10]
+    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
+    print("build %s" % bfc_amd._lib.build_id())
+    print("read_stats: %d reads of %d bases, %d positions, min_cov %d; %d k-mers, %d present, %d solid; %d reads solid throughout"
+          % (n, rs.L, len(stream), min_cov, got[:, 0].sum(), got[:, 1].sum(), got[:, 2].sum(), int((got[:, 5] == got[:, 0]).sum())))
+    print("read_stats, k_profile + k_read_stats, 4 runs (ms): %s; wall with the H2D and the %.1f MB D2H (ms): %s" % (f(ms), n * 32 / 1e6, f(wall)))
+    print("profile, k_profile alone, 4 runs (ms): %s; wall with the H2D and the %.1f MB D2H (ms): %s" % (f(pms), len(stream) * 2 / 1e6, f(pwall)))
+    print("numpy reduction of the profile per read, 4 runs (ms): %s" % f(hwall))
+    kp, both = min(pms), min(ms)
+    print("best: k_profile %.3f ms, both kernels %.3f ms: k_read_stats %.3f ms = %.2f of k_profile, %.1f G positions/s, %.2f TB/s of profile read"
+          % (kp, both, both - kp, (both - kp) / kp, len(stream) / (both - kp) / 1e6, len(stream) * 2 / (both - kp) / 1e9))
+    print("best wall: read_stats %.1f ms; profile %.1f ms + numpy %.1f ms = %.1f ms (%.1fx)"
+          % (min(wall), min(pwall), min(hwall), min(pwall) + min(hwall), (min(pwall) + min(hwall)) / min(wall)))
+
+
+if READSTATS:
+    readstats_rates()
+    km.close()
+    g.close()
+    sys.exit(0)
 
 if LOOKUP:
     lookup_rates()
