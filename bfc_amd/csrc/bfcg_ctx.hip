@@ -11,7 +11,6 @@
 #include <time.h>
 #include <vector>
 #include <thread>
-#include <vector>
 #include "bfc_gpu.h"
 #include "bfcg_internal.h"
 #include "bfc_host.h"
@@ -469,10 +468,17 @@ extern "C" void bfcg_destroy(bfcg_ctx_t *c)
 	free(c);
 }
 
+// fine buckets (bloom regions) this rank owns
+static inline uint64_t nfine(const bfcg_ctx_t *c) { return ((uint64_t)1 << c->P.F) >> c->log2n; }
+static int batch_fits(const bfcg_ctx_t *c, uint64_t n_pos)
+{
+	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
+	return 0;
+}
+
 static int drain(bfcg_ctx_t *c);
 static int replay_poisoned(bfcg_ctx_t *c);
 static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, uint32_t slab_cap, hipEvent_t *wait, int n_wait);
-extern "C" int bfcg_mg_process_ev(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, hipEvent_t *wait, int n_wait);
 static int enqueue_batch(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, int wait_copy, int no_kstats);
 static int ensure_agg(bfcg_ctx_t *c);
 static int same_block_offset(bfcg_ctx_t *c, int b, const uint8_t *d_seq, const uint8_t **d_qual, uint64_t n_pos, hipStream_t s);
@@ -508,29 +514,29 @@ extern "C" int bfcg_reset(bfcg_ctx_t *c)
 	BFCG_CK(hipMemsetAsync(c->B.bloom, 0, c->bloom_bytes, c->st));
 	if (c->B.bloom_hi) BFCG_CK(hipMemsetAsync(c->B.bloom_hi, 0, c->bloom_bytes, c->st));
 	if (c->seg_ok) { // back to region-owned segments of the initial size (a run that outgrew them, or an export, left the other layout behind)
-		const uint64_t nfine = ((uint64_t)1 << c->P.F) >> c->log2n;
+		const uint64_t nf = nfine(c);
 		if (c->seg_escaped || !c->B.seg_tab) {
 			BFCG_CK(hipStreamSynchronize(c->st));
 			if (c->B.table) { BFCG_CK(hipFree(c->B.table)); c->B.table = 0; }
 			if (c->B.seg_tab) { BFCG_CK(hipFree(c->B.seg_tab)); c->B.seg_tab = 0; }
 			set_seg_shift(c->P, c->seg_init_shift, c->seg_blk_max); c->seg_cap_shift = c->seg_init_shift;
-			BFCG_CK(hipMalloc(&c->B.seg_tab, (nfine << c->P.seg_shift) * 8));
+			BFCG_CK(hipMalloc(&c->B.seg_tab, (nf << c->P.seg_shift) * 8));
 		} else {
 			set_seg_shift(c->P, c->seg_init_shift, c->seg_blk_max); // start small again inside the allocation the last run grew to (seg_cap_shift says how far it goes)
-			if (c->n_batches && c->seg_spare && c->seg_spare_shift < c->seg_cap_shift && ((nfine << c->seg_cap_shift) * 8) <= (16ULL << 30)) {
+			if (c->n_batches && c->seg_spare && c->seg_spare_shift < c->seg_cap_shift && ((nf << c->seg_cap_shift) * 8) <= (16ULL << 30)) {
 				// second data set on this context: make the spare as large as the segments grew, so that this run's growths find their target ready
 				BFCG_CK(hipStreamSynchronize(c->st));
 				BFCG_CK(hipFree(c->seg_spare)); c->seg_spare = 0;
-				if (hipMalloc(&c->seg_spare, (nfine << c->seg_cap_shift) * 8) != hipSuccess) { (void)hipGetLastError(); c->seg_spare = 0; }
+				if (hipMalloc(&c->seg_spare, (nf << c->seg_cap_shift) * 8) != hipSuccess) { (void)hipGetLastError(); c->seg_spare = 0; }
 				c->seg_spare_shift = c->seg_cap_shift;
 			}
 		}
 		if (c->n_batches) c->reused = 1;
 		c->P.seg = 1; c->P.b3 = c->b3_ok; c->seg_escaped = 0;
-		BFCG_CK(hipMemsetAsync(c->ho_cur, 0, sizeof(uint32_t) * (size_t)nfine, c->st));
+		BFCG_CK(hipMemsetAsync(c->ho_cur, 0, sizeof(uint32_t) * (size_t)nf, c->st));
 		c->ho_pending = 0; c->slot_commit[0] = c->slot_commit[1] = 0; c->slot_all_committed[0] = c->slot_all_committed[1] = 0; c->keys_known = 0; c->commit_absorbed = 0;
 		c->keys_per_batch = 0; c->n_commits = 0; c->ho_window = 1;
-		BFCG_CK(hipMemsetAsync(c->B.seg_tab, 0, (nfine << c->P.seg_shift) * 8, c->st));
+		BFCG_CK(hipMemsetAsync(c->B.seg_tab, 0, (nf << c->P.seg_shift) * 8, c->st));
 	}
 	if (c->B.table) BFCG_CK(hipMemsetAsync(c->B.table, 0, 8ULL << (c->P.l_pre + c->P.tab_cshift), c->st));
 	if (c->B.tab_first) { BFCG_CK(hipMemsetAsync(c->B.tab_first, 0xff, 8ULL << (c->P.l_pre + c->P.tab_cshift), c->st)); BFCG_CK(hipMemsetAsync(c->B.sub_last, 0, 8ULL << c->P.l_pre, c->st)); }
@@ -543,32 +549,29 @@ extern "C" int bfcg_reset(bfcg_ctx_t *c)
 	return 0;
 }
 
-// bring the slotted counters to the host and fold them into h_stats[0..ST_N)
-static int fetch_stats_on(bfcg_ctx_t *c, hipStream_t s)
+// a copy of the slotted counters folded into h_stats[0..ST_N)
+static void fold_slots(bfcg_ctx_t *c, const unsigned long long *raw)
 {
-	unsigned long long *raw = c->h_stats + ST_N;
-	BFCG_CK(hipMemcpyAsync(raw, c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, s));
-	BFCG_CK(hipStreamSynchronize(s));
 	for (int i = 0; i < ST_N; ++i) {
 		unsigned long long s = 0;
 		for (int j = 0; j < ST_SLOTS; ++j) s += raw[(size_t)j * ST_N + i];
 		c->h_stats[i] = s;
 	}
 	c->h_stats[ST_TAB_OVF] = raw[(size_t)ST_SLOTS * ST_N]; // the overflow list index is a single word
+}
+// bring the slotted counters to the host and fold them
+static int fetch_stats(bfcg_ctx_t *c)
+{
+	unsigned long long *raw = c->h_stats + ST_N;
+	BFCG_CK(hipMemcpyAsync(raw, c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
+	BFCG_CK(hipStreamSynchronize(c->st));
+	fold_slots(c, raw);
 	return 0;
 }
-
-static int fetch_stats(bfcg_ctx_t *c) { return fetch_stats_on(c, c->st); }
 // the snapshot of slot b (complete once evB[b] has fired) folded into h_stats
 static void fold_snapshot(bfcg_ctx_t *c, int b)
 {
-	const unsigned long long *raw = c->h_snap[b];
-	for (int i = 0; i < ST_N; ++i) {
-		unsigned long long s = 0;
-		for (int j = 0; j < ST_SLOTS; ++j) s += raw[(size_t)j * ST_N + i];
-		c->h_stats[i] = s;
-	}
-	c->h_stats[ST_TAB_OVF] = raw[(size_t)ST_SLOTS * ST_N];
+	fold_slots(c, c->h_snap[b]);
 	absorb_pages(c, b);
 	if (c->slot_all_committed[b]) { // nothing waits in the hand-over log behind this batch: the snapshot is the table's state
 		c->final_call = c->slot_call[b]; c->call_keys[c->slot_call[b] & 63] = c->h_stats[ST_KEYS];
@@ -688,8 +691,8 @@ static void note_growth(bfcg_ctx_t *c)
 		c->commit_absorbed = 0;
 	}
 	// more than half of the regions filled their aggregation table in the batch(es) just finalised: aggregation does not pay here
-	const uint64_t crowded = c->h_stats[ST_CROWDED], nfine = ((uint64_t)1 << c->P.F) >> c->log2n;
-	if (!c->stream_mode && c->B.table && !c->P.track && c->P.n_hashes == 4 && c->P.bloom_bt == 512 && !getenv("BFCG_NO_STREAM") && (crowded - c->crowded_last) * 2 > nfine) c->stream_mode = 1;
+	const uint64_t crowded = c->h_stats[ST_CROWDED];
+	if (!c->stream_mode && c->B.table && !c->P.track && c->P.n_hashes == 4 && c->P.bloom_bt == 512 && !getenv("BFCG_NO_STREAM") && (crowded - c->crowded_last) * 2 > nfine(c)) c->stream_mode = 1;
 	c->crowded_last = crowded;
 }
 // sub-table size the table should have now: load <= 1/2 counting parked k-mers and the forecast
@@ -759,7 +762,7 @@ static int table_maintain(bfcg_ctx_t *c)
 static int seg_target_shift(const bfcg_ctx_t *c)
 {
 	const KParams &P = c->P;
-	const uint64_t nfine = ((uint64_t)1 << P.F) >> c->log2n;
+	const uint64_t nf = nfine(c);
 	// growing is one coalesced pass over the segments (k_seg_rehash: c3's 4 GiB in 0.9 ms), a batch into segments that are too full is not:
 	// forecast with the larger of the last two batches' additions
 	// (with the hand-over log the table changes commit by commit: what ONE more batch may add -- the largest page of the last commit, and what a
@@ -767,10 +770,10 @@ static int seg_target_shift(const bfcg_ctx_t *c)
 	const uint64_t need = c->h_stats[ST_KEYS] + c->h_stats[ST_TAB_OVF], g = c->ho_K > 1 ? c->keys_per_batch : c->grow[0] > c->grow[1] ? c->grow[0] : c->grow[1];
 	int t = P.seg_shift;
 	const double full = c->seg_no_grow ? 0.85 : 0.62;
-	while ((double)(need + (c->seg_no_grow ? 0 : g)) > full * (double)(nfine << t)) ++t;
+	while ((double)(need + (c->seg_no_grow ? 0 : g)) > full * (double)(nf << t)) ++t;
 	if (c->h_stats[ST_TAB_OVF] && t == P.seg_shift) ++t; // one full segment under a low overall load
 	if (t != P.seg_shift && getenv("BFCG_DEBUG")) fprintf(stderr, "[D::seg_target] shift %d -> %d: keys %llu parked %llu forecast %llu slots %llu\n", P.seg_shift, t,
-		(unsigned long long)c->h_stats[ST_KEYS], (unsigned long long)c->h_stats[ST_TAB_OVF], (unsigned long long)g, (unsigned long long)(nfine << P.seg_shift));
+		(unsigned long long)c->h_stats[ST_KEYS], (unsigned long long)c->h_stats[ST_TAB_OVF], (unsigned long long)g, (unsigned long long)(nf << P.seg_shift));
 	return t;
 }
 
@@ -779,7 +782,7 @@ static int seg_target_shift(const bfcg_ctx_t *c)
 static int seg_maintain(bfcg_ctx_t *c)
 {
 	KParams &P = c->P; BatchBufs &B = c->B;
-	const uint64_t nfine = ((uint64_t)1 << P.F) >> c->log2n;
+	const uint64_t nf = nfine(c);
 	const double t_dbg = dbg_now();
 	struct dbg_guard { double t; int s0; const int *s1; ~dbg_guard() { if (getenv("BFCG_DEBUG") && *s1 != s0) fprintf(stderr, "[D::seg_maintain] shift %d -> %d: %.3f ms\n", s0, *s1, (dbg_now() - t) * 1e3); } } dg{t_dbg, P.seg_shift, &P.seg_shift};
 	for (;;) {
@@ -790,9 +793,9 @@ static int seg_maintain(bfcg_ctx_t *c)
 		{ // the old segments live until the new ones are filled.  No room (or no LDS: s > 14) for the next size: run fuller instead while nothing is
 		  // parked and the mean load stays below 85 % (probing happens in LDS: a fuller segment costs probes, not HBM traffic) ...
 			size_t free_b = 0, total_b = 0;
-			const bool no_room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && ((nfine << target) * 8) + (1ULL << 30) > (uint64_t)free_b + (c->seg_spare && c->seg_spare_shift >= target ? (nfine << c->seg_spare_shift) * 8 : 0);
+			const bool no_room = hipMemGetInfo(&free_b, &total_b) == hipSuccess && ((nf << target) * 8) + (1ULL << 30) > (uint64_t)free_b + (c->seg_spare && c->seg_spare_shift >= target ? (nf << c->seg_spare_shift) * 8 : 0);
 			if (no_room || target > c->seg_total_max) { // (beyond 2^14 slots a segment is several blocks, one workgroup each: KParams.seg_blk)
-				if (ovf == 0 && (double)c->h_stats[ST_KEYS] < 0.85 * (double)(nfine << P.seg_shift)) { c->seg_no_grow = 1; return 0; }
+				if (ovf == 0 && (double)c->h_stats[ST_KEYS] < 0.85 * (double)(nf << P.seg_shift)) { c->seg_no_grow = 1; return 0; }
 				if (target > c->seg_total_max) return seg_to_legacy(c); // ... else the host's layout takes over (random CAS upserts, any size)
 				// no room for the next segment size, and too full (or k-mers parked) to run on as it is: the host's layout sizes its table to the memory
 				// that IS free (seg_to_legacy) and may well succeed where doubling every segment cannot -- try it before giving up
@@ -807,16 +810,16 @@ static int seg_maintain(bfcg_ctx_t *c)
 		if (c->seg_spare && c->seg_spare_shift >= target) { nt = c->seg_spare; nt_shift = c->seg_spare_shift; c->seg_spare = 0; }
 		else {
 			if (c->seg_spare) { BFCG_CK(hipFree(c->seg_spare)); c->seg_spare = 0; }
-			BFCG_CK(hipMalloc(&nt, (nfine << target) * 8));
+			BFCG_CK(hipMalloc(&nt, (nf << target) * 8));
 		}
-		run_seg_rehash(P, B.seg_tab, old_shift, old_blk, nt, (uint32_t)nfine, c->st);
+		run_seg_rehash(P, B.seg_tab, old_shift, old_blk, nt, (uint32_t)nf, c->st);
 		BFCG_CK(hipStreamSynchronize(c->st));
 		BFCG_CK(hipGetLastError());
-		if (((nfine << nt_shift) * 8) <= (16ULL << 30)) {
+		if (((nf << nt_shift) * 8) <= (16ULL << 30)) {
 			// the buffer left behind becomes the spare the NEXT growth rehashes into; one that is smaller than its successor could not
 			// take that growth after a reset: replace it now, so that from the second data set on a context never allocates
 			// (a fresh multi-GiB hipMalloc costs ~35 ms per GiB on this box: only contexts that are being reused pay for the second buffer)
-			if (c->seg_cap_shift < nt_shift && c->reused) { BFCG_CK(hipFree(B.seg_tab)); c->seg_spare = 0; if (hipMalloc(&c->seg_spare, (nfine << nt_shift) * 8) != hipSuccess) { (void)hipGetLastError(); c->seg_spare = 0; } c->seg_spare_shift = nt_shift; }
+			if (c->seg_cap_shift < nt_shift && c->reused) { BFCG_CK(hipFree(B.seg_tab)); c->seg_spare = 0; if (hipMalloc(&c->seg_spare, (nf << nt_shift) * 8) != hipSuccess) { (void)hipGetLastError(); c->seg_spare = 0; } c->seg_spare_shift = nt_shift; }
 			else { c->seg_spare = B.seg_tab; c->seg_spare_shift = c->seg_cap_shift; }
 		} else BFCG_CK(hipFree(B.seg_tab));
 		B.seg_tab = nt; c->seg_cap_shift = nt_shift;
@@ -842,12 +845,12 @@ static int seg_maintain(bfcg_ctx_t *c)
 static int seg_to_legacy(bfcg_ctx_t *c, int for_export)
 {
 	KParams &P = c->P; BatchBufs &B = c->B;
-	const uint64_t nfine = ((uint64_t)1 << P.F) >> c->log2n;
+	const uint64_t nf = nfine(c);
 	const uint64_t keys = c->h_stats[ST_KEYS];
 	if (c->seg_spare) { BFCG_CK(hipFree(c->seg_spare)); c->seg_spare = 0; }
 	// a context that counts on in the host's layout needs k_bloom's aggregation buffer (1.6 GB at -b35, 6.4 GB at -b37): taken BEFORE the table is
 	// sized to the memory that is free, not at the next batch when nothing may be left
-	if (!for_export && !P.filter_mode && !B.agg_out) BFCG_CK(hipMalloc(&B.agg_out, nfine * P.ag_cap * (P.track ? 32 : 24)));
+	if (!for_export && !P.filter_mode && !B.agg_out) BFCG_CK(hipMalloc(&B.agg_out, nf * P.ag_cap * (P.track ? 32 : 24)));
 	int cs = c->prm.tab_cshift > 0 ? c->prm.tab_cshift : 2;
 	const uint64_t want = for_export ? keys + keys * 3 / 4 : 2 * keys + (c->prm.max_batch_pos / 4);
 	while ((1ULL << (P.l_pre + cs)) < want && P.l_pre + cs < 36) ++cs;
@@ -861,7 +864,7 @@ static int seg_to_legacy(bfcg_ctx_t *c, int for_export)
 	BFCG_CK(hipMemsetAsync(B.table, 0, 8ULL << (P.l_pre + cs), c->st));
 	// the keys are counted afresh: k-mers the reference's lossy key cannot tell apart (k >= 38) become one key here
 	BFCG_CK(hipMemset2DAsync(B.stats + ST_KEYS, sizeof(unsigned long long) * ST_N, 0, sizeof(unsigned long long), ST_SLOTS, c->st));
-	run_seg_to_table(P, B.seg_tab, (uint32_t)nfine, B.table, B.stats, B.tab_ovf, B.tab_ovf_cap, c->st);
+	run_seg_to_table(P, B.seg_tab, (uint32_t)nf, B.table, B.stats, B.tab_ovf, B.tab_ovf_cap, c->st);
 	BFCG_CK(hipStreamSynchronize(c->st));
 	BFCG_CK(hipGetLastError());
 	BFCG_CK(hipFree(B.seg_tab));
@@ -887,6 +890,104 @@ extern "C" int bfcg_table_info(bfcg_ctx_t *c, int out[4])
 	return 0;
 }
 
+// ---- what every kind of batch shares: its parameters, its buffers, the enqueue of its stage B
+
+// The kernel parameters of the batch about to be enqueued.  k_bloom resolves the copies of a k-mer by class before the bit-level protocol
+// (KParams.dedupe) where that pays, and the LDS tables follow the filter's state (warm_tables).  onepass1: a single GPU's batch whose level 1
+// runs in one pass -- only there may level 2 work on tiles of 8192 records where a tile of 4096 would leave as runs of four (2^10 regions per
+// bucket): BFCG_L2_BIG=2; =1: from 2^9 on.  OFF by default: measured level with the small tile on c4e (64.9 against 62.3 ms per step: DESIGN 6b)
+// -- the kernel's rate there is not set by the run length.  The flag says which tile k_seg_setup counts the segments' rows in, so it is set only
+// where the launch will take the 8192-tile kernel (scatter2_big_ok): rows of 8192 under a kernel of 4096 lose the second half of every row.
+static KParams batch_params(const bfcg_ctx_t *c, int no_kstats, int onepass1)
+{
+	KParams Pt = c->P;
+	Pt.no_kstats = no_kstats;
+	Pt.dedupe = dedupe_hint(c);
+	warm_tables(c, Pt);
+	if (onepass1) {
+		const char *e = getenv("BFCG_L2_BIG");
+		const int want = e ? atoi(e) : 0;
+		Pt.l2_big = c->cap2 && want > 0 && Pt.F2 >= (want == 1 ? 9 : 10) && scatter2_big_ok(Pt);
+	}
+	return Pt;
+}
+
+// The context's buffers as that batch sees them: its number (order stamps) and how its seen k-mers are handed over.  (They go into the batch's
+// copy alone: the kernels read nothing else, and the context's own copy of these three fields is never read.)
+static int batch_bufs(bfcg_ctx_t *c, BatchBufs &Bt)
+{
+	if (ensure_agg(c) != 0 || use_stream(c) != 0) return -1;
+	Bt = c->B;
+	Bt.batch_hi = (unsigned long long)(c->n_batches + 1) << 32;
+	Bt.stream = c->stream_mode; Bt.stream_out = c->stream_out;
+	return 0;
+}
+
+// What differs between the stage Bs: the records and their segment arrays (run_stage_b's arguments), and how the batch is known afterwards
+struct StageB {
+	const uint64_t *in1; const uint32_t *seg_beg, *seg_end; int n_seg, segs_per_bucket; const uint32_t *row_base, *bucket_start; uint64_t rec_bound;
+	int slabs;           // its level 2 runs in one pass: a page of the hand-over log (handover_begin)
+	int queued;          // it belongs to a one-pass run: it tests the sticky word and waits in the replay queue until it is known to be clean
+	uint64_t call, pos;  // the call it belongs to (the context's call number from here on); its positions -- a rank's: the records it received
+	const uint8_t *seq, *qual; // what a replay starts from: a single GPU's streams,
+	const void *recv; const uint32_t *sizes; int sizes_slab; // or a rank's receive buffer and its sizes (nullptr: they follow; slab fills or bucket counts)
+	int finalise;        // the call returns once the PREVIOUS batch is finalised (0: the caller does that later)
+};
+
+// the batch of slot b waits in the replay queue; a rank's keeps a copy of its sizes in a free mg_seg (opq_t.mg says which, + 1)
+static int opq_push(bfcg_ctx_t *c, int b, const StageB &w)
+{
+	if (c->n_opq == 4) return fail("internal: one-pass queue overflow");
+	int mg = 0;
+	if (w.recv) {
+		const size_t words = (size_t)c->n_ranks * (size_t)((1 << c->P.F1) >> c->log2n) * (w.sizes_slab ? 8 : 1);
+		for (;; ++mg) { int used = 0; for (int i = 0; i < c->n_opq; ++i) used |= c->opq[i].mg == mg + 1; if (!used) break; }
+		if (w.sizes) memcpy(c->mg_seg[mg], w.sizes, sizeof(uint32_t) * words); else memset(c->mg_seg[mg], 0, sizeof(uint32_t) * words);
+		c->mg_seg_slab[mg++] = w.sizes_slab;
+	}
+	c->opq[c->n_opq++] = bfcg_ctx::opq_t{w.seq, w.qual, w.pos, b, w.recv, mg};
+	return 0;
+}
+
+// Stage B of the batch in slot b goes onto stream st behind whatever the caller has put there for it (its waits, the start event evt[b][6], a
+// rank's segment arrays, the clearing of seen_out and of a rank's slab flags): hand-over, the kernels, the sticky word and the counters'
+// snapshot behind them, evB -- and the batch is in flight.
+static int enqueue_stage_b(bfcg_ctx_t *c, int b, BatchBufs &Bt, const KParams &Pt, const StageB &w)
+{
+	if (handover_begin(c, Bt, b, w.slabs, w.call) != 0) return -1;
+	run_stage_b(Pt, Bt, w.in1, w.seg_beg, w.seg_end, w.n_seg, w.segs_per_bucket, w.row_base, w.bucket_start, w.rec_bound, c->st, c->evt[b]);
+	if (handover_end(c, Bt, b) != 0) return -1;
+	if (w.queued) { // behind k_seal: is the run poisoned up to and including this batch?  (read with the batch's snapshot; an overflow is replayed: replay_poisoned)
+		BFCG_CK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
+		if (opq_push(c, b, w) != 0) return -1;
+	}
+	BFCG_CK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
+	c->slot_call[b] = c->call_no = w.call; c->slot_pos[b] = w.pos; // (a rank's stage B is a call of its own: w.call is the next number; a single GPU's batch belongs to the current one)
+	BFCG_CK(hipEventRecord(c->evB[b], c->st));
+	BFCG_CK(hipGetLastError());
+	c->used[b] = 1;
+	++c->n_batches;
+	return w.finalise ? finalise_previous(c, b) : 0;
+}
+
+// A rank's stage B over the segment arrays at d (seg_beg | seg_end | row_base | bucket_start, on the device or on their way there on stream st).
+// Level 2 in one pass where the group allows it and the batch has more than a handful of records per region; no one-pass stage A on a rank, so
+// stage B clears its slot's flags itself.  (As for a single GPU every batch of a one-pass run tests the sticky word and is queued: enqueue_batch.)
+static int mg_stage_b(bfcg_ctx_t *c, int b, const void *d_recv, const uint32_t *d, int n_seg, int spb, uint64_t rec_bound, const uint32_t *sizes, int sizes_slab, int finalise)
+{
+	BatchBufs Bt;
+	if (batch_bufs(c, Bt) != 0) return -1;
+	const int op2_run = c->mg_op2 && c->mg_op2_allowed && c->cap2;
+	const int op2 = op2_run && rec_bound >= 8 * nfine(c);
+	if (op2_run) Bt.op_sticky = c->op_flags + OP_STICKY;
+	if (op2) {
+		Bt.cnt2 = c->cnt2; Bt.cap2 = c->cap2; Bt.op_flags = c->op_flags + 4 * b;
+		BFCG_CK(hipMemsetAsync(Bt.op_flags, 0, 4 * sizeof(uint32_t), c->st));
+	}
+	const StageB w = {(const uint64_t *)d_recv, d, d + n_seg, n_seg, spb, d + 2 * n_seg, d + 3 * n_seg + 1, rec_bound, op2, op2_run, c->call_no + 1, rec_bound, nullptr, nullptr, d_recv, sizes, sizes_slab, finalise};
+	return enqueue_stage_b(c, b, Bt, batch_params(c, 0, 0), w);
+}
+
 // ---- multi-GPU (owner computes): stage A on every rank, exchange by the caller, stage B on the owner
 
 extern "C" int bfcg_mg_info(bfcg_ctx_t *c, int out[4])
@@ -904,19 +1005,36 @@ extern "C" int bfcg_mg_scatter_again(bfcg_ctx_t *c, const uint8_t *d_seq, const 
 // A group of ONE rank has no exchange for stage A of the next batch to run beside: its kernels follow stage B on the same stream wherever a
 // single GPU's do (c->pipeline: kernels sized to fill the chip fight for its CUs -- DESIGN.md section 6b, c3 on two streams).
 static inline hipStream_t mg_stage_a_stream(bfcg_ctx_t *c) { return c->n_ranks == 1 && !c->pipeline ? c->st : c->stA; }
+// What a rank's stage A begins with, whichever partition it takes: 1 = the batch is empty (nothing to contribute to this global batch: the
+// timing events are kept defined and the caller hands out zeros), 0 = go on (the qualities where k_scatter1 wants them), -1 = failed
+static int mg_stage_a_begin(bfcg_ctx_t *c, int b, hipStream_t sA, const uint8_t *d_seq, const uint8_t **d_qual, uint64_t n_pos)
+{
+	if (batch_fits(c, n_pos) != 0) return -1;
+	BFCG_CK(hipSetDevice(c->prm.device));
+	if (n_pos == 0) {
+		for (int i = 0; i < 3; ++i) BFCG_CK(hipEventRecord(c->evt[b][i], sA));
+		return 1;
+	}
+	return same_block_offset(c, b, d_seq, d_qual, n_pos, sA);
+}
+// the buffers of a one-pass stage A in slot b whose slabs are a group's (own_delta: see bfcg_mg_scatter_slabs)
+static BatchBufs mg_slab_bufs(const bfcg_ctx_t *c, int b, uint32_t own_delta)
+{
+	const uint32_t nb_loc = (1u << c->P.F1) >> c->log2n;
+	BatchBufs Bt = c->B;
+	Bt.op_cursor = c->op_cursor[b]; Bt.op_seg = c->op_seg[b]; Bt.op_flags = c->op_flags + 4 * b; Bt.op_cap = c->op_cap; Bt.cap2 = c->cap2;
+	Bt.op_own_lo = (uint32_t)c->rank * nb_loc; Bt.op_own_n = nb_loc; Bt.op_own_delta = own_delta;
+	return Bt;
+}
 static int mg_scatter2(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t *counts, int no_kstats)
 {
 	const int nb1 = 1 << c->P.F1, b = c->cur;
 	const hipStream_t sA = mg_stage_a_stream(c);
-	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	BFCG_CK(hipSetDevice(c->prm.device));
-	if (n_pos == 0) { // nothing to contribute to this global batch: keep the timing events defined
-		for (int i = 0; i < 3; ++i) BFCG_CK(hipEventRecord(c->evt[b][i], sA));
-		memset(counts, 0, sizeof(uint32_t) * nb1); return 0;
-	}
+	const int begun = mg_stage_a_begin(c, b, sA, d_seq, &d_qual, n_pos);
+	if (begun == 1) memset(counts, 0, sizeof(uint32_t) * nb1);
+	if (begun) return begun < 0 ? -1 : 0;
 	BatchBufs Bt = c->B;
 	Bt.rows1 = c->rows1[b]; Bt.chunk1 = c->chunk1[b]; Bt.start1 = c->start1[b]; Bt.row_base = Bt.start1 + nb1 + 1;
-	if (same_block_offset(c, b, d_seq, &d_qual, n_pos, sA) != 0) return -1;
 	KParams Pa = c->P;
 	Pa.no_kstats = no_kstats;
 	run_stage_a(Pa, Bt, d_seq, d_qual, (int64_t)n_pos, (uint64_t *)d_send, sA, c->evt[b]);
@@ -939,20 +1057,14 @@ static int mg_scatter2(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qua
 extern "C" int bfcg_mg_slab_info(bfcg_ctx_t *c, uint32_t out[2]) { out[0] = c->op_cap; out[1] = (uint32_t)(c->mg_slab_ok && c->op_cursor[0] != 0); return 0; }
 extern "C" int bfcg_mg_scatter_slabs(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *fills, int *overflow)
 {
-	const int nb1 = 1 << c->P.F1, nb_loc = nb1 >> c->log2n, b = c->cur;
+	const int nb1 = 1 << c->P.F1, b = c->cur;
 	const hipStream_t sA = mg_stage_a_stream(c);
 	*overflow = 0;
 	if (!c->mg_slab_ok || !c->op_cursor[b]) return fail("this context has no slab mode");
-	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	BFCG_CK(hipSetDevice(c->prm.device));
-	if (n_pos == 0) { // nothing to contribute to this global batch: keep the timing events defined
-		for (int i = 0; i < 3; ++i) BFCG_CK(hipEventRecord(c->evt[b][i], sA));
-		memset(fills, 0, sizeof(uint32_t) * (size_t)nb1 * 8); return 0;
-	}
-	BatchBufs Bt = c->B;
-	Bt.op_cursor = c->op_cursor[b]; Bt.op_seg = c->op_seg[b]; Bt.op_flags = c->op_flags + 4 * b; Bt.op_cap = c->op_cap; Bt.cap2 = c->cap2;
-	Bt.op_own_lo = (uint32_t)c->rank * (uint32_t)nb_loc; Bt.op_own_n = (uint32_t)nb_loc; Bt.op_own_delta = own_delta;
-	if (same_block_offset(c, b, d_seq, &d_qual, n_pos, sA) != 0) return -1;
+	const int begun = mg_stage_a_begin(c, b, sA, d_seq, &d_qual, n_pos);
+	if (begun == 1) memset(fills, 0, sizeof(uint32_t) * (size_t)nb1 * 8);
+	if (begun) return begun < 0 ? -1 : 0;
+	const BatchBufs Bt = mg_slab_bufs(c, b, own_delta);
 	run_stage_a_onepass(c->P, Bt, d_seq, d_qual, (int64_t)n_pos, (uint64_t *)d_send, sA, c->evt[b]);
 	BFCG_CK(hipGetLastError());
 	std::vector<uint32_t> tmp((size_t)8 * nb1);
@@ -973,20 +1085,15 @@ extern "C" int bfcg_mg_scatter_slabs(bfcg_ctx_t *c, const uint8_t *d_seq, const 
 extern "C" int bfcg_mg_row_words(bfcg_ctx_t *c) { return (((1 << c->P.F1) >> c->log2n) * 8) + 2; }
 extern "C" int bfcg_mg_scatter_slabs_async(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *d_rows_out, hipEvent_t *done)
 {
-	const int nb1 = 1 << c->P.F1, nb_loc = nb1 >> c->log2n, b = c->cur, row_w = nb_loc * 8 + 2;
+	const int b = c->cur, row_w = bfcg_mg_row_words(c);
 	const hipStream_t sA = mg_stage_a_stream(c);
 	if (!c->mg_slab_ok || !c->op_cursor[b] || !c->h_rows[b]) return fail("this context has no slab mode");
-	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	BFCG_CK(hipSetDevice(c->prm.device));
+	const int begun = mg_stage_a_begin(c, b, sA, d_seq, &d_qual, n_pos);
+	if (begun < 0) return -1;
 	const size_t row_bytes = sizeof(uint32_t) * (size_t)c->n_ranks * row_w;
-	if (n_pos == 0) { // nothing to contribute to this global batch: rows of zeros; keep the timing events defined
-		for (int i = 0; i < 3; ++i) BFCG_CK(hipEventRecord(c->evt[b][i], sA));
-		BFCG_CK(hipMemsetAsync(d_rows_out, 0, row_bytes, sA));
-	} else {
-		BatchBufs Bt = c->B;
-		Bt.op_cursor = c->op_cursor[b]; Bt.op_seg = c->op_seg[b]; Bt.op_flags = c->op_flags + 4 * b; Bt.op_cap = c->op_cap; Bt.cap2 = c->cap2;
-		Bt.op_own_lo = (uint32_t)c->rank * (uint32_t)nb_loc; Bt.op_own_n = (uint32_t)nb_loc; Bt.op_own_delta = own_delta;
-		if (same_block_offset(c, b, d_seq, &d_qual, n_pos, sA) != 0) return -1;
+	if (begun) BFCG_CK(hipMemsetAsync(d_rows_out, 0, row_bytes, sA)); // (rows of zeros)
+	else {
+		const BatchBufs Bt = mg_slab_bufs(c, b, own_delta);
 		run_stage_a_onepass(c->P, Bt, d_seq, d_qual, (int64_t)n_pos, (uint64_t *)d_send, sA, c->evt[b]);
 		run_pack_rows(c->P, Bt, c->n_ranks, (uint32_t)row_w, d_rows_out, sA);
 		BFCG_CK(hipGetLastError());
@@ -1018,7 +1125,6 @@ extern "C" int bfcg_mg_scatter_slabs_wait(bfcg_ctx_t *c, uint32_t *fills, int *o
 // next bfcg_mg_process (or bfcg_sync) returns: callers alternate between two receive buffers.
 // slab_cap != 0 (bfcg_mg_process_slabs): d_recv holds, source-major, every source's SLABS for the owned buckets (8 per bucket, slab_cap records
 // each, at fixed places) and seg_cnt[(s * nb_loc + b) * 8 + x] says how far each is filled.
-static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, uint32_t slab_cap, hipEvent_t *wait, int n_wait);
 extern "C" int bfcg_mg_process_ev(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, hipEvent_t *wait, int n_wait) { return mg_process_any(c, d_recv, seg_cnt, 0u, wait, n_wait); }
 extern "C" int bfcg_mg_process(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt) { return mg_process_any(c, d_recv, seg_cnt, 0u, 0, 0); }
 extern "C" int bfcg_mg_process_slabs(bfcg_ctx_t *c, const void *d_recv, const uint32_t *fills, uint32_t slab_cap, hipEvent_t *wait, int n_wait) { return mg_process_any(c, d_recv, fills, slab_cap, wait, n_wait); }
@@ -1061,39 +1167,7 @@ static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg
 	BFCG_CK(hipEventRecord(c->evt[b][6], c->st));
 	BFCG_CK(hipMemcpyAsync(d, seg_beg, sizeof(uint32_t) * words, hipMemcpyHostToDevice, c->st));
 	if (c->B.seen_out) BFCG_CK(hipMemsetAsync(c->B.seen_out, 0, c->prm.max_batch_pos, c->st));
-	c->B.batch_hi = (unsigned long long)(c->n_batches + 1) << 32;
-	if (use_stream(c) != 0 || ensure_agg(c) != 0) return -1;
-	c->B.stream = c->stream_mode; c->B.stream_out = c->stream_out;
-	BatchBufs Bt = c->B;
-	const int op2_run = c->mg_op2 && c->mg_op2_allowed && c->cap2; // (as enqueue_batch: every batch of a one-pass run tests the sticky word and is queued)
-	const int op2 = op2_run && off >= (uint64_t)8 << c->P.F >> c->log2n; // (a handful of records per region: two passes)
-	if (op2_run) Bt.op_sticky = c->op_flags + OP_STICKY;
-	if (op2) {
-		Bt.cnt2 = c->cnt2; Bt.cap2 = c->cap2; Bt.op_flags = c->op_flags + 4 * b;
-		BFCG_CK(hipMemsetAsync(Bt.op_flags, 0, 4 * sizeof(uint32_t), c->st)); // (no one-pass stage A on a rank: stage B clears its slot's flags itself)
-	}
-	if (handover_begin(c, Bt, b, op2, c->call_no + 1) != 0) return -1; // (this call's number: assigned below)
-	KParams Pm = c->P;
-	Pm.dedupe = dedupe_hint(c);
-	warm_tables(c, Pm);
-	run_stage_b(Pm, Bt, (const uint64_t *)d_recv, d, d + n_seg, n_seg, spb, d + 2 * n_seg, d + 3 * n_seg + 1, off, c->st, c->evt[b]);
-	if (handover_end(c, Bt, b) != 0) return -1;
-	if (op2_run) { // was every region's slab large enough?  (as for a single GPU: the flag is read with the batch's snapshot, an overflow is replayed -- stage B only)
-		BFCG_CK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
-		if (c->n_opq == 4) return fail("internal: one-pass queue overflow");
-		int free_i = 0;
-		for (;; ++free_i) { int used = 0; for (int i = 0; i < c->n_opq; ++i) used |= c->opq[i].mg == free_i + 1; if (!used) break; }
-		memcpy(c->mg_seg[free_i], seg_cnt, sizeof(uint32_t) * (size_t)N * nb_loc * (slab_cap ? 8 : 1)); c->mg_seg_slab[free_i] = slab_cap != 0;
-		bfcg_ctx::opq_t &q = c->opq[c->n_opq++];
-		q.seq = q.qual = nullptr; q.n_pos = off; q.slot = b; q.recv = d_recv; q.mg = free_i + 1;
-	}
-	BFCG_CK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
-	c->slot_call[b] = ++c->call_no; c->slot_pos[b] = off;
-	BFCG_CK(hipEventRecord(c->evB[b], c->st));
-	BFCG_CK(hipGetLastError());
-	c->used[b] = 1;
-	++c->n_batches;
-	return finalise_previous(c, b);
+	return mg_stage_b(c, b, d_recv, d, n_seg, spb, off, seg_cnt, slab_cap != 0, 1);
 }
 
 // Stage B of a global batch whose sizes the host does not have yet (slab mode, all ranks in one process): d_rows_in holds every source's row for
@@ -1117,39 +1191,9 @@ extern "C" int bfcg_mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, cons
 	for (int i = 0; i < n_wait; ++i) BFCG_CK(hipStreamWaitEvent(c->st, wait[i], 0));
 	BFCG_CK(hipEventRecord(c->evt[b][6], c->st));
 	run_seg_setup_mg(c->P, c->rw / 4, d_rows_in, (uint32_t)(nb_loc * 8 + 2), N, s_lo, s_hi, slab_cap, d, nullptr, c->st);
-	c->B.batch_hi = (unsigned long long)(c->n_batches + 1) << 32;
-	if (use_stream(c) != 0 || ensure_agg(c) != 0) return -1;
-	c->B.stream = c->stream_mode; c->B.stream_out = c->stream_out;
-	BatchBufs Bt = c->B;
-	const int op2_run = c->mg_op2 && c->mg_op2_allowed && c->cap2;
-	const int op2 = op2_run && rec_bound >= (uint64_t)8 << c->P.F >> c->log2n;
-	if (op2_run) Bt.op_sticky = c->op_flags + OP_STICKY;
-	if (op2) {
-		Bt.cnt2 = c->cnt2; Bt.cap2 = c->cap2; Bt.op_flags = c->op_flags + 4 * b;
-		BFCG_CK(hipMemsetAsync(Bt.op_flags, 0, 4 * sizeof(uint32_t), c->st));
-	}
-	if (handover_begin(c, Bt, b, op2, c->call_no + 1) != 0) return -1;
-	KParams Pm = c->P;
-	Pm.dedupe = dedupe_hint(c);
-	warm_tables(c, Pm);
-	run_stage_b(Pm, Bt, (const uint64_t *)d_recv, d, d + n_seg, n_seg, spb, d + 2 * n_seg, d + 3 * n_seg + 1, rec_bound, c->st, c->evt[b]);
-	if (handover_end(c, Bt, b) != 0) return -1;
-	if (op2_run) {
-		BFCG_CK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st));
-		if (c->n_opq == 4) return fail("internal: one-pass queue overflow");
-		int free_i = 0;
-		for (;; ++free_i) { int used = 0; for (int i = 0; i < c->n_opq; ++i) used |= c->opq[i].mg == free_i + 1; if (!used) break; }
-		memset(c->mg_seg[free_i], 0, sizeof(uint32_t) * (size_t)N * nb_loc * 8); c->mg_seg_slab[free_i] = 1; // (the sizes follow: bfcg_mg_process_finish)
-		bfcg_ctx::opq_t &q = c->opq[c->n_opq++];
-		q.seq = q.qual = nullptr; q.n_pos = rec_bound; q.slot = b; q.recv = d_recv; q.mg = free_i + 1;
-		c->unfinished_mg = free_i + 1;
-	} else c->unfinished_mg = 0;
-	BFCG_CK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
-	c->slot_call[b] = ++c->call_no; c->slot_pos[b] = rec_bound;
-	BFCG_CK(hipEventRecord(c->evB[b], c->st));
-	BFCG_CK(hipGetLastError());
-	c->used[b] = 1;
-	++c->n_batches;
+	const int n_q = c->n_opq; // (a stage B pushes at most one entry, at the queue's end, and nothing is popped before bfcg_mg_process_finish: opq[n_q] is this batch's, if any)
+	if (mg_stage_b(c, b, d_recv, d, n_seg, spb, rec_bound, nullptr, 1, 0) != 0) return -1; // (the sizes follow, and with them the previous batch's end: bfcg_mg_process_finish)
+	c->unfinished_mg = c->n_opq > n_q ? c->opq[n_q].mg : 0;
 	c->unfinished = 1;
 	return 0;
 }
@@ -1212,11 +1256,11 @@ static int finalise_previous(bfcg_ctx_t *c, int b)
 static int commit_pending_pages(bfcg_ctx_t *c, int b)
 {
 	if (!c->ho_pending) return 0;
-	const uint32_t nfine = (uint32_t)(((uint64_t)1 << c->P.F) >> c->log2n);
+	const uint32_t nf = (uint32_t)nfine(c);
 	BatchBufs Bt = c->B;
-	Bt.ho = c->ho; Bt.ho_stride = c->ho_stride; Bt.ho_cur = c->ho_cur; Bt.ho_mark = c->ho_mark; Bt.ho_mark_stride = nfine; Bt.ho_keys = c->ho_keys;
+	Bt.ho = c->ho; Bt.ho_stride = c->ho_stride; Bt.ho_cur = c->ho_cur; Bt.ho_mark = c->ho_mark; Bt.ho_mark_stride = nf; Bt.ho_keys = c->ho_keys;
 	BFCG_CK(hipMemsetAsync(c->ho_keys, 0, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, c->st));
-	run_commit_pages(c->P, Bt, nfine, (uint32_t)c->ho_pending, c->st);
+	run_commit_pages(c->P, Bt, nf, (uint32_t)c->ho_pending, c->st);
 	BFCG_CK(hipMemcpyAsync(c->h_ho_keys[b], c->ho_keys, sizeof(unsigned long long) * ST_SLOTS * (size_t)c->ho_pending, hipMemcpyDeviceToHost, c->st));
 	c->slot_commit[b] = c->ho_pending;
 	memcpy(c->slot_page_call[b], c->ho_page_call, sizeof(uint64_t) * (size_t)c->ho_pending);
@@ -1230,9 +1274,9 @@ static int handover_begin(bfcg_ctx_t *c, BatchBufs &Bt, int b, int slabs, uint64
 {
 	c->slot_commit[b] = 0; c->slot_all_committed[b] = 1;
 	if (!c->P.seg) return 0;
-	const uint32_t nfine = (uint32_t)(((uint64_t)1 << c->P.F) >> c->log2n);
+	const uint32_t nf = (uint32_t)nfine(c);
 	Bt.stream_out = (uint32_t *)c->ho;
-	Bt.ho = c->ho; Bt.ho_cur = c->ho_cur; Bt.ho_mark = c->ho_mark; Bt.ho_mark_stride = nfine; Bt.ho_keys = c->ho_keys;
+	Bt.ho = c->ho; Bt.ho_cur = c->ho_cur; Bt.ho_mark = c->ho_mark; Bt.ho_mark_stride = nf; Bt.ho_keys = c->ho_keys;
 	if (!slabs || c->ho_stride == 0 || Bt.seen_out) { // (debug_seen contexts run one batch at a time anyway)
 		if (commit_pending_pages(c, b) != 0) return -1;
 		Bt.ho_stride = 0; Bt.ho_page = 0; Bt.ho_commit = 1; Bt.ho_keys = nullptr;
@@ -1244,12 +1288,12 @@ static int handover_begin(bfcg_ctx_t *c, BatchBufs &Bt, int b, int slabs, uint64
 		if (c->ho_K > 1 && c->n_commits > 0) {
 			// (upserts probe in LDS: a window may fill the segments to 85 % on average; what a batch adds only shrinks as the keys level off, so
 			// the last commit's largest page bounds the next batches'; a segment that fills up all the same parks its k-mers, exactly)
-			const double room = 0.85 * (double)((uint64_t)nfine << c->P.seg_shift) - (double)c->keys_known, g = 1.1 * (double)(c->keys_per_batch ? c->keys_per_batch : 1);
+			const double room = 0.85 * (double)((uint64_t)nf << c->P.seg_shift) - (double)c->keys_known, g = 1.1 * (double)(c->keys_per_batch ? c->keys_per_batch : 1);
 			w = room <= g ? 1 : room / g >= (double)c->ho_K ? c->ho_K : (int)(room / g);
 		}
 		c->ho_window = w;
 		if (getenv("BFCG_DEBUG")) fprintf(stderr, "[D::window] %d batches: keys %llu, largest page of the last commit %llu, slots %llu, commits so far %d\n", w,
-			(unsigned long long)c->keys_known, (unsigned long long)c->keys_per_batch, (unsigned long long)((uint64_t)nfine << c->P.seg_shift), c->n_commits);
+			(unsigned long long)c->keys_known, (unsigned long long)c->keys_per_batch, (unsigned long long)((uint64_t)nf << c->P.seg_shift), c->n_commits);
 	}
 	Bt.ho_stride = c->ho_stride; Bt.ho_page = (uint32_t)c->ho_pending;
 	c->ho_page_call[c->ho_pending++] = call;
@@ -1307,73 +1351,49 @@ static int same_block_offset(bfcg_ctx_t *c, int b, const uint8_t *d_seq, const u
 static int ensure_agg(bfcg_ctx_t *c)
 {
 	if (c->P.filter_mode || c->P.seg || c->B.agg_out) return 0;
-	const uint64_t nfine = ((uint64_t)1 << c->P.F) >> c->log2n;
-	BFCG_CK(hipMalloc(&c->B.agg_out, nfine * c->P.ag_cap * (c->P.track ? 32 : 24)));
+	BFCG_CK(hipMalloc(&c->B.agg_out, nfine(c) * c->P.ag_cap * (c->P.track ? 32 : 24)));
 	return 0;
 }
 
 static int enqueue_batch(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, int wait_copy, int no_kstats)
 {
 	const int b = c->cur, nb1 = 1 << c->P.F1;
-	if (ensure_agg(c) != 0) return -1;
-	BatchBufs Bt = c->B;
-	Bt.batch_hi = (unsigned long long)(c->n_batches + 1) << 32;
+	BatchBufs Bt;
+	if (batch_bufs(c, Bt) != 0) return -1;
 	Bt.rows1 = c->rows1[b]; Bt.chunk1 = c->chunk1[b]; Bt.start1 = c->start1[b]; Bt.row_base = Bt.start1 + nb1 + 1; Bt.recs1 = c->recs1[b];
 	hipStream_t sA = c->pipeline ? c->stA : c->st; // one stream: the batches' kernels simply follow each other
 	if (c->used[b]) BFCG_CK(hipStreamWaitEvent(sA, c->evB[b], 0)); // stage B two batches ago has released this buffer set
 	if (!c->pipeline && wait_copy) BFCG_CK(hipStreamWaitEvent(sA, c->evCopy, 0)); // the host batch is being copied on stream stA
-	if (use_stream(c) != 0) return -1;
-	Bt.stream = c->stream_mode; Bt.stream_out = c->stream_out;
-	KParams Pt = c->P;
-	Pt.no_kstats = no_kstats;
-	Pt.dedupe = dedupe_hint(c);
-	warm_tables(c, Pt);
-	const uint8_t *const d_qual_given = d_qual; // (what a replay starts from again)
-	if (same_block_offset(c, b, d_seq, &d_qual, n_pos, sA) != 0) return -1;
 	const int op_run = c->onepass && !no_kstats;  // the run still uses the one-pass partition: an earlier batch may turn out to have overflowed a slab
 	const int op = op_run && n_pos >= c->op_min_pos; // (a handful of tiles cannot fill 8 slabs per bucket evenly: such a batch takes two passes)
+	const KParams Pt = batch_params(c, no_kstats, op);
+	StageB w = {};
+	w.seq = d_seq; w.qual = d_qual; // (what a replay starts from again: the qualities as given)
+	if (same_block_offset(c, b, d_seq, &d_qual, n_pos, sA) != 0) return -1;
 	// every batch of such a run -- one-pass or not -- tests the sticky word in its stage B and waits in the queue until it is known to be clean:
 	// a small two-pass batch enqueued behind a poisoned one must not be applied before the replay of that one
 	if (op_run) Bt.op_sticky = c->op_flags + OP_STICKY;
 	if (op) {
 		Bt.op_cursor = c->op_cursor[b]; Bt.op_seg = c->op_seg[b]; Bt.op_flags = c->op_flags + 4 * b; Bt.op_cap = c->op_cap;
 		Bt.cnt2 = c->cnt2; Bt.cap2 = c->cap2;
-		{ // level 2 on tiles of 8192 records where a tile of 4096 would leave as runs of four (2^10 regions per bucket): BFCG_L2_BIG=2; =1: from 2^9 on.  OFF by default:
-		  // measured level with the small tile on c4e (64.9 against 62.3 ms per step: DESIGN 6b) -- the kernel's rate there is not set by the run length
-			const char *e = getenv("BFCG_L2_BIG");
-			const int want = e ? atoi(e) : 0;
-			Pt.l2_big = c->rw == 12 && c->cap2 && want > 0 && Pt.F2 >= (want == 1 ? 9 : 10);
-		}
 		run_stage_a_onepass(Pt, Bt, d_seq, d_qual, (int64_t)n_pos, Bt.recs1, sA, c->evt[b]);
 	} else run_stage_a(Pt, Bt, d_seq, d_qual, (int64_t)n_pos, Bt.recs1, sA, c->evt[b]);
 	BFCG_CK(hipEventRecord(c->evA[b], sA));
 	BFCG_CK(hipStreamWaitEvent(c->st, c->evA[b], 0));
 	BFCG_CK(hipEventRecord(c->evt[b][6], c->st));
 	if (c->B.seen_out) BFCG_CK(hipMemsetAsync(c->B.seen_out, 0, n_pos, c->st));
-	if (handover_begin(c, Bt, b, op && Bt.cap2, c->call_no) != 0) return -1;
+	w.in1 = Bt.recs1; w.segs_per_bucket = op ? 8 : 1; w.n_seg = nb1 * w.segs_per_bucket;
 	if (op) {
-		uint32_t *sg = c->op_seg[b];
+		const uint32_t *sg = c->op_seg[b];
 		// the bound on level 2's rows is the slabs' CAPACITY, not the batch's positions: a segment is a slab's fill, and that holds the dead records of
 		// everything level 1 reserved and did not use -- per (workgroup, bucket) a group and a half and a padded buffer with k_scatter1_wc, whatever
 		// the batch's size.  With n_pos here, a batch of a few million positions in a context sized for 2^28 had more rows than workgroups, and the
 		// k-mers of the rows beyond the grid were lost without a word (tests/test_gpu_parity.py::test_small_batch_in_a_large_context).
 		// Surplus workgroups leave at once.
-		run_stage_b(Pt, Bt, Bt.recs1, sg, sg + 8 * nb1, 8 * nb1, 8, sg + 16 * nb1, sg + 24 * nb1 + 1, (uint64_t)8 * nb1 * c->op_cap, c->st, c->evt[b]);
-	} else
-	run_stage_b(Pt, Bt, Bt.recs1, Bt.start1, Bt.start1 + 1, nb1, 1, Bt.row_base, Bt.start1, n_pos, c->st, c->evt[b]);
-	if (handover_end(c, Bt, b) != 0) return -1;
-	if (op_run) {
-		BFCG_CK(hipMemcpyAsync(c->h_flags[b] + 1, c->op_flags + OP_STICKY, sizeof(uint32_t), hipMemcpyDeviceToHost, c->st)); // behind k_seal: is the run poisoned up to and including this batch?
-		if (c->n_opq == 4) return fail("internal: one-pass queue overflow");
-		c->opq[c->n_opq].seq = d_seq; c->opq[c->n_opq].qual = d_qual_given; c->opq[c->n_opq].n_pos = n_pos; c->opq[c->n_opq].slot = b; c->opq[c->n_opq].recv = nullptr; c->opq[c->n_opq].mg = 0; ++c->n_opq;
-	}
-	BFCG_CK(hipMemcpyAsync(c->h_snap[b], c->B.stats, sizeof(unsigned long long) * ST_N * (ST_SLOTS + 1), hipMemcpyDeviceToHost, c->st));
-	c->slot_call[b] = c->call_no; c->slot_pos[b] = n_pos;
-	BFCG_CK(hipEventRecord(c->evB[b], c->st));
-	BFCG_CK(hipGetLastError());
-	c->used[b] = 1;
-	++c->n_batches;
-	return finalise_previous(c, b);
+		w.seg_beg = sg; w.seg_end = sg + 8 * nb1; w.row_base = sg + 16 * nb1; w.bucket_start = sg + 24 * nb1 + 1; w.rec_bound = (uint64_t)8 * nb1 * c->op_cap;
+	} else { w.seg_beg = Bt.start1; w.seg_end = Bt.start1 + 1; w.row_base = Bt.row_base; w.bucket_start = Bt.start1; w.rec_bound = n_pos; }
+	w.slabs = op && Bt.cap2; w.queued = op_run; w.call = c->call_no; w.pos = n_pos; w.finalise = 1;
+	return enqueue_stage_b(c, b, Bt, Pt, w);
 }
 
 // A batch much larger than the filter's regions can take at full speed (list_cap k-mers with clear bits per region) is cut into
@@ -1399,7 +1419,7 @@ static void split_rule(const bfcg_ctx_t *c, uint64_t *from, uint64_t *target_max
 }
 static uint64_t split_limit(const bfcg_ctx_t *c)
 {
-	const uint64_t nfine = ((uint64_t)1 << c->P.F) >> c->log2n;
+	const uint64_t nf = nfine(c);
 	// positions; ~0.8 k-mers per position.  In the first batch of an empty filter every k-mer has clear bits, and a region's load varies by far
 	// more than sqrt(mean) -- its few dozen distinct genome k-mers come at coverage/4 copies each -- so the cut sits below list_cap on average:
 	// c2 at 1 048 576 reads per batch ran at 12.2 instead of 25 G k-mers/s with the cut at 1.15 (5 % of the regions on the slow path).
@@ -1409,19 +1429,19 @@ static uint64_t split_limit(const bfcg_ctx_t *c)
 	// Filter mode through k_bloom3fm: a batch costs a sweep over BOTH filters (c5: 2 x 2 x 16 GiB each way -- 17 ms at the rate the kernel draws, as
 	// much as the rest of its work on 8 M reads), while a region whose list overflows only takes its records in two rounds instead of one: the limit
 	// sits where a region's k-mers (0.66 per position at k = 51) about fill the list, not a third below it
-	if (c->P.b3fm) return (uint64_t)((double)nfine * (double)cap * 0.95 * 1.6);
-	return (uint64_t)((double)nfine * (double)cap * 0.95);
+	if (c->P.b3fm) return (uint64_t)((double)nf * (double)cap * 0.95 * 1.6);
+	return (uint64_t)((double)nf * (double)cap * 0.95);
 }
 static inline int is_acgt(uint8_t ch) { ch &= 0xDF; return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
 // last cut point in (lo, hi]: index just behind a non-ACGT byte, searched backwards from hi over at most 1 MiB; 0 = none
-static uint64_t find_cut(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t lo, uint64_t hi)
+static uint64_t find_cut(const uint8_t *seq, int on_device, uint64_t lo, uint64_t hi)
 {
 	const uint64_t win = hi - lo < (1u << 20) ? hi - lo : (1u << 20);
-	const uint8_t *p = h_seq ? h_seq + hi - win : 0;
+	const uint8_t *p = seq + hi - win;
 	uint8_t *tmp = 0;
-	if (!h_seq) {
+	if (on_device) {
 		tmp = (uint8_t *)malloc(win);
-		if (hipMemcpy(tmp, d_seq + hi - win, win, hipMemcpyDeviceToHost) != hipSuccess) { free(tmp); return 0; }
+		if (hipMemcpy(tmp, p, win, hipMemcpyDeviceToHost) != hipSuccess) { free(tmp); return 0; }
 		p = tmp;
 	}
 	uint64_t cut = 0;
@@ -1444,60 +1464,6 @@ extern "C" double bfcg_mg_warm_factor(bfcg_ctx_t *c)
 	return w < 1.0 ? 1.0 : w;
 }
 
-extern "C" int bfcg_count_batch_dev(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos)
-{
-	if (c->n_ranks > 1) return fail("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
-	if (n_pos == 0) return 0;
-	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	BFCG_CK(hipSetDevice(c->prm.device));
-	uint64_t from, lim;
-	split_rule(c, &from, &lim);
-	struct depth_guard { bfcg_ctx_t *c; depth_guard(bfcg_ctx_t *c_) : c(c_) { if (c->call_depth++ == 0) ++c->call_no; } ~depth_guard() { --c->call_depth; } } guard(c);
-	if (!c->B.seen_out && n_pos > from) { // oversized for this filter: equal sub-batches of at most `lim` positions
-		const uint64_t target = n_pos / ((n_pos + lim - 1) / lim) + 1;
-		uint64_t o = 0;
-		while (n_pos - o > target + target / 8) {
-			const uint64_t cut = find_cut(c, 0, d_seq, o, o + target);
-			if (cut == 0) break; // a megabase without a cut point: take the rest as it is
-			if (bfcg_count_batch_dev(c, d_seq + o, d_qual ? d_qual + o : 0, cut - o) != 0) return -1;
-			o = cut;
-		}
-		if (o) return o < n_pos ? bfcg_count_batch_dev(c, d_seq + o, d_qual ? d_qual + o : 0, n_pos - o) : 0;
-	}
-	int rc = enqueue_batch(c, d_seq, d_qual, n_pos, 0, 0);
-	if (rc == 0 && (c->B.seen_out || getenv("BFCG_SYNC_BATCHES"))) rc = drain(c); // debug aids want one batch at a time
-	return rc;
-}
-
-extern "C" int bfcg_count_batch_host(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos)
-{
-	if (c->n_ranks > 1) return fail("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
-	if (n_pos == 0) return 0;
-	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	BFCG_CK(hipSetDevice(c->prm.device));
-	uint64_t from, lim;
-	split_rule(c, &from, &lim);
-	struct depth_guard { bfcg_ctx_t *c; depth_guard(bfcg_ctx_t *c_) : c(c_) { if (c->call_depth++ == 0) ++c->call_no; } ~depth_guard() { --c->call_depth; } } guard(c);
-	if (!c->B.seen_out && n_pos > from) { // oversized for this filter: equal sub-batches of at most `lim` positions (see bfcg_count_batch_dev)
-		const uint64_t target = n_pos / ((n_pos + lim - 1) / lim) + 1;
-		uint64_t o = 0;
-		while (n_pos - o > target + target / 8) {
-			const uint64_t cut = find_cut(c, h_seq, 0, o, o + target);
-			if (cut == 0) break;
-			if (bfcg_count_batch_host(c, h_seq + o, h_qual ? h_qual + o : 0, cut - o) != 0) return -1;
-			o = cut;
-		}
-		if (o) return o < n_pos ? bfcg_count_batch_host(c, h_seq + o, h_qual ? h_qual + o : 0, n_pos - o) : 0;
-	}
-	const int b = c->cur;
-	BFCG_CK(hipMemcpyAsync(c->d_seq2[b], h_seq, n_pos, hipMemcpyHostToDevice, c->stA)); // ordered behind stage A of two batches ago (same stream)
-	if (h_qual) BFCG_CK(hipMemcpyAsync(c->d_qual2[b], h_qual, n_pos, hipMemcpyHostToDevice, c->stA));
-	BFCG_CK(hipEventRecord(c->evCopy, c->stA));
-	int rc = enqueue_batch(c, c->d_seq2[b], h_qual ? c->d_qual2[b] : NULL, n_pos, 1, 0);
-	BFCG_CK(hipEventSynchronize(c->evCopy)); // the caller may reuse its host buffers now
-	if (rc == 0 && (c->B.seen_out || getenv("BFCG_SYNC_BATCHES"))) rc = drain(c);
-	return rc;
-}
 
 
 // ---- batches that arrive as bit planes (include/bfc_gpu.h: bfcg_count_batch_planes) --------------------------------------------------
@@ -1552,43 +1518,78 @@ static uint64_t find_cut_planes(const uint32_t *np, uint64_t lo, uint64_t hi)
 	return 0;
 }
 
-extern "C" int bfcg_count_batch_planes(bfcg_ctx_t *c, const uint32_t *h_planes, uint64_t plane_words, uint64_t first_pos, uint64_t n_pos, int has_qual)
+// ---- the one door of a single GPU's batches -------------------------------------------------------------------------------------------------
+// Where a batch comes from: byte streams on the device or on the host (qual may be NULL), or bit planes on the host (planes != NULL: positions
+// [first_pos, ...) of 4 planes of plane_words words each).  The kinds differ in where a cut point is searched and in how positions [o, o + n)
+// get onto the device; everything else about a batch is count_batch's.
+struct BatchSrc { const uint8_t *seq, *qual; int on_device; const uint32_t *planes; uint64_t plane_words, first_pos; int has_qual; };
+
+static uint64_t src_find_cut(const BatchSrc &s, uint64_t lo, uint64_t hi)
+{
+	if (!s.planes) return find_cut(s.seq, s.on_device, lo, hi);
+	const uint64_t cut = find_cut_planes(s.planes + 2 * s.plane_words, s.first_pos + lo, s.first_pos + hi);
+	return cut ? cut - s.first_pos : 0;
+}
+// positions [o, o + n) as one batch: onto the device (stream stA, in the slot's staging buffers) where they are the host's, then enqueue_batch
+static int src_submit(bfcg_ctx_t *c, const BatchSrc &s, uint64_t o, uint64_t n)
+{
+	int rc;
+	if (s.on_device) rc = enqueue_batch(c, s.seq + o, s.qual ? s.qual + o : 0, n, 0, 0);
+	else {
+		const int b = c->cur, has_qual = s.planes ? s.has_qual : s.qual != 0;
+		if (s.planes) { // ordered behind stage A of two batches ago (same stream), as the byte streams below are
+			const uint64_t first = s.first_pos + o, w0 = first >> 5, nw = ((first + n + 31) >> 5) - w0 + 1; // (+ the word the expansion reads ahead: a spare one at the planes' end)
+			const uint64_t nw_c = w0 + nw <= s.plane_words ? nw : s.plane_words - w0;
+			for (int p = 0; p < (has_qual ? 4 : 3); ++p)
+				BFCG_CK(hipMemcpyAsync(c->d_planes[b] + (uint64_t)p * c->plane_cap, s.planes + (uint64_t)p * s.plane_words + w0, nw_c * sizeof(uint32_t), hipMemcpyHostToDevice, c->stA));
+			hipLaunchKernelGGL(k_expand_planes, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, c->stA, c->d_planes[b], c->plane_cap, (uint32_t)(first & 31), n, has_qual,
+			                   c->d_seq2[b], c->d_qual2[b]);
+		} else {
+			BFCG_CK(hipMemcpyAsync(c->d_seq2[b], s.seq + o, n, hipMemcpyHostToDevice, c->stA)); // ordered behind stage A of two batches ago (same stream)
+			if (has_qual) BFCG_CK(hipMemcpyAsync(c->d_qual2[b], s.qual + o, n, hipMemcpyHostToDevice, c->stA));
+		}
+		BFCG_CK(hipEventRecord(c->evCopy, c->stA)); // (behind the expansion: where the batches' kernels run on the other stream they wait for this)
+		rc = enqueue_batch(c, c->d_seq2[b], has_qual ? c->d_qual2[b] : NULL, n, 1, 0);
+		BFCG_CK(hipEventSynchronize(c->evCopy)); // the caller may reuse its host buffers now -- whatever enqueue_batch returned
+	}
+	if (rc == 0 && (c->B.seen_out || getenv("BFCG_SYNC_BATCHES"))) rc = drain(c); // debug aids want one batch at a time
+	return rc;
+}
+// Positions [o, o + n_pos) of a source.  An oversized batch is cut into equal sub-batches of at most `lim` positions, and each of them comes
+// through this door again: the rule is evaluated afresh for every remainder (the filter warms up between sub-batches), the call number advances
+// once per top-level call.
+static int count_batch(bfcg_ctx_t *c, const BatchSrc &s, uint64_t o, uint64_t n_pos)
 {
 	if (c->n_ranks > 1) return fail("this context is one of %d ranks: use bfcg_mg_scatter / bfcg_mg_process", c->n_ranks);
 	if (n_pos == 0) return 0;
-	if (n_pos > c->prm.max_batch_pos) return fail("batch of %llu positions exceeds max_batch_pos=%llu", (unsigned long long)n_pos, (unsigned long long)c->prm.max_batch_pos);
-	if ((first_pos + n_pos + 31) / 32 > plane_words) return fail("positions [%llu, %llu) lie outside planes of %llu words", (unsigned long long)first_pos, (unsigned long long)(first_pos + n_pos), (unsigned long long)plane_words);
+	if (batch_fits(c, n_pos) != 0) return -1;
+	if (s.planes && (s.first_pos + o + n_pos + 31) / 32 > s.plane_words) return fail("positions [%llu, %llu) lie outside planes of %llu words", (unsigned long long)(s.first_pos + o), (unsigned long long)(s.first_pos + o + n_pos), (unsigned long long)s.plane_words);
 	BFCG_CK(hipSetDevice(c->prm.device));
-	if (!c->d_planes[0]) { // (first batch of this kind)
+	if (s.planes && !c->d_planes[0]) { // (first batch of this kind)
 		c->plane_cap = c->prm.max_batch_pos / 32 + 4;
 		for (int b = 0; b < 2; ++b) BFCG_CK(hipMalloc(&c->d_planes[b], c->plane_cap * 4 * sizeof(uint32_t)));
 	}
 	uint64_t from, lim;
 	split_rule(c, &from, &lim);
 	struct depth_guard { bfcg_ctx_t *c; depth_guard(bfcg_ctx_t *c_) : c(c_) { if (c->call_depth++ == 0) ++c->call_no; } ~depth_guard() { --c->call_depth; } } guard(c);
-	if (!c->B.seen_out && n_pos > from) { // oversized for this filter: equal sub-batches of at most `lim` positions (see bfcg_count_batch_dev)
+	if (!c->B.seen_out && n_pos > from) {
 		const uint64_t target = n_pos / ((n_pos + lim - 1) / lim) + 1;
-		uint64_t o = 0;
-		while (n_pos - o > target + target / 8) {
-			const uint64_t cut = find_cut_planes(h_planes + 2 * plane_words, first_pos + o, first_pos + o + target);
-			if (cut == 0) break;
-			if (bfcg_count_batch_planes(c, h_planes, plane_words, first_pos + o, cut - (first_pos + o), has_qual) != 0) return -1;
-			o = cut - first_pos;
+		uint64_t done = 0;
+		while (n_pos - done > target + target / 8) {
+			const uint64_t cut = src_find_cut(s, o + done, o + done + target);
+			if (cut == 0) break; // a megabase without a cut point: take the rest as it is
+			if (count_batch(c, s, o + done, cut - (o + done)) != 0) return -1;
+			done = cut - o;
 		}
-		if (o) return o < n_pos ? bfcg_count_batch_planes(c, h_planes, plane_words, first_pos + o, n_pos - o, has_qual) : 0;
+		if (done) return done < n_pos ? count_batch(c, s, o + done, n_pos - done) : 0;
 	}
-	const int b = c->cur;
-	const uint64_t w0 = first_pos >> 5, nw = ((first_pos + n_pos + 31) >> 5) - w0 + 1; // (+ the word the expansion reads ahead: a spare one at the planes' end)
-	const uint64_t nw_c = w0 + nw <= plane_words ? nw : plane_words - w0;
-	for (int p = 0; p < (has_qual ? 4 : 3); ++p) // ordered behind stage A of two batches ago (same stream), as the byte streams of bfcg_count_batch_host are
-		BFCG_CK(hipMemcpyAsync(c->d_planes[b] + (uint64_t)p * c->plane_cap, h_planes + (uint64_t)p * plane_words + w0, nw_c * sizeof(uint32_t), hipMemcpyHostToDevice, c->stA));
-	hipLaunchKernelGGL(k_expand_planes, dim3((unsigned)((n_pos + 4095) / 4096)), dim3(256), 0, c->stA, c->d_planes[b], c->plane_cap, (uint32_t)(first_pos & 31), n_pos, has_qual,
-	                   c->d_seq2[b], c->d_qual2[b]);
-	BFCG_CK(hipEventRecord(c->evCopy, c->stA)); // (behind the expansion: where the batches' kernels run on the other stream they wait for this)
-	int rc = enqueue_batch(c, c->d_seq2[b], has_qual ? c->d_qual2[b] : NULL, n_pos, 1, 0);
-	BFCG_CK(hipEventSynchronize(c->evCopy)); // the caller may reuse its planes now
-	if (rc == 0 && (c->B.seen_out || getenv("BFCG_SYNC_BATCHES"))) rc = drain(c);
-	return rc;
+	return src_submit(c, s, o, n_pos);
+}
+extern "C" int bfcg_count_batch_dev(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos) { return count_batch(c, BatchSrc{d_seq, d_qual, 1, nullptr, 0, 0, 0}, 0, n_pos); }
+extern "C" int bfcg_count_batch_host(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos) { return count_batch(c, BatchSrc{h_seq, h_qual, 0, nullptr, 0, 0, 0}, 0, n_pos); }
+extern "C" int bfcg_count_batch_planes(bfcg_ctx_t *c, const uint32_t *h_planes, uint64_t plane_words, uint64_t first_pos, uint64_t n_pos, int has_qual)
+{
+	return count_batch(c, BatchSrc{nullptr, nullptr, 0, h_planes, plane_words, first_pos, has_qual}, 0, n_pos);
 }
 
 extern "C" void *bfcg_dev_alloc(bfcg_ctx_t *c, uint64_t bytes)

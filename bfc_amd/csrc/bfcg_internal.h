@@ -43,6 +43,7 @@ struct bfcg_kmers {
 };
 
 namespace bfcg {
+#define BFCG_LOCAL __attribute__((visibility("hidden"))) /* shared between the library's files, not exported from it */
 
 // statistics block in device memory (u64 counters)
 enum { ST_KMERS = 0, ST_HIGH, ST_SEEN, ST_KEYS, ST_TAB_OVF, ST_ERR_POOL, ST_SLOW_BUCKETS, ST_CROWDED /* regions whose aggregation table was full */, ST_N = 16 };
@@ -122,6 +123,7 @@ void run_batch(const KParams &P, const BatchBufs &B, const uint8_t *seq, const u
 int bloom_lds_bytes(const KParams &P);
 bool bloom3fm_geometry_ok(const KParams &P); // k_bloom3fm's conditions (16-byte records, k >= bf_shift + 9: block, h1, h2 are bits of y0; 4 hashes; regions of <= 256 blocks)
 bool bloom3_geometry_ok(const KParams &P); // k_bloom3's conditions (12-byte records whose bloom address is a bit field of their words, 4 hashes, regions of <= 256 blocks)
+BFCG_LOCAL bool scatter2_big_ok(const KParams &P); // k_scatter2's 8192-record tile can serve this geometry (12-byte records whose region is a bit field of their first word): KParams.l2_big is set nowhere else
 hipError_t set_bloom_lds_attr(const KParams &P);
 void run_query(const KParams &P, const uint8_t *seq, int64_t n_pos, const void *bloom, uint8_t *flags, hipStream_t st);
 void run_kcov(const KParams &P, const uint8_t *seq, int64_t n_pos, int min_occ, const void *tab, uint8_t *flags, uint16_t *out, hipStream_t st);
@@ -144,7 +146,6 @@ void run_table_rehash(const KParams &P, const unsigned long long *old_tab, int c
 
 // ---- the one error channel of the host files (bfcg_mg.hip's GHIP / grp_err mark a group failed instead and do not return)
 // the thread's message (bfcg_last_error) and the [E::bfcg] line on stderr; returns -1.  Defined in bfcg_ctx.hip.
-#define BFCG_LOCAL __attribute__((visibility("hidden"))) /* shared between the library's files, not exported from it */
 BFCG_LOCAL int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 // a HIP call in a function that returns int
 #define BFCG_CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return bfcg::fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)

@@ -2256,6 +2256,7 @@ bool bloom3fm_geometry_ok(const KParams &P)
 	       && P.R <= up && up >= 1 && up <= 31 && a >= up + 18 && io + 32 <= 128;
 }
 bool bloom3_geometry_ok(const KParams &P) { return bfcg_rec_dwords(P.k, P.rec_n) == 3 && P.n_hashes == 4 && P.R <= 8 && bloom_fast3(P); }
+bool scatter2_big_ok(const KParams &P) { return bfcg_rec_dwords(P.k, P.rec_n) == 3 && scatter2_fast(P); } // what run_level2_t asks before it takes KParams.l2_big's kernel
 
 // one workgroup per (region, block of its segment): one-dimensional `f * blocks + blk` -- a region's blocks back to back -- unless that
 // exceeds HIP's 2^32 threads per grid dimension (tiny test blocks on large filters), then regions x blocks

@@ -56,7 +56,7 @@ def _draw(seed, scale=1, b_range=(10, 28)):
     return dict(k=k, b=b, nh=nh, l_pre=l_pre, q=q, fm=fm), seq, qual, off, cuts, kw
 
 
-def _check(gpu_lib, prm, seq, qual, off, cuts, kw, planes=False):
+def _check(gpu_lib, prm, seq, qual, off, cuts, kw, planes=False, partition=None):
     n = len(off) - 1
     oc = oracle.Counter(prm["k"], prm["b"], q=prm["q"], n_hashes=prm["nh"], l_pre=prm["l_pre"], filter_mode=prm["fm"])
     oc.count(seq, qual, off)
@@ -84,6 +84,8 @@ def _check(gpu_lib, prm, seq, qual, off, cuts, kw, planes=False):
         osz, osl = oc.export()
         assert np.array_equal(sizes, osz) and np.array_equal(slots, osl), tag
     info = g.table_info() if not prm["fm"] else None
+    if partition is not None:
+        assert g.partition_info() == partition, tag
     g.close(); oc.close()
     return info
 
@@ -272,6 +274,33 @@ def test_random_configuration_uneven_level_split(gpu_lib, seed, f1, monkeypatch)
     if seed & 1:
         monkeypatch.setenv("BFCG_ONEPASS_MIN_TILES", "1")
     _check(gpu_lib, *_draw(47000 + seed, scale=8, b_range=(28, 34)))
+
+
+@pytest.mark.parametrize("k,no_fast_s2", [(17, 0), (31, 1)])
+def test_uneven_level_split_large_level2_tile_without_its_kernel(gpu_lib, k, no_fast_s2, monkeypatch):
+    """BFCG_L2_BIG asks for level 2 on tiles of 8192 records; only k_scatter2's fast variant has that tile (12-byte records whose region is a
+    bit field of their first word).  Where the launch takes another variant the batch must stay on tiles of 4096 in BOTH places -- the rows
+    k_seg_setup counts and the kernel that walks them -- or every row loses its second half without a word.  Two ways to be off the fast
+    variant: k = 17 < bf_shift - 9 (by geometry), and k = 31 with BFCG_NO_FAST_S2 (by switch).
+    The smallest shape where rows of 8192 and of 4096 differ: b = 28 with BFCG_F1 = 2 gives R = 8, F = 11, F2 = 9 (where BFCG_L2_BIG=1 applies),
+    4 level-1 buckets = 32 slabs; one batch of 4000 reads of 100 bases is 99 tiles of stage A, 12 or 13 per XCD, so a slab holds 8 000 to
+    11 000 records (capacity 14 200): two rows of 4096 and a part.  One-pass level 1 and 2 with no replay is asserted: a genome at 2x keeps a
+    region's share (mean 140 to 165 records, a k-mer's copies fall together) below its slab of 285."""
+    monkeypatch.setenv("BFCG_F1", "2")
+    monkeypatch.setenv("BFCG_ONEPASS_MIN_TILES", "1")
+    monkeypatch.setenv("BFCG_L2_BIG", "1")
+    if no_fast_s2:
+        monkeypatch.setenv("BFCG_NO_FAST_S2", "1")
+    rng = np.random.default_rng(47100 + k)
+    n, L, G = 4000, 100, 200000  # (if these or BFCG_F1 change: the test bites only while a level-1 slab holds MORE than 4096 records -- the assert below)
+    assert n * (L - k + 1) // 32 > 2 * 4096, "k-mers per slab (4 buckets x 8 XCDs) must exceed a tile of 4096 well"
+    genome = rng.integers(0, 4, G + L)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    off = np.arange(n + 1, dtype=np.uint64) * L
+    seq = np.concatenate([acgt[genome[p:p + L]] for p in rng.integers(0, G, n)]).astype(np.uint8)
+    qual = rng.integers(33, 75, len(seq)).astype(np.uint8)
+    _check(gpu_lib, dict(k=k, b=28, nh=4, l_pre=20, q=20, fm=0), seq, qual, off, [0, n], {},
+           partition=dict(one_pass=True, level2_one_pass=True, replayed_batches=0))
 
 
 @pytest.mark.parametrize("seed", range(8))
