@@ -82,13 +82,13 @@ struct bfcg_ctx {
 	// the batches behind it on the device; the host then replays them, in order, through the two-pass partition and stays there until the next reset.
 	int onepass_ok, onepass;     // the buffers exist / the current run still uses the one-pass partition
 	uint32_t *op_cursor[2], *op_seg[2], *op_flags, *h_flags[2];
-	int unfinished, unfinished_mg;     // bfcg_mg_process_slabs_dev has enqueued a stage B that bfcg_mg_process_finish has not seen yet (and its entry in the replay queue)
-	uint32_t *h_rows[2]; int rows_slot; // a group's slab mode without the host's wait: the host's copy of a stage A's rows (bfcg_mg_scatter_slabs_async), the slot of the last one
+	int unfinished, unfinished_mg;     // mg_process_slabs_dev has enqueued a stage B that mg_process_finish has not seen yet (and its entry in the replay queue)
+	uint32_t *h_rows[2]; int rows_slot; // a group's slab mode without the host's wait: the host's copy of a stage A's rows (mg_scatter_slabs_async), the slot of the last one
 	uint32_t op_cap; uint64_t op_min_pos;
 	uint32_t *cnt2; uint32_t cap2; uint64_t recs2_n; // one-pass level 2 (region slabs); records recs2 / stream_out hold
 	struct opq_t { const uint8_t *seq, *qual; uint64_t n_pos; int slot; const void *recv; int mg; } opq[4]; int n_opq; // batches enqueued one-pass and not yet known to be clean
 	int mg_op2_ok, mg_op2, mg_op2_allowed; uint32_t *mg_seg[4];  // a rank of a multi-GPU run: level 2 (its own stage B) in one pass; copies of the queued batches' segment sizes
-	int mg_slab_ok; int mg_seg_slab[4]; // ... level 1 in one pass into per-destination slabs (bfcg_mg_scatter_slabs); which queued copies are slab fills
+	int mg_slab_ok; int mg_seg_slab[4]; // ... level 1 in one pass into per-destination slabs (mg_scatter_slabs); which queued copies are slab fills
 	uint64_t n_replayed;
 	int reused;                  // a reset has followed counted batches: this context counts one data set after the other
 	int seg_no_grow;             // the next segment size does not fit (memory / LDS): grow only when a segment overflows or the load passes 85 %
@@ -343,7 +343,7 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 		const char *e = getenv("BFCG_ONEPASS");
 		c->mg_op2_ok = P.F2 > 0 && !(e && atoi(e) == 0); // (also the single rank of a group of one: bench.py with BFC_BENCH_FORCE_DIST, tests)
 	}
-	{ const char *e = getenv("BFCG_MG_SLABS"); c->mg_slab_ok = P.F2 > 0 && !(e && atoi(e) == 0); } // (a rank's level 1 in one pass: bfcg_mg_scatter_slabs; used by groups only)
+	{ const char *e = getenv("BFCG_MG_SLABS"); c->mg_slab_ok = P.F2 > 0 && !(e && atoi(e) == 0); } // (a rank's level 1 in one pass: mg_scatter_slabs; used by groups only)
 	if (c->onepass_ok || c->mg_slab_ok) {
 		for (int b = 0; b < 2; ++b) {
 			BFCG_CKN(bfcg_destroy(c), hipMalloc(&c->op_cursor[b], sizeof(uint32_t) * (8 * nb1 * 32 + 32))); // (+ the tile counter of k_scatter1)
@@ -478,7 +478,6 @@ static int batch_fits(const bfcg_ctx_t *c, uint64_t n_pos)
 
 static int drain(bfcg_ctx_t *c);
 static int replay_poisoned(bfcg_ctx_t *c);
-static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, uint32_t slab_cap, hipEvent_t *wait, int n_wait);
 static int enqueue_batch(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, int wait_copy, int no_kstats);
 static int ensure_agg(bfcg_ctx_t *c);
 static int same_block_offset(bfcg_ctx_t *c, int b, const uint8_t *d_seq, const uint8_t **d_qual, uint64_t n_pos, hipStream_t s);
@@ -659,13 +658,13 @@ static int replay_poisoned(bfcg_ctx_t *c)
 	if (fetch_stats(c) != 0) return -1;
 	c->n_batches -= (uint64_t)n; // the batches keep their places in the count (order stamps carry the batch number)
 	std::vector<uint32_t> seg;
-	for (int i = 0; i < n; ++i) if (q[i].mg) --c->call_no; // (bfcg_mg_process_ev numbers its calls itself)
+	for (int i = 0; i < n; ++i) if (q[i].mg) --c->call_no; // (mg_process numbers its calls itself)
 	for (int i = 0; i < n; ++i) {
 		if (q[i].mg) { // a rank's stage B: what it received is still in its receive buffer (the exchange of the next batch has not begun: this thread starts it)
 			const int slab = c->mg_seg_slab[q[i].mg - 1];
 			const size_t w = (size_t)c->n_ranks * (size_t)((1 << c->P.F1) >> c->log2n) * (slab ? 8 : 1);
 			seg.assign(c->mg_seg[q[i].mg - 1], c->mg_seg[q[i].mg - 1] + w);
-			if (mg_process_any(c, q[i].recv, seg.data(), slab ? c->op_cap : 0u, 0, 0) != 0) return -1;
+			if (mg_process(c, q[i].recv, seg.data(), slab ? c->op_cap : 0u, 0, 0) != 0) return -1;
 		} else if (enqueue_batch(c, q[i].seq, q[i].qual, q[i].n_pos, 0, 1) != 0) return -1;
 		if (drain(c) != 0) return -1;
 		++c->n_replayed;
@@ -1001,7 +1000,7 @@ extern "C" int bfcg_mg_info(bfcg_ctx_t *c, int out[4])
 static int mg_scatter2(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t *counts, int no_kstats);
 extern "C" int bfcg_mg_scatter(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t *counts) { return mg_scatter2(c, d_seq, d_qual, n_pos, d_send, counts, 0); }
 // (a batch whose one-pass stage A overflowed a slab, repeated: its k-mers were counted the first time)
-extern "C" int bfcg_mg_scatter_again(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t *counts) { return mg_scatter2(c, d_seq, d_qual, n_pos, d_send, counts, 1); }
+int bfcg::mg_scatter_again(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t *counts) { return mg_scatter2(c, d_seq, d_qual, n_pos, d_send, counts, 1); }
 // A group of ONE rank has no exchange for stage A of the next batch to run beside: its kernels follow stage B on the same stream wherever a
 // single GPU's do (c->pipeline: kernels sized to fill the chip fight for its CUs -- DESIGN.md section 6b, c3 on two streams).
 static inline hipStream_t mg_stage_a_stream(bfcg_ctx_t *c) { return c->n_ranks == 1 && !c->pipeline ? c->st : c->stA; }
@@ -1017,7 +1016,7 @@ static int mg_stage_a_begin(bfcg_ctx_t *c, int b, hipStream_t sA, const uint8_t 
 	}
 	return same_block_offset(c, b, d_seq, d_qual, n_pos, sA);
 }
-// the buffers of a one-pass stage A in slot b whose slabs are a group's (own_delta: see bfcg_mg_scatter_slabs)
+// the buffers of a one-pass stage A in slot b whose slabs are a group's (own_delta: see mg_scatter_slabs)
 static BatchBufs mg_slab_bufs(const bfcg_ctx_t *c, int b, uint32_t own_delta)
 {
 	const uint32_t nb_loc = (1u << c->P.F1) >> c->log2n;
@@ -1054,8 +1053,8 @@ static int mg_scatter2(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qua
 // send buffer, where this rank's block belongs -- no self-copy.  fills[8 * 2^F1]: records in every slab (bucket-major, XCD-minor), on the host
 // when the call returns; *overflow: a slab was too small (skewed input) -- nothing of this batch may be used, the group falls back to
 // bfcg_mg_scatter for it.  count_kmers = 0: a repeated stage A of a batch whose k-mers were counted already.
-extern "C" int bfcg_mg_slab_info(bfcg_ctx_t *c, uint32_t out[2]) { out[0] = c->op_cap; out[1] = (uint32_t)(c->mg_slab_ok && c->op_cursor[0] != 0); return 0; }
-extern "C" int bfcg_mg_scatter_slabs(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *fills, int *overflow)
+int bfcg::mg_slab_info(bfcg_ctx_t *c, uint32_t out[2]) { out[0] = c->op_cap; out[1] = (uint32_t)(c->mg_slab_ok && c->op_cursor[0] != 0); return 0; }
+int bfcg::mg_scatter_slabs(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *fills, int *overflow)
 {
 	const int nb1 = 1 << c->P.F1, b = c->cur;
 	const hipStream_t sA = mg_stage_a_stream(c);
@@ -1080,12 +1079,12 @@ extern "C" int bfcg_mg_scatter_slabs(bfcg_ctx_t *c, const uint8_t *d_seq, const 
 // The same stage A WITHOUT the host's wait (round 5: a group whose ranks are all in one process keeps the host out of the batch's loop).  The fills
 // stay on the device: k_pack_rows lays them out as one row per destination in d_rows_out (n_ranks rows of row_w = nb_loc x 8 + 2 words: the fills of
 // the destination's slabs, then this stage A's overflow flag), which the caller sends beside the blocks; a copy of the rows is on its way to the
-// host.  bfcg_mg_scatter_slabs_wait -- called when the exchange and the owner's stage B are already enqueued -- waits for that copy and hands
-// out what bfcg_mg_scatter_slabs would have.  *done: recorded on stage A's stream behind all of it (the exchange waits for it).
-extern "C" int bfcg_mg_row_words(bfcg_ctx_t *c) { return (((1 << c->P.F1) >> c->log2n) * 8) + 2; }
-extern "C" int bfcg_mg_scatter_slabs_async(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *d_rows_out, hipEvent_t *done)
+// host.  mg_scatter_slabs_wait -- called when the exchange and the owner's stage B are already enqueued -- waits for that copy and hands
+// out what mg_scatter_slabs would have.  *done: recorded on stage A's stream behind all of it (the exchange waits for it).
+int bfcg::mg_row_words(bfcg_ctx_t *c) { return (((1 << c->P.F1) >> c->log2n) * 8) + 2; }
+int bfcg::mg_scatter_slabs_async(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *d_rows_out, hipEvent_t *done)
 {
-	const int b = c->cur, row_w = bfcg_mg_row_words(c);
+	const int b = c->cur, row_w = mg_row_words(c);
 	const hipStream_t sA = mg_stage_a_stream(c);
 	if (!c->mg_slab_ok || !c->op_cursor[b] || !c->h_rows[b]) return fail("this context has no slab mode");
 	const int begun = mg_stage_a_begin(c, b, sA, d_seq, &d_qual, n_pos);
@@ -1104,8 +1103,8 @@ extern "C" int bfcg_mg_scatter_slabs_async(bfcg_ctx_t *c, const uint8_t *d_seq, 
 	*done = c->evA[b];
 	return 0;
 }
-// fills[8 * 2^F1] (bucket-major, XCD-minor, as bfcg_mg_scatter_slabs) and *overflow of the stage A enqueued last
-extern "C" int bfcg_mg_scatter_slabs_wait(bfcg_ctx_t *c, uint32_t *fills, int *overflow)
+// fills[8 * 2^F1] (bucket-major, XCD-minor, as mg_scatter_slabs) and *overflow of the stage A enqueued last
+int bfcg::mg_scatter_slabs_wait(bfcg_ctx_t *c, uint32_t *fills, int *overflow)
 {
 	const int nb1 = 1 << c->P.F1, nb_loc = nb1 >> c->log2n, b = c->rows_slot, row_w = nb_loc * 8 + 2;
 	BFCG_CK(hipSetDevice(c->prm.device));
@@ -1123,13 +1122,11 @@ extern "C" int bfcg_mg_scatter_slabs_wait(bfcg_ctx_t *c, uint32_t *fills, int *o
 // Stage B is ENQUEUED (stream st) and left running: the call returns once the PREVIOUS batch is finalised (statistics read,
 // table maintained), so the caller's next bfcg_mg_scatter and exchange overlap with it.  d_recv must stay untouched until the
 // next bfcg_mg_process (or bfcg_sync) returns: callers alternate between two receive buffers.
-// slab_cap != 0 (bfcg_mg_process_slabs): d_recv holds, source-major, every source's SLABS for the owned buckets (8 per bucket, slab_cap records
+// slab_cap != 0 (a group's slab mode): d_recv holds, source-major, every source's SLABS for the owned buckets (8 per bucket, slab_cap records
 // each, at fixed places) and seg_cnt[(s * nb_loc + b) * 8 + x] says how far each is filled.
-extern "C" int bfcg_mg_process_ev(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, hipEvent_t *wait, int n_wait) { return mg_process_any(c, d_recv, seg_cnt, 0u, wait, n_wait); }
-extern "C" int bfcg_mg_process(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt) { return mg_process_any(c, d_recv, seg_cnt, 0u, 0, 0); }
-extern "C" int bfcg_mg_process_slabs(bfcg_ctx_t *c, const void *d_recv, const uint32_t *fills, uint32_t slab_cap, hipEvent_t *wait, int n_wait) { return mg_process_any(c, d_recv, fills, slab_cap, wait, n_wait); }
+extern "C" int bfcg_mg_process(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt) { return mg_process(c, d_recv, seg_cnt, 0u, 0, 0); }
 // (stage B ordered behind `wait[0..n_wait)`: events of the exchange that fills d_recv, on other streams / devices -- no host wait)
-static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, uint32_t slab_cap, hipEvent_t *wait, int n_wait)
+int bfcg::mg_process(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, uint32_t slab_cap, hipEvent_t *wait, int n_wait)
 {
 	const int N = c->n_ranks, nb_loc = (1 << c->P.F1) >> c->log2n, spb = slab_cap ? N * 8 : N, n_seg = nb_loc * spb, b = c->cur;
 	BFCG_CK(hipSetDevice(c->prm.device));
@@ -1171,36 +1168,36 @@ static int mg_process_any(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg
 }
 
 // Stage B of a global batch whose sizes the host does not have yet (slab mode, all ranks in one process): d_rows_in holds every source's row for
-// this rank (n_ranks rows of bfcg_mg_row_words words, written by the exchange that `wait` orders this behind); k_seg_setup_mg turns them into the
+// this rank (n_ranks rows of mg_row_words words, written by the exchange that `wait` orders this behind); k_seg_setup_mg turns them into the
 // segment arrays on the device.  rec_bound: what the batch can hold at most (sizes the level-2 grid; surplus workgroups exit).  The batch is
-// enqueued and NOT finalised: bfcg_mg_process_finish does that once the caller has the sizes (the same call of the group, a moment later).
+// enqueued and NOT finalised: mg_process_finish does that once the caller has the sizes (the same call of the group, a moment later).
 // may this rank take batches that way?  A property of the context's parameters, not of its state (no order stamps, no per-position debug output):
 // the processes of a multi-process group must all answer alike.  (Level 2 in one pass or two: the slabs a source can fill -- nb1 x 8 x capacity
 // records -- are fewer than the level-2 buffers hold, so the bound sizes the grids and nothing can be overrun whatever the sizes turn out to be.)
-extern "C" int bfcg_mg_async_ok(bfcg_ctx_t *c) { return c->mg_slab_ok && !c->B.seen_out && !c->P.track && c->h_rows[0] != 0 && (c->n_ranks == 1 || (uint64_t)8 * (1u << c->P.F1) * c->op_cap <= c->recv_cap); } // (one rank: what it "receives" is its own batch, <= max_batch_pos = its capacity)
-// (only the sources [s_lo, s_hi) of the receive buffer: an overloaded owner applies the others in further passes, bfcg_mg_process_slabs with their sizes)
-extern "C" int bfcg_mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, const uint32_t *d_rows_in, uint32_t slab_cap, uint64_t rec_bound, int s_lo, int s_hi, hipEvent_t *wait, int n_wait)
+int bfcg::mg_async_ok(bfcg_ctx_t *c) { return c->mg_slab_ok && !c->B.seen_out && !c->P.track && c->h_rows[0] != 0 && (c->n_ranks == 1 || (uint64_t)8 * (1u << c->P.F1) * c->op_cap <= c->recv_cap); } // (one rank: what it "receives" is its own batch, <= max_batch_pos = its capacity)
+// (only the sources [s_lo, s_hi) of the receive buffer: an overloaded owner applies the others in further passes, mg_process with slabs with their sizes)
+int bfcg::mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, const uint32_t *d_rows_in, uint32_t slab_cap, uint64_t rec_bound, int s_lo, int s_hi, hipEvent_t *wait, int n_wait)
 {
 	const int N = c->n_ranks, nb_loc = (1 << c->P.F1) >> c->log2n, spb = N * 8, n_seg = nb_loc * spb, b = c->cur;
 	BFCG_CK(hipSetDevice(c->prm.device));
 	const size_t words = (size_t)3 * n_seg + 1 + nb_loc + 1;
 	if (words > c->seg_words) return fail("internal: %zu segment words, room for %zu", words, c->seg_words);
-	if (!slab_cap || !bfcg_mg_async_ok(c)) return fail("internal: bfcg_mg_process_slabs_dev needs slabs and no debug_seen");
+	if (!slab_cap || !mg_async_ok(c)) return fail("internal: mg_process_slabs_dev needs slabs and no debug_seen");
 	if (rec_bound > c->recv_cap) rec_bound = c->recv_cap;
 	uint32_t *d = c->d_seg + (size_t)b * c->seg_words;
 	for (int i = 0; i < n_wait; ++i) BFCG_CK(hipStreamWaitEvent(c->st, wait[i], 0));
 	BFCG_CK(hipEventRecord(c->evt[b][6], c->st));
 	run_seg_setup_mg(c->P, c->rw / 4, d_rows_in, (uint32_t)(nb_loc * 8 + 2), N, s_lo, s_hi, slab_cap, d, nullptr, c->st);
-	const int n_q = c->n_opq; // (a stage B pushes at most one entry, at the queue's end, and nothing is popped before bfcg_mg_process_finish: opq[n_q] is this batch's, if any)
-	if (mg_stage_b(c, b, d_recv, d, n_seg, spb, rec_bound, nullptr, 1, 0) != 0) return -1; // (the sizes follow, and with them the previous batch's end: bfcg_mg_process_finish)
+	const int n_q = c->n_opq; // (a stage B pushes at most one entry, at the queue's end, and nothing is popped before mg_process_finish: opq[n_q] is this batch's, if any)
+	if (mg_stage_b(c, b, d_recv, d, n_seg, spb, rec_bound, nullptr, 1, 0) != 0) return -1; // (the sizes follow, and with them the previous batch's end: mg_process_finish)
 	c->unfinished_mg = c->n_opq > n_q ? c->opq[n_q].mg : 0;
 	c->unfinished = 1;
 	return 0;
 }
 // ... and the sizes have arrived on the host: fills[(s * nb_loc + k) * 8 + x] = records from source s in the slab of (owned bucket k, XCD x) -- kept
 // for a replay of this stage B (a region's slab may turn out too small one call later) --, then the batch BEFORE this one is finalised as
-// bfcg_mg_process_slabs does.
-extern "C" int bfcg_mg_process_finish(bfcg_ctx_t *c, const uint32_t *fills)
+// mg_process with slabs does.
+int bfcg::mg_process_finish(bfcg_ctx_t *c, const uint32_t *fills)
 {
 	if (!c->unfinished) return fail("internal: no stage B waits for its sizes");
 	const int N = c->n_ranks, nb_loc = (1 << c->P.F1) >> c->log2n, b = c->cur;
@@ -1432,7 +1429,6 @@ static uint64_t split_limit(const bfcg_ctx_t *c)
 	if (c->P.b3fm) return (uint64_t)((double)nf * (double)cap * 0.95 * 1.6);
 	return (uint64_t)((double)nf * (double)cap * 0.95);
 }
-static inline int is_acgt(uint8_t ch) { ch &= 0xDF; return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
 // last cut point in (lo, hi]: index just behind a non-ACGT byte, searched backwards from hi over at most 1 MiB; 0 = none
 static uint64_t find_cut(const uint8_t *seq, int on_device, uint64_t lo, uint64_t hi)
 {
@@ -1454,8 +1450,8 @@ static uint64_t find_cut(const uint8_t *seq, int on_device, uint64_t lo, uint64_
 extern "C" uint64_t bfcg_batch_limit(bfcg_ctx_t *c) { return split_limit(c); }
 // A rank of a multi-GPU run: how many times the cold limit its regions take at full speed right now.  Into a filter that is still filling up
 // every received k-mer takes an entry of its region's LDS list (1.0); later only the unseen ones do -- the share the last stage B showed
-// (of RECORDS here: bfcg_mg_process_ev counts what it received) -- and the aim is 60 % of the list capacity, at most 3 x the cold limit.
-extern "C" double bfcg_mg_warm_factor(bfcg_ctx_t *c)
+// (of RECORDS here: mg_process counts what it received) -- and the aim is 60 % of the list capacity, at most 3 x the cold limit.
+double bfcg::mg_warm_factor(bfcg_ctx_t *c)
 {
 	if (c->cold || getenv("BFCG_NO_WARM_BATCHES")) return 1.0;
 	double unseen = 1.0 - c->seen_per_pos;

@@ -1,5 +1,5 @@
-// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip):
-// kernel parameters and launchers, the one error channel, the resident registry, what the satellites borrow from a context
+// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_mg.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip):
+// kernel parameters and launchers, the one error channel, the resident registry, what the satellites and the group layer borrow from a context
 #pragma once
 #include <hip/hip_runtime.h>
 #define BFCG_TILE1 4096
@@ -24,6 +24,11 @@ static constexpr int bfcg_tile1_of_rw(int rw) { return rw == 3 ? 4096 : 3072; }
 #endif
 #include <stdint.h>
 struct bfcg_ctx; struct bfcg_kcov; /* include/bfc_gpu.h: bfcg_ctx_t, bfcg_kcov_t */
+
+/* exported from the library without being part of include/bfc_gpu.h: the one declaration of each */
+extern "C" void bfcg_set_error(const char *msg); /* bfcg_ctx.hip: a message into the error channel below (bfcg_mg.hip; bfc_host.c declares it weak for itself) */
+extern "C" void *bfcg_bloom_slice(struct bfcg_ctx *c, int which, uint64_t *bytes); /* bfcg_ctx.hip: a rank's part of a filter where it lies, in device memory */
+extern "C" int bfcg_resident_register(const void *bf, void *dev, int device, int n_shift); /* bfcg_query.hip: a full device copy behind a host filter */
 
 /* the table read-out's object (include/bfc_gpu.h: bfcg_kmers_t): made and destroyed in bfcg_kmers.hip, which lists the table; bfcg_lookup.hip probes it,
    bfcg_readstats.hip reduces a profile per read */
@@ -116,7 +121,7 @@ void run_stage_a_onepass(const KParams &P, const BatchBufs &B, const uint8_t *se
 void run_stage_b(const KParams &P, const BatchBufs &B, const uint64_t *in1, const uint32_t *seg_beg, const uint32_t *seg_end, int n_seg, int segs_per_bucket,
                  const uint32_t *row_base, const uint32_t *bucket_start, uint64_t n_rec_bound, hipStream_t st, hipEvent_t *ev);
 // a rank of a group, slab mode without the host's sizes: the fills of stage A's slabs as one row per destination (behind run_stage_a_onepass, same stream);
-// the owner's segment arrays (seg_beg | seg_end | row_base | bucket_start, as mg_process_any lays them out) from all sources' rows
+// the owner's segment arrays (seg_beg | seg_end | row_base | bucket_start, as mg_process lays them out) from all sources' rows
 void run_pack_rows(const KParams &P, const BatchBufs &B, int n_ranks, uint32_t row_w, uint32_t *rows, hipStream_t st);
 void run_seg_setup_mg(const KParams &P, int rw_dwords, const uint32_t *rows, uint32_t row_w, int n_ranks, int s_lo, int s_hi, uint32_t cap, uint32_t *seg, unsigned long long *total, hipStream_t st);
 void run_batch(const KParams &P, const BatchBufs &B, const uint8_t *seq, const uint8_t *qual, int64_t n_pos, hipStream_t st, hipEvent_t *ev);
@@ -154,6 +159,9 @@ BFCG_LOCAL int fail(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 // report it as its own --, the creator returns NULL
 #define BFCG_CKN(cleanup, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { bfcg::fail("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); cleanup; (void)hipGetLastError(); return NULL; } } while (0)
 
+// a base, in either case (every other byte ends the k-mers that reach it)
+static inline int is_acgt(uint8_t ch) { ch &= 0xDF; return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
+
 // ---- device copies left in HBM behind host filters and tables (bfcg_query.hip): k == 0 marks a filter's entry (n_shift says which), a table's carries k, l_pre, cshift
 struct resident_t { const void *host; void *dev; int device, n_shift, k, l_pre, cshift; };
 BFCG_LOCAL int resident_put(const resident_t &r); // -1: the registry is full (the caller keeps r.dev)
@@ -163,6 +171,18 @@ BFCG_LOCAL void *resident_take(const void *host, int device, int n_shift, int k,
 // a counting context's table (bfcg_ctx.hip): drained, in the host's layout, not exported; k of a table-mode context, -1 for a filter-mode one
 const unsigned long long *ctx_borrow_table(::bfcg_ctx *c, KParams *P, int *device);
 int ctx_table_k(::bfcg_ctx *c);
+// What the group layer (bfcg_mg.hip) drives a rank's context with beside the public bfcg_mg_info / _scatter / _process: all in bfcg_ctx.hip, where each is described
+BFCG_LOCAL int mg_scatter_again(::bfcg_ctx *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t *counts);
+BFCG_LOCAL int mg_slab_info(::bfcg_ctx *c, uint32_t out[2]); // slab capacity; slab mode possible
+BFCG_LOCAL int mg_scatter_slabs(::bfcg_ctx *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *fills, int *overflow);
+BFCG_LOCAL int mg_row_words(::bfcg_ctx *c);
+BFCG_LOCAL int mg_async_ok(::bfcg_ctx *c);
+BFCG_LOCAL int mg_scatter_slabs_async(::bfcg_ctx *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *d_rows_out, hipEvent_t *done);
+BFCG_LOCAL int mg_scatter_slabs_wait(::bfcg_ctx *c, uint32_t *fills, int *overflow);
+BFCG_LOCAL int mg_process(::bfcg_ctx *c, const void *d_recv, const uint32_t *sizes, uint32_t slab_cap, hipEvent_t *wait, int n_wait); // slab_cap == 0: exact buckets
+BFCG_LOCAL int mg_process_slabs_dev(::bfcg_ctx *c, const void *d_recv, const uint32_t *d_rows_in, uint32_t slab_cap, uint64_t rec_bound, int s_lo, int s_hi, hipEvent_t *wait, int n_wait);
+BFCG_LOCAL int mg_process_finish(::bfcg_ctx *c, const uint32_t *fills);
+BFCG_LOCAL double mg_warm_factor(::bfcg_ctx *c); // times the cold limit this rank's regions take at full speed right now
 // a coverage pass's table, probe parameters and device, for the corrector behind it (bfcg_query.hip)
 const unsigned long long *kcov_table(::bfcg_kcov *t, KParams *P, int *device);
 int kcov_adopted(::bfcg_kcov *t);

@@ -25,22 +25,7 @@
 #include "bfcg_internal.h"
 #include "bfc_host.h"
 
-extern "C" int bfcg_mg_process_ev(bfcg_ctx_t *c, const void *d_recv, const uint32_t *seg_cnt, hipEvent_t *wait, int n_wait);
-extern "C" int bfcg_mg_process_slabs(bfcg_ctx_t *c, const void *d_recv, const uint32_t *fills, uint32_t slab_cap, hipEvent_t *wait, int n_wait);
-extern "C" int bfcg_mg_slab_info(bfcg_ctx_t *c, uint32_t out[2]);
-extern "C" int bfcg_mg_scatter_slabs(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *fills, int *overflow);
-extern "C" int bfcg_mg_scatter_again(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t *counts);
-extern "C" int bfcg_mg_row_words(bfcg_ctx_t *c);
-extern "C" int bfcg_mg_async_ok(bfcg_ctx_t *c);
-extern "C" int bfcg_mg_scatter_slabs_async(bfcg_ctx_t *c, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n_pos, void *d_send, uint32_t own_delta, uint32_t *d_rows_out, hipEvent_t *done);
-extern "C" int bfcg_mg_scatter_slabs_wait(bfcg_ctx_t *c, uint32_t *fills, int *overflow);
-extern "C" int bfcg_mg_process_slabs_dev(bfcg_ctx_t *c, const void *d_recv, const uint32_t *d_rows_in, uint32_t slab_cap, uint64_t rec_bound, int s_lo, int s_hi, hipEvent_t *wait, int n_wait);
-extern "C" int bfcg_mg_process_finish(bfcg_ctx_t *c, const uint32_t *fills);
-extern "C" void bfcg_set_error(const char *msg);
-extern "C" double bfcg_mg_warm_factor(bfcg_ctx_t *c);
-extern "C" void bfcg_mg_allow_onepass(bfcg_ctx_t *c, int on);
-extern "C" int bfcg_resident_register(const void *bf, void *dev, int device, int n_shift);
-extern "C" void *bfcg_bloom_slice(bfcg_ctx_t *c, int which, uint64_t *bytes);
+using namespace bfcg;
 
 namespace {
 
@@ -98,13 +83,14 @@ struct rank_t {
 	uint32_t *counts;          // this rank's level-1 bucket sizes of the current batch (host) + one word: this rank's group has failed
 	uint32_t *d_counts;        // multi-process: all ranks' rows, device side of the all-gather
 	uint32_t *d_rows_out[2], *d_rows_in[2]; // slab mode, all ranks in this process: the fills of stage A's slabs as one row per destination (device), and every
-	                           // source's row for this rank -- they travel beside the blocks, the owner's stage B reads them on the device (rank_batch: `lazy`)
+	                           // source's row for this rank -- they travel beside the blocks, the owner's stage B reads them on the device (lazy_batch)
 	unsigned long long *d_moved; // PUSH: bytes k_push_slabs has written to peers (device counter, read at bfcg_group_exchange_bytes)
 	uint64_t batch_call[64];   // the context's call number after stage B of global batch t (t & 63): bfcg_group_progress
 	ncclComm_t comm;
 	uint8_t *d_seq, *d_qual; uint64_t in_cap; // staging of host batches
 	// the current batch's share
 	const uint8_t *in_seq, *in_qual; uint64_t in_pos; int in_host;
+	bfcg_group_t *grp;        // the group this rank belongs to (what its thread starts from)
 	pthread_t th;
 	int rc;
 };
@@ -137,7 +123,6 @@ struct bfcg_group {
 	char err[512];
 };
 
-static int drain_exchange(bfcg_group_t *g);
 static void grp_err(bfcg_group_t *g, const char *fmt, ...)
 {
 	pthread_mutex_lock(&g->mu);
@@ -151,54 +136,27 @@ static void grp_err(bfcg_group_t *g, const char *fmt, ...)
 #define GHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) grp_err(g, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 #define GNCCL(call) do { ncclResult_t e_ = (call); if (e_ != ncclSuccess) grp_err(g, "%s failed: %s (%s:%d)", #call, ncclGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
-// stage B of one global batch on the owner.  When the rank received more k-mers than its bloom regions take at full speed the sources are
+// stage B of one global batch on the owner.  `sizes`: `per` words per source -- its records for each owned bucket, or, with slab_cap != 0, the fills
+// of its 8 slabs per owned bucket.  When the rank received more k-mers than its bloom regions take at full speed the sources are
 // processed in consecutive groups, each its own stage B: the receive buffer is source-major and the global order rank-major, so a group's
 // records all precede the next group's -- the result is that of one big batch without every region overflowing its LDS list.  Not with
 // order stamps (the batch number is part of a stamp and must agree across ranks).
-static int process_in_groups(bfcg_group_t *g, rank_t &R, const uint8_t *recv, const uint32_t *seg_cnt, hipEvent_t *wait, int n_wait)
+// Exact buckets (slab_cap == 0): a group's records begin where the sources before it end.  Slabs: every source's slabs sit at fixed places, so a
+// group of sources is simply the fills of the others set to zero.
+// (s_begin, launched0: the sources before s_begin went through launched0 passes already -- the lazy protocol's first group, lazy_batch)
+static int process_in_groups(bfcg_group_t *g, rank_t &R, const uint8_t *recv, const uint32_t *sizes, size_t per, uint32_t slab_cap, hipEvent_t *wait, int n_wait, int s_begin = 0, int launched0 = 0)
 {
-	const int N = g->n_ranks, nb_loc = g->nb_loc;
+	const int N = g->n_ranks;
 	std::vector<uint64_t> per_src((size_t)N, 0);
-	uint64_t total = 0;
-	for (int s = 0; s < N; ++s) { for (int k = 0; k < nb_loc; ++k) per_src[s] += seg_cnt[(size_t)s * nb_loc + k]; total += per_src[s]; }
+	uint64_t total = 0, off = 0;
+	for (int s = 0; s < N; ++s) {
+		for (size_t k = 0; k < per; ++k) per_src[s] += sizes[(size_t)s * per + k];
+		if (s < s_begin) off += per_src[s]; else total += per_src[s];
+	}
 	// (the limit follows the filter's fill, as a single GPU's batch cuts do: once most k-mers are seen again a region takes ~3 x as many per pass,
 	// and every pass streams the rank's share of the filter and of the table segments)
-	const uint64_t limit = (uint64_t)((double)g->kmer_limit * bfcg_mg_warm_factor(R.ctx));
-	if (g->prm.track_order || total <= limit || N == 1) return bfcg_mg_process_ev(R.ctx, recv, seg_cnt, wait, n_wait);
-	std::vector<uint32_t> seg((size_t)N * nb_loc);
-	uint64_t off = 0;
-	int s0 = 0, launched = 0;
-	while (s0 < N) {
-		uint64_t acc = per_src[s0]; int s1 = s0 + 1;
-		while (s1 < N && acc + per_src[s1] <= limit) acc += per_src[s1++];
-		if (acc) {
-			memset(seg.data(), 0, seg.size() * sizeof(uint32_t));
-			memcpy(&seg[(size_t)s0 * nb_loc], &seg_cnt[(size_t)s0 * nb_loc], sizeof(uint32_t) * (size_t)(s1 - s0) * nb_loc);
-			if (launched) { // stage A and stage B come in pairs (buffer sets, timing events): an empty stage A opens the next pair
-				std::vector<uint32_t> dummy((size_t)g->nb1);
-				if (bfcg_mg_scatter(R.ctx, 0, 0, 0, 0, dummy.data()) != 0) return -1;
-			}
-			if (bfcg_mg_process_ev(R.ctx, recv + off * (uint64_t)g->rec_bytes, seg.data(), launched ? 0 : wait, launched ? 0 : n_wait) != 0) return -1;
-			++launched;
-		}
-		for (int s = s0; s < s1; ++s) off += per_src[s];
-		s0 = s1;
-	}
-	if (!launched) return bfcg_mg_process_ev(R.ctx, recv, seg_cnt, wait, n_wait);
-	return 0;
-}
-
-// the same in slab mode: every source's slabs sit at fixed places, so a group of sources is simply the fills of the others set to zero
-// (s_begin, launched0: the sources before s_begin went through launched0 passes already -- the lazy protocol's first group, rank_batch)
-static int process_in_groups_slabs(bfcg_group_t *g, rank_t &R, const uint8_t *recv, const uint32_t *fills, hipEvent_t *wait, int n_wait, int s_begin = 0, int launched0 = 0)
-{
-	const int N = g->n_ranks, nb_loc = g->nb_loc;
-	const size_t per = (size_t)nb_loc * 8;
-	std::vector<uint64_t> per_src((size_t)N, 0);
-	uint64_t total = 0;
-	for (int s = s_begin; s < N; ++s) { for (size_t k = 0; k < per; ++k) per_src[s] += fills[(size_t)s * per + k]; total += per_src[s]; }
-	const uint64_t limit = (uint64_t)((double)g->kmer_limit * bfcg_mg_warm_factor(R.ctx));
-	if (!launched0 && (g->prm.track_order || total <= limit || N == 1)) return bfcg_mg_process_slabs(R.ctx, recv, fills, g->slab_cap, wait, n_wait);
+	const uint64_t limit = (uint64_t)((double)g->kmer_limit * mg_warm_factor(R.ctx));
+	if (!launched0 && (g->prm.track_order || total <= limit || N == 1)) return mg_process(R.ctx, recv, sizes, slab_cap, wait, n_wait);
 	std::vector<uint32_t> seg((size_t)N * per);
 	int s0 = s_begin, launched = launched0;
 	while (s0 < N) {
@@ -206,18 +164,18 @@ static int process_in_groups_slabs(bfcg_group_t *g, rank_t &R, const uint8_t *re
 		while (s1 < N && acc + per_src[s1] <= limit) acc += per_src[s1++];
 		if (acc) {
 			memset(seg.data(), 0, seg.size() * sizeof(uint32_t));
-			memcpy(&seg[(size_t)s0 * per], &fills[(size_t)s0 * per], sizeof(uint32_t) * (size_t)(s1 - s0) * per);
+			memcpy(&seg[(size_t)s0 * per], &sizes[(size_t)s0 * per], sizeof(uint32_t) * (size_t)(s1 - s0) * per);
 			if (launched) { // stage A and stage B come in pairs (buffer sets, timing events): an empty stage A opens the next pair
 				std::vector<uint32_t> dummy((size_t)g->nb1);
 				if (bfcg_mg_scatter(R.ctx, 0, 0, 0, 0, dummy.data()) != 0) return -1;
 			}
-			if (bfcg_mg_process_slabs(R.ctx, recv, seg.data(), g->slab_cap, launched ? 0 : wait, launched ? 0 : n_wait) != 0) return -1;
+			if (mg_process(R.ctx, recv + (slab_cap ? 0 : off * (uint64_t)g->rec_bytes), seg.data(), slab_cap, launched ? 0 : wait, launched ? 0 : n_wait) != 0) return -1;
 			++launched;
 		}
+		off += acc;
 		s0 = s1;
 	}
-	if (!launched) return bfcg_mg_process_slabs(R.ctx, recv, fills, g->slab_cap, wait, n_wait);
-	return 0;
+	return 0; // (launched >= 1: more than the limit means some source sent something)
 }
 // The lazy protocol's first group of sources: [0, s1) with s1 the most sources whose BOUND fits what this rank's regions take at full speed -- a source
 // sends an owner at most its share's positions / N (k-mers <= positions; the hash spreads them evenly: + 5 %).  `pos[s]`: the shares' positions
@@ -229,7 +187,7 @@ static int lazy_first_group(bfcg_group_t *g, rank_t &R)
 {
 	const int N = g->n_ranks;
 	if (N == 1 || g->prm.track_order) return N;
-	const uint64_t limit = (uint64_t)((double)g->kmer_limit * bfcg_mg_warm_factor(R.ctx));
+	const uint64_t limit = (uint64_t)((double)g->kmer_limit * mg_warm_factor(R.ctx));
 	uint64_t acc = 0;
 	int s1 = 0;
 	for (int s = 0; s < N; ++s) {
@@ -240,195 +198,254 @@ static int lazy_first_group(bfcg_group_t *g, rank_t &R)
 	return s1;
 }
 
-// every rank's row of sizes: shared memory between the local ranks, an all-gather over RCCL between processes
-static void publish_sizes(bfcg_group_t *g, rank_t &R)
+// One rank per process: my n words -> every rank's n words on the host (out[n_ranks x n]), all-gathered over R.comm on the stream R.xs through
+// R.d_counts (n_ranks x row_words words: free between batches; in place, rank p's words at p x n).  Returns NULL, or what failed.
+static const char *all_gather_words(bfcg_group_t *g, rank_t &R, const uint32_t *mine, size_t n, uint32_t *out)
+{
+	uint32_t *const at = R.d_counts + (size_t)R.rank * n;
+	ncclResult_t ne = ncclSuccess;
+	hipError_t he = hipSetDevice(R.device);
+	if (he == hipSuccess) he = hipMemcpyAsync(at, mine, sizeof(uint32_t) * n, hipMemcpyHostToDevice, R.xs);
+	if (he == hipSuccess) ne = ncclAllGather(at, R.d_counts, n, ncclUint32, R.comm, R.xs);
+	if (he == hipSuccess && ne == ncclSuccess) he = hipMemcpyAsync(out, R.d_counts, sizeof(uint32_t) * (size_t)g->n_ranks * n, hipMemcpyDeviceToHost, R.xs);
+	if (he == hipSuccess && ne == ncclSuccess) he = hipStreamSynchronize(R.xs);
+	return he != hipSuccess ? hipGetErrorString(he) : ne != ncclSuccess ? ncclGetErrorString(ne) : NULL;
+}
+
+// ---- what the steps of a batch share.  A rank's row in all_counts: its sizes, then (row_words - 2) its failure word, (row_words - 1) a slab of its stage A overflowed
+
+// This rank's row goes out (a rank whose stage A failed publishes no sizes): shared memory between the local ranks, an all-gather over RCCL between
+// processes.  Every local rank's row is in when this returns; it says whether a slab of any rank's stage A overflowed (every rank of the run reads the same rows).
+// The failure word travels with the sizes: g->failed is local to a process, and a rank that skipped the exchange while its peers posted
+// ncclSend / ncclRecv for it would leave them blocked for good.  A group that has failed keeps taking part in this all-gather (and only in it),
+// so that every process of the run takes the same decision in the same batch.
+static int publish_row(bfcg_group_t *g, rank_t &R, int ok, int ovf)
 {
 	const int N = g->n_ranks, me = R.rank;
 	const size_t cs = g->row_words;
+	if (!ok) memset(R.counts, 0, sizeof(uint32_t) * cs);
+	R.counts[cs - 1] = ok && ovf ? 1u : 0u;
+	R.counts[cs - 2] = g->failed ? 1u : 0u;
 	memcpy(g->all_counts + (size_t)me * cs, R.counts, sizeof(uint32_t) * cs);
-	if (g->mp) { // between processes: all-gather over RCCL (the local ranks of a multi-process group are one per process)
-		ncclResult_t ne = ncclSuccess;
-		hipError_t he = hipMemcpyAsync(R.d_counts + (size_t)me * cs, R.counts, sizeof(uint32_t) * cs, hipMemcpyHostToDevice, R.xs);
-		if (he == hipSuccess) ne = ncclAllGather(R.d_counts + (size_t)me * cs, R.d_counts, cs, ncclUint32, R.comm, R.xs);
-		if (he == hipSuccess && ne == ncclSuccess) he = hipMemcpyAsync(g->all_counts, R.d_counts, sizeof(uint32_t) * (size_t)N * cs, hipMemcpyDeviceToHost, R.xs);
-		if (he == hipSuccess && ne == ncclSuccess) he = hipStreamSynchronize(R.xs);
-		if (he != hipSuccess || ne != ncclSuccess) grp_err(g, "all-gather of the bucket sizes failed: %s", he != hipSuccess ? hipGetErrorString(he) : ncclGetErrorString(ne));
+	if (g->mp) { // (the local ranks of a multi-process group are one per process)
+		const char *why = all_gather_words(g, R, R.counts, cs, g->all_counts);
+		if (why) grp_err(g, "all-gather of the bucket sizes failed: %s", why);
 		else for (int p = 0; p < N; ++p) if (p != me && g->all_counts[(size_t)p * cs + cs - 2]) grp_err(g, "rank %d of the run has failed: this batch is not exchanged", p);
+	}
+	pthread_barrier_wait(&g->bar); // all local ranks have published their sizes
+	int any = 0;
+	for (int p = 0; p < N; ++p) any |= g->all_counts[(size_t)p * cs + cs - 1] != 0;
+	return any;
+}
+// this owner's sizes from every source's row: `per` words per source (its nb_loc buckets; x 8 slabs each in slab mode)
+static std::vector<uint32_t> owner_sizes(const bfcg_group_t *g, const rank_t &R, size_t per)
+{
+	std::vector<uint32_t> seg((size_t)g->n_ranks * per);
+	for (int s = 0; s < g->n_ranks; ++s) memcpy(&seg[(size_t)s * per], &g->all_counts[(size_t)s * g->row_words + (size_t)R.rank * per], sizeof(uint32_t) * per);
+	return seg;
+}
+// the events a stage B waits for: this rank's receives with RCCL; with peer copies every local rank's outgoing copies (they write into this rank's buffer)
+static std::vector<hipEvent_t> exchange_events(bfcg_group_t *g, rank_t &R)
+{
+	std::vector<hipEvent_t> ev;
+	if (g->xp == XP_RCCL) ev.push_back(R.ev_x);
+	else for (int j = 0; j < g->n_local; ++j) ev.push_back(g->r[j].ev_x);
+	return ev;
+}
+
+// ---- One global batch on a local rank (on the rank's own host thread), step by step: rank_batch, below the steps.  Buffers [t & 1]: send buffer,
+// receive buffer and rows alternate.  Every local rank passes the same barriers on a given path whether or not it has itself failed -- a failing call
+// marks the group (GHIP, grp_err) and the rank walks on.  Barriers per path (peer copies or push / RCCL, which has no "events" barrier in sized_exchange):
+//     lazy, clean                5      lazy_batch: stage A | events | sizes | rows read;  rank_batch: end
+//     lazy, a slab overflowed    8 / 7  the same 4;  fall_back: sizes;  sized_exchange: go | [events];  rank_batch: end
+//     sized slabs, clean         5 / 4  sized_stage_a: sizes;  rank_batch: rows read;  sized_exchange: go | [events];  rank_batch: end
+//     sized slabs, overflow      6 / 5  ... and fall_back: sizes, behind "rows read"
+//     two passes                 4 / 3  sized_stage_a: sizes;  sized_exchange: go | [events];  rank_batch: end
+
+// The lazy exchange on the stream R.xs: this rank's block of slabs (whole: the host knows no fill) and its row of rw words for every other rank, one of three ways.
+// RCCL -- between processes too: grouped sends and receives, ring-shifted peer order
+static void lazy_post_rccl(bfcg_group_t *g, rank_t &R, size_t rw)
+{
+	const int N = g->n_ranks, me = R.rank, b = (int)(g->t & 1);
+	uint8_t *const send = R.send2[b], *const recv = R.recv[b];
+	const uint64_t nbytes = g->blk * (uint64_t)g->rec_bytes;
+	if (N > 1) GNCCL(ncclGroupStart());
+	for (int step = 1; step < N; ++step) {
+		const int to = (me + step) % N, from = (me - step + N) % N;
+		for (uint64_t c0 = 0; c0 < nbytes; c0 += MSG_BYTES) {
+			GNCCL(ncclSend(send + (uint64_t)to * nbytes + c0, (size_t)(nbytes - c0 < MSG_BYTES ? nbytes - c0 : MSG_BYTES), ncclUint8, to, R.comm, R.xs));
+			GNCCL(ncclRecv(recv + (uint64_t)from * nbytes + c0, (size_t)(nbytes - c0 < MSG_BYTES ? nbytes - c0 : MSG_BYTES), ncclUint8, from, R.comm, R.xs));
+		}
+		GNCCL(ncclSend(R.d_rows_out[b] + (size_t)to * rw, rw, ncclUint32, to, R.comm, R.xs));
+		GNCCL(ncclRecv(R.d_rows_in[b] + (size_t)from * rw, rw, ncclUint32, from, R.comm, R.xs));
+	}
+	if (N > 1) GNCCL(ncclGroupEnd());
+}
+// the push kernel (all ranks local, N > 1): the filled part of every slab and the rows, straight into the owners' memory
+static void lazy_post_push(bfcg_group_t *g, rank_t &R, size_t rw)
+{
+	const int N = g->n_ranks, b = (int)(g->t & 1);
+	PushDst D = {};
+	for (int p = 0; p < N; ++p) { const rank_t &T = g->r[p - g->first]; D.recv[p] = T.recv[b]; D.rows[p] = T.d_rows_in[b]; }
+	const uint32_t per = (uint32_t)g->nb_loc * 8u;
+	unsigned wgs = g->push_wgs;
+	if (wgs > (unsigned)(N - 1) * per) wgs = (unsigned)(N - 1) * per;
+	if (wgs < (unsigned)(N - 1)) wgs = (unsigned)(N - 1);
+	hipLaunchKernelGGL(k_push_slabs, dim3(wgs), dim3(256), 0, R.xs, (const uint8_t *)R.send2[b], (const uint32_t *)R.d_rows_out[b], D, N, R.rank, per, g->slab_cap, (uint32_t)g->rec_bytes, (uint32_t)rw, R.d_moved);
+	GHIP(hipGetLastError());
+}
+// peer copies (all ranks local): whole blocks, and the rows beside them
+static void lazy_post_peer(bfcg_group_t *g, rank_t &R, size_t rw)
+{
+	const int N = g->n_ranks, me = R.rank, b = (int)(g->t & 1);
+	const uint64_t nbytes = g->blk * (uint64_t)g->rec_bytes;
+	for (int step = 1; step < N; ++step) {
+		const int to = (me + step) % N;
+		const rank_t &T = g->r[to - g->first];
+		GHIP(hipMemcpyPeerAsync(T.recv[b] + (uint64_t)me * nbytes, T.device, R.send2[b] + (uint64_t)to * nbytes, R.device, nbytes, R.xs));
+		GHIP(hipMemcpyPeerAsync(T.d_rows_in[b] + (size_t)me * rw, T.device, R.d_rows_out[b] + (size_t)to * rw, R.device, sizeof(uint32_t) * rw, R.xs));
 	}
 }
 
-// one global batch on local rank i (runs on the rank's own host thread)
-static int rank_batch(bfcg_group_t *g, int i)
+// lazy batch: slab mode without the host in the batch's loop (round 5).  The exchange never depended on the sizes (whole blocks travel); only the
+// owner's stage B did, and only through the host.  Now every source's fills travel beside its block as a ROW in device memory
+// (k_pack_rows), the owner builds its segment arrays from the rows on the device (k_seg_setup_mg), and stage A, exchange and stage B are
+// all enqueued before this thread looks at anything: it reads its own copy of the rows -- the overflow decision, the sizes a replay of
+// this stage B would need -- while the device still has the whole of stage B before it.  A slab that overflowed anywhere marks its row;
+// every owner sees every row, so stage B of the batch moves nothing on every rank, and the ranks repeat it through the two passes
+// (fall_back, sized_exchange) exactly as before -- the decision still falls inside this call, the caller's buffers are still his.
+// Returns whether a slab overflowed (redo); without one the batch is complete: its exchange and stage B are enqueued.
+static int lazy_batch(bfcg_group_t *g, rank_t &R, int ok)
 {
-	rank_t &R = g->r[i];
-	const int N = g->n_ranks, nb1 = g->nb1, nb_loc = g->nb_loc, me = R.rank;
-	const size_t cs = g->row_words; // a rank's row: its sizes, then (cs - 2) its failure word, (cs - 1) a slab of its stage A overflowed
+	const int N = g->n_ranks, me = R.rank, b = (int)(g->t & 1);
+	const size_t per = (size_t)g->nb_loc * 8, rw = (size_t)mg_row_words(R.ctx);
 	const uint64_t rb = (uint64_t)g->rec_bytes;
-	int ok = !g->failed;
-	GHIP(hipSetDevice(R.device));
-	// ---- stage A into send buffer [t & 1]: the exchange two batches ago read it last
-	const int sb = (int)(g->t & 1);
-	uint8_t *const send = R.send2[sb];
-	uint8_t *recv = R.recv[g->t & 1];
-	if (R.sent_pending[sb]) { GHIP(hipEventSynchronize(R.ev_sent[sb])); R.sent_pending[sb] = 0; }
-	const uint8_t *ds = R.in_seq, *dq = R.in_qual;
-	int slab = g->slabs; // (the same on every rank: decided between batches)
-	const int lazy = slab && g->lazy; // (decided by run_job for this batch)
-	int redo = 0;        // lazy: a slab overflowed somewhere -- found after this batch's (empty) stage B was enqueued
-	memset(R.counts, 0, sizeof(uint32_t) * cs);
-	if (ok) {
-		if (R.in_host && R.in_pos) {
-			if (R.in_pos > R.in_cap) { grp_err(g, "share of %llu positions exceeds the staging buffer", (unsigned long long)R.in_pos); ok = 0; }
-			else {
-				GHIP(hipMemcpyAsync(R.d_seq, R.in_seq, R.in_pos, hipMemcpyHostToDevice, R.cs));
-				if (R.in_qual) GHIP(hipMemcpyAsync(R.d_qual, R.in_qual, R.in_pos, hipMemcpyHostToDevice, R.cs));
-				GHIP(hipStreamSynchronize(R.cs));
-				ds = R.d_seq; dq = R.in_qual ? R.d_qual : 0;
-			}
+	hipEvent_t ev_a = 0;
+	int a_ok = ok;
+	if (ok && mg_scatter_slabs_async(R.ctx, R.in_seq, R.in_qual, R.in_pos, R.send2[b], (uint32_t)(R.send_cap / rb), R.d_rows_out[b], &ev_a) != 0) { grp_err(g, "rank %d: %s", me, bfcg_last_error()); ok = a_ok = 0; }
+	pthread_barrier_wait(&g->bar); // every local rank has enqueued its stage A, or failed to
+	if (!g->mp) ok = !g->failed;
+	// Between processes a rank cannot tell its peers that it has failed before they post their sends and receives for it: it takes part in
+	// the exchange all the same, with rows that say "nothing of this may be used" (every owner's stage B of the batch then moves nothing),
+	// and the failure word of the sizes' all-gather below ends the run on every process in this same batch.
+	const int post = g->mp ? 1 : ok;
+	if (post) {
+		if (a_ok) GHIP(hipStreamWaitEvent(R.xs, ev_a, 0));
+		else GHIP(hipMemsetAsync(R.d_rows_out[b], 0xff, sizeof(uint32_t) * (size_t)N * rw, R.xs));
+		GHIP(hipMemcpyAsync(R.d_rows_in[b] + (size_t)me * rw, R.d_rows_out[b] + (size_t)me * rw, sizeof(uint32_t) * rw, hipMemcpyDeviceToDevice, R.xs)); // (the own block was written in place)
+		if (g->xp == XP_RCCL) lazy_post_rccl(g, R, rw);
+		else if (g->push && N > 1) lazy_post_push(g, R, rw);
+		else lazy_post_peer(g, R, rw);
+		if (!(g->push && g->xp == XP_PEER)) __atomic_fetch_add(&g->x_links, (unsigned long long)(N - 1) * (g->blk * rb + sizeof(uint32_t) * rw), __ATOMIC_RELAXED);
+		GHIP(hipEventRecord(R.ev_x, R.xs));
+	}
+	pthread_barrier_wait(&g->bar); // every sender's event is recorded: the owners may wait for them
+	// the owner's stage B, from the rows on the device: all sources, or -- where that is more than this rank's regions take at full speed --
+	// a first group of them chosen by what they can send at most; the others follow below, grouped by their sizes
+	const int s1 = lazy_first_group(g, R);
+	int enq = 0;
+	if (ok && !g->failed) {
+		std::vector<hipEvent_t> ev = exchange_events(g, R);
+		if (mg_process_slabs_dev(R.ctx, R.recv[b], R.d_rows_in[b], g->slab_cap, (uint64_t)N * g->blk, 0, s1, ev.data(), (int)ev.size()) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
+		else enq = 1;
+	}
+	// ---- only now the host's copy of the sizes
+	int ovf = 0, have = a_ok;
+	if (a_ok && mg_scatter_slabs_wait(R.ctx, R.counts, &ovf) != 0) { grp_err(g, "rank %d: %s", me, bfcg_last_error()); have = 0; }
+	if (have && post && N > 1) { // what of this rank's stage A belonged on the links: the live records of the other ranks' buckets
+		unsigned long long live = 0;
+		for (int p = 0; p < N; ++p) if (p != me) for (size_t i2 = 0; i2 < per; ++i2) live += R.counts[(size_t)p * per + i2];
+		__atomic_fetch_add(&g->x_exact, live * rb, __ATOMIC_RELAXED);
+	}
+	// (between processes: the all-gather, behind this batch's exchange on the same stream; an overflow: found after this batch's (empty) stage B was enqueued)
+	const int redo = publish_row(g, R, have, ovf);
+	std::vector<uint32_t> seg((size_t)N * per, 0u), first((size_t)N * per, 0u);
+	if (!redo && !g->failed) {
+		seg = owner_sizes(g, R, per);
+		memcpy(first.data(), seg.data(), sizeof(uint32_t) * (size_t)s1 * per);
+	}
+	if (enq && mg_process_finish(R.ctx, first.data()) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
+	if (enq && !redo && !g->failed && s1 < N && process_in_groups(g, R, R.recv[b], seg.data(), per, g->slab_cap, 0, 0, s1, 1) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
+	pthread_barrier_wait(&g->bar); // (everybody has read the rows before anybody writes the next ones)
+	if (redo) { // the empty stage B and the exchange that carried the overflowed slabs: out of the way before the send buffer is written again
+		if (bfcg_sync(R.ctx) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
+		GHIP(hipStreamSynchronize(R.xs));
+	} else if (me == g->first) ++g->n_lazy;
+	return redo;
+}
+
+// sized stage A: into slabs in one pass, or exact buckets in two; the host has the sizes when it returns, and publishes the rank's row.
+// Returns whether a slab overflowed somewhere (redo).
+static int sized_stage_a(bfcg_group_t *g, rank_t &R, int slab, int &ok)
+{
+	const int b = (int)(g->t & 1);
+	int ovf = 0;
+	// (the rank's own slabs: the same place inside its block of the receive buffer, which lies send_cap bytes behind the send buffer)
+	if (ok && slab) {
+		if (mg_scatter_slabs(R.ctx, R.in_seq, R.in_qual, R.in_pos, R.send2[b], (uint32_t)(R.send_cap / (uint64_t)g->rec_bytes), R.counts, &ovf) != 0) { grp_err(g, "rank %d: %s", R.rank, bfcg_last_error()); ok = 0; }
+	} else if (ok && bfcg_mg_scatter(R.ctx, R.in_seq, R.in_qual, R.in_pos, R.send2[b], R.counts) != 0) { grp_err(g, "rank %d: %s", R.rank, bfcg_last_error()); ok = 0; }
+	return publish_row(g, R, ok, ovf);
+}
+
+// fall-back: a slab overflowed somewhere: every rank repeats its stage A through the two passes (its k-mers are counted) and the run stays with them
+static int fall_back(bfcg_group_t *g, rank_t &R, int ok)
+{
+	if (R.rank == g->first && getenv("BFCG_DEBUG_MG")) fprintf(stderr, "[D::group] batch %llu: a level-1 slab overflowed on some rank: two-pass stage A from here on\n", (unsigned long long)g->t);
+	if (R.rank == g->first) g->slabs = 0;
+	memset(R.counts, 0, sizeof(uint32_t) * g->row_words);
+	if (ok && mg_scatter_again(R.ctx, R.in_seq, R.in_qual, R.in_pos, R.send2[g->t & 1], R.counts) != 0) { grp_err(g, "rank %d: %s", R.rank, bfcg_last_error()); ok = 0; }
+	publish_row(g, R, ok, 0);
+	return ok;
+}
+
+// The sized exchange on the stream R.xs: records [s_off[p], s_off[p + 1]) of the send buffer go to rank p, one of two ways.
+// RCCL: the own block by a copy (slabs: it was written in place), the others grouped, and what the others send me to r_off[from]
+static void sized_post_rccl(bfcg_group_t *g, rank_t &R, int slab, const std::vector<uint64_t> &s_off, const std::vector<uint64_t> &r_off)
+{
+	const int N = g->n_ranks, me = R.rank, b = (int)(g->t & 1);
+	const uint64_t rb = (uint64_t)g->rec_bytes;
+	uint8_t *const send = R.send2[b], *const recv = R.recv[b];
+	if (!slab && s_off[me + 1] > s_off[me]) GHIP(hipMemcpyAsync(recv + r_off[me] * rb, send + s_off[me] * rb, (s_off[me + 1] - s_off[me]) * rb, hipMemcpyDeviceToDevice, R.xs));
+	if (N > 1) GNCCL(ncclGroupStart());
+	for (int step = 1; step < N; ++step) { // ring-shifted peer order: every rank talks to a different peer at any time
+		const int to = (me + step) % N, from = (me - step + N) % N;
+		const uint64_t n_to = (s_off[to + 1] - s_off[to]) * rb, n_from = (r_off[from + 1] - r_off[from]) * rb;
+		for (uint64_t c0 = 0; c0 < (n_to > n_from ? n_to : n_from); c0 += MSG_BYTES) {
+			if (c0 < n_to) GNCCL(ncclSend(send + s_off[to] * rb + c0, (size_t)(n_to - c0 < MSG_BYTES ? n_to - c0 : MSG_BYTES), ncclUint8, to, R.comm, R.xs));
+			if (c0 < n_from) GNCCL(ncclRecv(recv + r_off[from] * rb + c0, (size_t)(n_from - c0 < MSG_BYTES ? n_from - c0 : MSG_BYTES), ncclUint8, from, R.comm, R.xs));
 		}
 	}
-	if (lazy) {
-		// ---- Slab mode without the host in the batch's loop (round 5).  The exchange never depended on the sizes (whole blocks travel); only the
-		// owner's stage B did, and only through the host.  Now every source's fills travel beside its block as a ROW in device memory
-		// (k_pack_rows), the owner builds its segment arrays from the rows on the device (k_seg_setup_mg), and stage A, exchange and stage B are
-		// all enqueued before this thread looks at anything: it reads its own copy of the rows -- the overflow decision, the sizes a replay of
-		// this stage B would need -- while the device still has the whole of stage B before it.  A slab that overflowed anywhere marks its row;
-		// every owner sees every row, so stage B of the batch moves nothing on every rank, and the ranks repeat it through the two passes
-		// below exactly as before -- the decision still falls inside this call, the caller's buffers are still his.
-		const size_t rw_ = (size_t)bfcg_mg_row_words(R.ctx);
-		hipEvent_t ev_a = 0;
-		int a_ok = ok;
-		if (ok && bfcg_mg_scatter_slabs_async(R.ctx, ds, dq, R.in_pos, send, (uint32_t)(R.send_cap / rb), R.d_rows_out[sb], &ev_a) != 0) { grp_err(g, "rank %d: %s", me, bfcg_last_error()); ok = a_ok = 0; }
-		pthread_barrier_wait(&g->bar); // every local rank has enqueued its stage A, or failed to
-		if (!g->mp) ok = !g->failed;
-		// Between processes a rank cannot tell its peers that it has failed before they post their sends and receives for it: it takes part in
-		// the exchange all the same, with rows that say "nothing of this may be used" (every owner's stage B of the batch then moves nothing),
-		// and the failure word of the sizes' all-gather below ends the run on every process in this same batch.
-		const int post = g->mp ? 1 : ok;
-		if (post) {
-			if (a_ok) GHIP(hipStreamWaitEvent(R.xs, ev_a, 0));
-			else GHIP(hipMemsetAsync(R.d_rows_out[sb], 0xff, sizeof(uint32_t) * (size_t)N * rw_, R.xs));
-			uint32_t *const rin = R.d_rows_in[g->t & 1];
-			GHIP(hipMemcpyAsync(rin + (size_t)me * rw_, R.d_rows_out[sb] + (size_t)me * rw_, sizeof(uint32_t) * rw_, hipMemcpyDeviceToDevice, R.xs)); // (the own block was written in place)
-			if (g->xp == XP_RCCL) {
-				if (N > 1) GNCCL(ncclGroupStart());
-				for (int step = 1; step < N; ++step) {
-					const int to = (me + step) % N, from = (me - step + N) % N;
-					const uint64_t nbytes = g->blk * rb;
-					for (uint64_t c0 = 0; c0 < nbytes; c0 += MSG_BYTES) {
-						GNCCL(ncclSend(send + (uint64_t)to * nbytes + c0, (size_t)(nbytes - c0 < MSG_BYTES ? nbytes - c0 : MSG_BYTES), ncclUint8, to, R.comm, R.xs));
-						GNCCL(ncclRecv(recv + (uint64_t)from * nbytes + c0, (size_t)(nbytes - c0 < MSG_BYTES ? nbytes - c0 : MSG_BYTES), ncclUint8, from, R.comm, R.xs));
-					}
-					GNCCL(ncclSend(R.d_rows_out[sb] + (size_t)to * rw_, rw_, ncclUint32, to, R.comm, R.xs));
-					GNCCL(ncclRecv(rin + (size_t)from * rw_, rw_, ncclUint32, from, R.comm, R.xs));
-				}
-				if (N > 1) GNCCL(ncclGroupEnd());
-			} else if (g->push && N > 1) {
-				PushDst D;
-				memset(&D, 0, sizeof(D));
-				for (int p = 0; p < N; ++p) { const rank_t &T = g->r[p - g->first]; D.recv[p] = T.recv[g->t & 1]; D.rows[p] = T.d_rows_in[g->t & 1]; }
-				const uint32_t per = (uint32_t)nb_loc * 8u;
-				unsigned wgs = g->push_wgs;
-				if (wgs > (unsigned)(N - 1) * per) wgs = (unsigned)(N - 1) * per;
-				if (wgs < (unsigned)(N - 1)) wgs = (unsigned)(N - 1);
-				hipLaunchKernelGGL(k_push_slabs, dim3(wgs), dim3(256), 0, R.xs, (const uint8_t *)send, (const uint32_t *)R.d_rows_out[sb], D, N, me, per, g->slab_cap, (uint32_t)rb, (uint32_t)rw_, R.d_moved);
-				GHIP(hipGetLastError());
-			} else {
-				for (int step = 1; step < N; ++step) {
-					const int to = (me + step) % N;
-					const rank_t &T = g->r[to - g->first];
-					GHIP(hipMemcpyPeerAsync(T.recv[g->t & 1] + (uint64_t)me * g->blk * rb, T.device, send + (uint64_t)to * g->blk * rb, R.device, g->blk * rb, R.xs));
-					GHIP(hipMemcpyPeerAsync(T.d_rows_in[g->t & 1] + (size_t)me * rw_, T.device, R.d_rows_out[sb] + (size_t)to * rw_, R.device, sizeof(uint32_t) * rw_, R.xs));
-				}
-			}
-			if (!(g->push && g->xp == XP_PEER)) __atomic_fetch_add(&g->x_links, (unsigned long long)(N - 1) * (g->blk * rb + sizeof(uint32_t) * rw_), __ATOMIC_RELAXED);
-			GHIP(hipEventRecord(R.ev_x, R.xs));
-		}
-		pthread_barrier_wait(&g->bar); // every sender's event is recorded: the owners may wait for them
-		// the owner's stage B, from the rows on the device: all sources, or -- where that is more than this rank's regions take at full speed --
-		// a first group of them chosen by what they can send at most; the others follow below, grouped by their sizes
-		const int s1 = lazy_first_group(g, R);
-		int enq = 0;
-		if (ok && !g->failed) {
-			std::vector<hipEvent_t> ev;
-			if (g->xp == XP_RCCL) ev.push_back(R.ev_x);
-			else for (int j = 0; j < g->n_local; ++j) ev.push_back(g->r[j].ev_x);
-			if (bfcg_mg_process_slabs_dev(R.ctx, recv, R.d_rows_in[g->t & 1], g->slab_cap, (uint64_t)N * g->blk, 0, s1, ev.data(), (int)ev.size()) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
-			else enq = 1;
-		}
-		// ---- only now the host's copy of the sizes
-		int ovf = 0;
-		if (a_ok && bfcg_mg_scatter_slabs_wait(R.ctx, R.counts, &ovf) != 0) { grp_err(g, "rank %d: %s", me, bfcg_last_error()); memset(R.counts, 0, sizeof(uint32_t) * cs); }
-		if (!a_ok) memset(R.counts, 0, sizeof(uint32_t) * cs);
-		if (post && N > 1) { // what of this rank's stage A belonged on the links: the live records of the other ranks' buckets
-			unsigned long long live = 0;
-			const size_t per = (size_t)nb_loc * 8;
-			for (int p = 0; p < N; ++p) if (p != me) for (size_t i2 = 0; i2 < per; ++i2) live += R.counts[(size_t)p * per + i2];
-			__atomic_fetch_add(&g->x_exact, live * rb, __ATOMIC_RELAXED);
-		}
-		R.counts[cs - 1] = ovf ? 1u : 0u;
-		R.counts[cs - 2] = g->failed ? 1u : 0u;
-		publish_sizes(g, R); // (between processes: the all-gather, behind this batch's exchange on the same stream)
-		pthread_barrier_wait(&g->bar); // all local ranks have published their sizes
-		for (int p = 0; p < N; ++p) redo |= g->all_counts[(size_t)p * cs + cs - 1] != 0;
-		{
-			const size_t per = (size_t)nb_loc * 8;
-			std::vector<uint32_t> seg((size_t)N * per, 0u), first((size_t)N * per, 0u);
-			if (!redo && !g->failed) {
-				for (int s2 = 0; s2 < N; ++s2) memcpy(&seg[(size_t)s2 * per], &g->all_counts[(size_t)s2 * cs + (size_t)me * per], sizeof(uint32_t) * per);
-				memcpy(first.data(), seg.data(), sizeof(uint32_t) * (size_t)s1 * per);
-			}
-			if (enq && bfcg_mg_process_finish(R.ctx, first.data()) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
-			if (enq && !redo && !g->failed && s1 < N && process_in_groups_slabs(g, R, recv, seg.data(), 0, 0, s1, 1) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
-		}
-		pthread_barrier_wait(&g->bar); // (everybody has read the rows before anybody writes the next ones)
-		ok = !g->failed;
-		if (redo) { // the empty stage B and the exchange that carried the overflowed slabs: out of the way before the send buffer is written again
-			if (bfcg_sync(R.ctx) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
-			GHIP(hipStreamSynchronize(R.xs));
-			ok = !g->failed;
-		} else if (i == 0) ++g->n_lazy;
-	} else
-	if (ok) {
-		if (ok && slab) {
-			int ovf = 0;
-			// (the rank's own slabs: the same place inside its block of the receive buffer, which lies send_cap bytes behind the send buffer)
-			if (bfcg_mg_scatter_slabs(R.ctx, ds, dq, R.in_pos, send, (uint32_t)(R.send_cap / rb), R.counts, &ovf) != 0) { grp_err(g, "rank %d: %s", me, bfcg_last_error()); ok = 0; }
-			R.counts[cs - 1] = ovf ? 1u : 0u;
-		} else if (ok && bfcg_mg_scatter(R.ctx, ds, dq, R.in_pos, send, R.counts) != 0) { grp_err(g, "rank %d: %s", me, bfcg_last_error()); ok = 0; }
+	if (N > 1) GNCCL(ncclGroupEnd());
+}
+// peer copies: I push my records into every owner's receive buffer (all ranks are local), my own included unless slabs put them there
+static void sized_post_peer(bfcg_group_t *g, rank_t &R, int slab, const std::vector<uint64_t> &s_off)
+{
+	const int N = g->n_ranks, nb_loc = g->nb_loc, me = R.rank, b = (int)(g->t & 1);
+	const size_t cs = g->row_words;
+	const uint64_t rb = (uint64_t)g->rec_bytes;
+	for (int step = slab ? 1 : 0; step < N; ++step) {
+		const int to = (me + step) % N;
+		const rank_t &T = g->r[to - g->first];
+		const uint64_t n_to = (s_off[to + 1] - s_off[to]) * rb;
+		// my block in `to`'s buffer starts behind the blocks of the sources before me
+		uint64_t at = 0;
+		if (slab) at = (uint64_t)me * g->blk;
+		else for (int p = 0; p < me; ++p) for (int k = 0; k < nb_loc; ++k) at += g->all_counts[(size_t)p * cs + (size_t)to * nb_loc + k];
+		if (n_to) GHIP(hipMemcpyPeerAsync(T.recv[b] + at * rb, T.device, R.send2[b] + s_off[to] * rb, R.device, n_to, R.xs));
 	}
-	if (!lazy) {
-	if (!ok) memset(R.counts, 0, sizeof(uint32_t) * cs);
-	// The failure word travels with the sizes: g->failed is local to a process, and a rank that skipped the exchange while its peers posted
-	// ncclSend / ncclRecv for it would leave them blocked for good.  A group that has failed keeps taking part in this all-gather (and only in it),
-	// so that every process of the run takes the same decision in the same batch.
-	R.counts[cs - 2] = g->failed ? 1u : 0u;
-	publish_sizes(g, R);
-	pthread_barrier_wait(&g->bar); // all local ranks have published their sizes
-	}
-	if (slab) { // a slab overflowed somewhere: every rank repeats its stage A through the two passes (its k-mers are counted) and the run stays with them
-		int any = redo;
-		if (!lazy) {
-			for (int p = 0; p < N; ++p) any |= g->all_counts[(size_t)p * cs + cs - 1] != 0;
-			pthread_barrier_wait(&g->bar); // (everybody has read the rows before anybody writes the next ones)
-		}
-		if (any) {
-			if (i == 0 && getenv("BFCG_DEBUG_MG")) fprintf(stderr, "[D::group] batch %llu: a level-1 slab overflowed on some rank: two-pass stage A from here on\n", (unsigned long long)g->t);
-			if (i == 0) g->slabs = 0;
-			slab = 0;
-			memset(R.counts, 0, sizeof(uint32_t) * cs);
-			if (ok && bfcg_mg_scatter_again(R.ctx, ds, dq, R.in_pos, send, R.counts) != 0) { grp_err(g, "rank %d: %s", me, bfcg_last_error()); ok = 0; }
-			if (!ok) memset(R.counts, 0, sizeof(uint32_t) * cs);
-			R.counts[cs - 2] = g->failed ? 1u : 0u;
-			publish_sizes(g, R);
-			pthread_barrier_wait(&g->bar);
-		}
-	}
-	if (!lazy || redo) { // (a lazy batch that went well is complete: its exchange and stage B were enqueued above)
-	if (i == 0) g->go = !g->failed; // one decision for all local ranks -- and, the failure words being all-gathered, for all processes
+}
+
+// sized exchange + stage B: the sizes of every rank are on the host.  Offsets, capacity check, books, the records, stage B behind them.
+// Returns whether this rank's part of the exchange was enqueued.
+static int sized_exchange(bfcg_group_t *g, rank_t &R, int slab)
+{
+	const int N = g->n_ranks, nb_loc = g->nb_loc, me = R.rank;
+	const size_t cs = g->row_words, per = (size_t)nb_loc * (slab ? 8 : 1);
+	const uint64_t rb = (uint64_t)g->rec_bytes;
+	if (me == g->first) g->go = !g->failed; // one decision for all local ranks -- and, the failure words being all-gathered, for all processes
 	pthread_barrier_wait(&g->bar);
 	const uint32_t *C = g->all_counts;
-	ok = g->go;
+	int ok = g->go;
 	std::vector<uint64_t> s_off((size_t)N + 1, 0), r_off((size_t)N + 1, 0);
 	if (slab) { // fixed places: block p of my send buffer goes to rank p, block s of my receive buffer comes from rank s
 		for (int p = 0; p <= N; ++p) s_off[p] = r_off[p] = (uint64_t)p * g->blk;
@@ -450,76 +467,71 @@ static int rank_batch(bfcg_group_t *g, int i)
 		unsigned long long links = 0, live = 0;
 		for (int p = 0; p < N; ++p) if (p != me) {
 			links += (s_off[p + 1] - s_off[p]) * rb;
-			if (slab) for (int i2 = 0; i2 < nb_loc * 8; ++i2) live += (unsigned long long)C[(size_t)me * cs + (size_t)p * nb_loc * 8 + i2] * rb;
+			if (slab) for (size_t i2 = 0; i2 < per; ++i2) live += (unsigned long long)C[(size_t)me * cs + (size_t)p * per + i2] * rb;
 		}
 		__atomic_fetch_add(&g->x_links, links, __ATOMIC_RELAXED);
 		__atomic_fetch_add(&g->x_exact, slab ? live : links, __ATOMIC_RELAXED);
 	}
 	// ---- records
-	if (g->xp == XP_RCCL) {
-		if (ok) {
-			if (!slab && s_off[me + 1] > s_off[me]) GHIP(hipMemcpyAsync(recv + r_off[me] * rb, send + s_off[me] * rb, (s_off[me + 1] - s_off[me]) * rb, hipMemcpyDeviceToDevice, R.xs));
-			if (N > 1) GNCCL(ncclGroupStart());
-			for (int step = 1; step < N; ++step) { // ring-shifted peer order: every rank talks to a different peer at any time
-				const int to = (me + step) % N, from = (me - step + N) % N;
-				const uint64_t n_to = (s_off[to + 1] - s_off[to]) * rb, n_from = (r_off[from + 1] - r_off[from]) * rb;
-				for (uint64_t c0 = 0; c0 < (n_to > n_from ? n_to : n_from); c0 += MSG_BYTES) {
-					if (c0 < n_to) GNCCL(ncclSend(send + s_off[to] * rb + c0, (size_t)(n_to - c0 < MSG_BYTES ? n_to - c0 : MSG_BYTES), ncclUint8, to, R.comm, R.xs));
-					if (c0 < n_from) GNCCL(ncclRecv(recv + r_off[from] * rb + c0, (size_t)(n_from - c0 < MSG_BYTES ? n_from - c0 : MSG_BYTES), ncclUint8, from, R.comm, R.xs));
-				}
-			}
-			if (N > 1) GNCCL(ncclGroupEnd());
-			GHIP(hipEventRecord(R.ev_x, R.xs));
-		}
-	} else { // peer copies: I push my records into every owner's receive buffer (all ranks are local)
-		if (ok) {
-			for (int step = slab ? 1 : 0; step < N; ++step) {
-				const int to = (me + step) % N;
-				const rank_t &T = g->r[to - g->first];
-				const uint64_t n_to = (s_off[to + 1] - s_off[to]) * rb;
-				// my block in `to`'s buffer starts behind the blocks of the sources before me
-				uint64_t at = 0;
-				if (slab) at = (uint64_t)me * g->blk;
-				else for (int p = 0; p < me; ++p) for (int k = 0; k < nb_loc; ++k) at += C[(size_t)p * cs + (size_t)to * nb_loc + k];
-				if (n_to) GHIP(hipMemcpyPeerAsync(T.recv[g->t & 1] + at * rb, T.device, send + s_off[to] * rb, R.device, n_to, R.xs));
-			}
-			GHIP(hipEventRecord(R.ev_x, R.xs));
-		}
-		pthread_barrier_wait(&g->bar); // every sender's event is recorded: the owners may wait for them
+	if (ok) {
+		if (g->xp == XP_RCCL) sized_post_rccl(g, R, slab, s_off, r_off);
+		else sized_post_peer(g, R, slab, s_off);
+		GHIP(hipEventRecord(R.ev_x, R.xs));
 	}
+	if (g->xp != XP_RCCL) pthread_barrier_wait(&g->bar); // every sender's event is recorded: the owners may wait for them (RCCL: a rank waits for its own receives only)
 	// ---- stage B behind the exchange
 	if (ok && !g->failed) {
-		std::vector<hipEvent_t> ev;
-		if (g->xp == XP_RCCL) ev.push_back(R.ev_x);
-		else for (int j = 0; j < g->n_local; ++j) ev.push_back(g->r[j].ev_x);
-		if (slab) {
-			const size_t per = (size_t)nb_loc * 8;
-			std::vector<uint32_t> seg((size_t)N * per);
-			for (int s = 0; s < N; ++s) memcpy(&seg[(size_t)s * per], &C[(size_t)s * cs + (size_t)me * per], sizeof(uint32_t) * per);
-			if (process_in_groups_slabs(g, R, recv, seg.data(), ev.data(), (int)ev.size()) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
-		} else {
-			std::vector<uint32_t> seg((size_t)N * nb_loc);
-			for (int s = 0; s < N; ++s) memcpy(&seg[(size_t)s * nb_loc], &C[(size_t)s * cs + (size_t)me * nb_loc], sizeof(uint32_t) * (size_t)nb_loc);
-			if (process_in_groups(g, R, recv, seg.data(), ev.data(), (int)ev.size()) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
+		std::vector<hipEvent_t> ev = exchange_events(g, R);
+		const std::vector<uint32_t> seg = owner_sizes(g, R, per);
+		if (process_in_groups(g, R, R.recv[g->t & 1], seg.data(), per, slab ? g->slab_cap : 0u, ev.data(), (int)ev.size()) != 0) grp_err(g, "rank %d: %s", me, bfcg_last_error());
+	}
+	return ok;
+}
+
+// one global batch on a local rank: begin, one of the protocols, end
+static int rank_batch(bfcg_group_t *g, rank_t &R)
+{
+	const int b = (int)(g->t & 1);
+	int slab = g->slabs;              // (the same on every rank: decided between batches)
+	const int lazy = slab && g->lazy; // (decided by run_job for this batch)
+	int ok = !g->failed, redo;
+	GHIP(hipSetDevice(R.device));
+	// ---- begin.  Stage A goes into send buffer [t & 1]: the exchange two batches ago read it last
+	if (R.sent_pending[b]) { GHIP(hipEventSynchronize(R.ev_sent[b])); R.sent_pending[b] = 0; }
+	memset(R.counts, 0, sizeof(uint32_t) * g->row_words);
+	if (ok && R.in_host && R.in_pos) {
+		if (R.in_pos > R.in_cap) { grp_err(g, "share of %llu positions exceeds the staging buffer", (unsigned long long)R.in_pos); ok = 0; }
+		else {
+			GHIP(hipMemcpyAsync(R.d_seq, R.in_seq, R.in_pos, hipMemcpyHostToDevice, R.cs));
+			if (R.in_qual) GHIP(hipMemcpyAsync(R.d_qual, R.in_qual, R.in_pos, hipMemcpyHostToDevice, R.cs));
+			GHIP(hipStreamSynchronize(R.cs));
+			R.in_seq = R.d_seq; R.in_qual = R.in_qual ? R.d_qual : 0; R.in_host = 0; // (the share is the staged one from here on)
 		}
 	}
+	// ---- the protocol
+	if (lazy) { redo = lazy_batch(g, R, ok); ok = !g->failed; }
+	else {
+		redo = sized_stage_a(g, R, slab, ok);
+		if (slab) pthread_barrier_wait(&g->bar); // (everybody has read the rows before anybody writes the next ones)
 	}
+	if (redo) { ok = fall_back(g, R, ok); slab = 0; }
+	if (!lazy || redo) ok = sized_exchange(g, R, slab); // (a lazy batch that went well is complete: its exchange and stage B were enqueued)
+	// ---- end
 	{ uint64_t calls = 0; bfcg_progress(R.ctx, &calls, 0, 0, 0); R.batch_call[g->t & 63] = calls; } // this global batch is complete on this rank once that call is
 	// The exchange is left running: the next batch's stage A (other send buffer) proceeds beside it.  What the next batch may not do before
 	// this one is through is ordered elsewhere: its exchange follows this one on the stream xs; a receive buffer is written again two batches
-	// on, behind this barrier of the batch in between, which every rank reaches only after its bfcg_mg_process_ev has waited for THIS
+	// on, behind this barrier of the batch in between, which every rank reaches only after its mg_process has waited for THIS
 	// batch's stage B (finalise_previous); the other ranks have read all_counts before they come here.  (Slab mode: stage A of batch t + 2 writes
 	// the rank's own share into receive buffer [t & 1] again -- behind the same wait for this batch's stage B.)
-	if (ok) { GHIP(hipEventRecord(R.ev_sent[sb], R.xs)); R.sent_pending[sb] = 1; }
+	if (ok) { GHIP(hipEventRecord(R.ev_sent[b], R.xs)); R.sent_pending[b] = 1; }
 	pthread_barrier_wait(&g->bar);
 	return g->failed ? -1 : 0;
 }
 
 static void *rank_main(void *arg)
 {
-	bfcg_group_t *g = (bfcg_group_t *)((void **)arg)[0];
-	const int i = (int)(intptr_t)((void **)arg)[1];
-	free(arg);
+	rank_t &R = *(rank_t *)arg;
+	bfcg_group_t *g = R.grp;
 	uint64_t seen = 0;
 	for (;;) {
 		pthread_mutex_lock(&g->mu);
@@ -527,14 +539,14 @@ static void *rank_main(void *arg)
 		if (g->quit) { pthread_mutex_unlock(&g->mu); return 0; }
 		seen = g->job;
 		pthread_mutex_unlock(&g->mu);
-		g->r[i].rc = rank_batch(g, i);
+		R.rc = rank_batch(g, R);
 		pthread_mutex_lock(&g->mu);
 		if (++g->n_done == g->n_local) { g->done_job = seen; pthread_cond_broadcast(&g->cv); }
 		pthread_mutex_unlock(&g->mu);
 	}
 }
 
-// May the next global batch keep the host out of its loop (rank_batch: `lazy`)?  Slab mode, and every context able to take its stage B from rows
+// May the next global batch keep the host out of its loop (lazy_batch)?  Slab mode, and every context able to take its stage B from rows
 // on the device (checked when the group is created).
 static int lazy_possible(bfcg_group_t *g)
 {
@@ -632,13 +644,13 @@ extern "C" bfcg_group_t *bfcg_group_create(const bfcg_params_t *prm, int n_ranks
 		const char *e = getenv("BFCG_MG_SLABS");
 		g->slabs_ok = !(e && atoi(e) == 0) && !prm->track_order;
 		g->slab_cap = 0;
-		for (auto &R : g->r) { uint32_t si[2]; bfcg_mg_slab_info(R.ctx, si); if (!si[1]) g->slabs_ok = 0; g->slab_cap = si[0]; }
+		for (auto &R : g->r) { uint32_t si[2]; mg_slab_info(R.ctx, si); if (!si[1]) g->slabs_ok = 0; g->slab_cap = si[0]; }
 		g->blk = (uint64_t)g->nb_loc * 8 * g->slab_cap;
 		const uint64_t S = (uint64_t)g->nb1 * 8 * g->slab_cap;
 		if (S + (rcap > S ? rcap : S) + 8192 >= 0xffffffffULL) g->slabs_ok = 0;
 		g->slabs = g->slabs_ok;
 		g->row_words = (size_t)g->nb1 * (g->slabs_ok ? 8 : 1) + 2;
-		{ const char *e2 = getenv("BFCG_MG_LAZY"); g->lazy_ok = g->slabs_ok && !(e2 && atoi(e2) == 0); for (auto &R : g->r) if (!bfcg_mg_async_ok(R.ctx)) g->lazy_ok = 0; }
+		{ const char *e2 = getenv("BFCG_MG_LAZY"); g->lazy_ok = g->slabs_ok && !(e2 && atoi(e2) == 0); for (auto &R : g->r) if (!mg_async_ok(R.ctx)) g->lazy_ok = 0; }
 		g->lazy = 0; g->n_lazy = 0;
 	}
 	if (hipHostMalloc(&g->all_counts, sizeof(uint32_t) * (size_t)n_ranks * g->row_words, hipHostMallocDefault) != hipSuccess) { bfcg_set_error("hipHostMalloc failed"); bfcg_group_destroy(g); return NULL; }
@@ -673,7 +685,7 @@ extern "C" bfcg_group_t *bfcg_group_create(const bfcg_params_t *prm, int n_ranks
 		}
 		if (e == hipSuccess) e = hipMalloc(&R.d_counts, sizeof(uint32_t) * (size_t)n_ranks * g->row_words);
 		if (g->lazy_ok) for (int b = 0; b < 2; ++b) {
-			const size_t w = (size_t)n_ranks * (size_t)bfcg_mg_row_words(R.ctx);
+			const size_t w = (size_t)n_ranks * (size_t)mg_row_words(R.ctx);
 			if (e == hipSuccess) e = hipMalloc(&R.d_rows_out[b], sizeof(uint32_t) * w);
 			if (e == hipSuccess) e = hipMalloc(&R.d_rows_in[b], sizeof(uint32_t) * w);
 			if (e == hipSuccess) e = hipMemset(R.d_rows_in[b], 0, sizeof(uint32_t) * w);
@@ -701,16 +713,9 @@ extern "C" bfcg_group_t *bfcg_group_create(const bfcg_params_t *prm, int n_ranks
 	(void)hipGetLastError(); // hipDeviceEnablePeerAccess on an already enabled pair
 	if (g->mp) { // one rank per process: every process must have decided the same exchange layout (slab mode, slab capacity, words per row of sizes) --
 	             // each decides it from its own environment and context; an all-gather with different counts would hang or corrupt memory
-		rank_t &R = g->r[0];
 		const uint32_t mine[4] = {(uint32_t)(g->slabs_ok | (g->lazy_ok << 1)), g->slab_cap, (uint32_t)g->row_words, (uint32_t)g->rec_bytes}; // (bit 1: the sizes stay on the device -- BFCG_MG_LAZY)
 		std::vector<uint32_t> all((size_t)4 * n_ranks, 0);
-		hipError_t he = hipSetDevice(R.device);
-		ncclResult_t ne = ncclSuccess;
-		if (he == hipSuccess) he = hipMemcpyAsync(R.d_counts + (size_t)4 * R.rank, mine, sizeof(mine), hipMemcpyHostToDevice, R.xs); // (d_counts holds n_ranks x row_words >= 4 n_ranks words)
-		if (he == hipSuccess) ne = ncclAllGather(R.d_counts + (size_t)4 * R.rank, R.d_counts, 4, ncclUint32, R.comm, R.xs);
-		if (he == hipSuccess && ne == ncclSuccess) he = hipMemcpyAsync(all.data(), R.d_counts, sizeof(uint32_t) * all.size(), hipMemcpyDeviceToHost, R.xs);
-		if (he == hipSuccess && ne == ncclSuccess) he = hipStreamSynchronize(R.xs);
-		if (he != hipSuccess || ne != ncclSuccess) { bfcg_set_error("all-gather of the ranks' exchange layout failed"); g->failed = 1; bfcg_group_destroy(g); return NULL; }
+		if (all_gather_words(g, g->r[0], mine, 4, all.data())) { bfcg_set_error("all-gather of the ranks' exchange layout failed"); g->failed = 1; bfcg_group_destroy(g); return NULL; } // (d_counts holds n_ranks x row_words >= 4 n_ranks words)
 		for (int p = 0; p < n_ranks; ++p)
 			if (memcmp(&all[(size_t)4 * p], mine, sizeof(mine)) != 0) {
 				char msg[256];
@@ -720,9 +725,8 @@ extern "C" bfcg_group_t *bfcg_group_create(const bfcg_params_t *prm, int n_ranks
 			}
 	}
 	for (int i = 0; i < n_local; ++i) {
-		void **arg = (void **)malloc(2 * sizeof(void *));
-		arg[0] = g; arg[1] = (void *)(intptr_t)i;
-		if (pthread_create(&g->r[i].th, 0, rank_main, arg) != 0) { g->r[i].th = 0; free(arg); bfcg_set_error("pthread_create failed"); bfcg_group_destroy(g); return NULL; }
+		g->r[i].grp = g;
+		if (pthread_create(&g->r[i].th, 0, rank_main, &g->r[i]) != 0) { g->r[i].th = 0; bfcg_set_error("pthread_create failed"); bfcg_group_destroy(g); return NULL; }
 	}
 	return g;
 }
@@ -775,17 +779,9 @@ extern "C" int bfcg_group_reset(bfcg_group_t *g)
 static int mp_agree(bfcg_group_t *g, int local_rc)
 {
 	if (!g->mp) return local_rc;
-	rank_t &R = g->r[0];
-	uint32_t w = (local_rc != 0 || g->failed) ? 1u : 0u;
+	const uint32_t w = (local_rc != 0 || g->failed) ? 1u : 0u;
 	std::vector<uint32_t> all((size_t)g->n_ranks, 0);
-	hipError_t he = hipSetDevice(R.device);
-	ncclResult_t ne = ncclSuccess;
-	// (d_counts is free between batches; in place: word `rank` is this rank's contribution)
-	if (he == hipSuccess) he = hipMemcpyAsync(R.d_counts + R.rank, &w, sizeof(w), hipMemcpyHostToDevice, R.xs);
-	if (he == hipSuccess) ne = ncclAllGather(R.d_counts + R.rank, R.d_counts, 1, ncclUint32, R.comm, R.xs);
-	if (he == hipSuccess && ne == ncclSuccess) he = hipMemcpyAsync(all.data(), R.d_counts, sizeof(uint32_t) * (size_t)g->n_ranks, hipMemcpyDeviceToHost, R.xs);
-	if (he == hipSuccess && ne == ncclSuccess) he = hipStreamSynchronize(R.xs);
-	if (he != hipSuccess || ne != ncclSuccess) { bfcg_set_error("all-gather of the ranks' status failed"); return -1; }
+	if (all_gather_words(g, g->r[0], &w, 1, all.data())) { bfcg_set_error("all-gather of the ranks' status failed"); return -1; }
 	for (int p = 0; p < g->n_ranks; ++p) if (all[(size_t)p] && local_rc == 0 && !g->failed) { grp_err(g, "rank %d of the run has failed", p); bfcg_set_error(g->err); return -1; }
 	return local_rc != 0 || g->failed ? -1 : 0;
 }
@@ -829,8 +825,6 @@ extern "C" int bfcg_group_progress(bfcg_group_t *g, uint64_t *batches, uint64_t 
 	return j;
 }
 
-static inline int is_acgt(uint8_t ch) { ch &= 0xDF; return ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T'; }
-
 // A group of ONE rank counts a batch far larger than the filter's regions take at full speed in ROUNDS, as a single GPU cuts an oversized call
 // into sub-batches (a region handles only so many k-mers with clear bits per pass -- list_cap -- before it falls onto the exact but slow HBM
 // path).  With several ranks the owner splits what it received by SOURCES instead (process_in_groups): the file order of a global batch is
@@ -841,22 +835,14 @@ static int rounds_for(bfcg_group_t *g, uint64_t local_pos, int *rounds)
 	if (g->n_ranks > 1) return 0;
 	uint64_t total = local_pos;
 	if (g->mp) {
-		rank_t &R = g->r[0];
-		std::vector<unsigned long long> all((size_t)g->n_ranks, 0);
-		unsigned long long mine = local_pos;
-		unsigned long long *d = reinterpret_cast<unsigned long long *>(R.d_counts); // (free between batches; N * (nb1 + 1) words >= 2 N)
-		hipError_t he = hipSetDevice(R.device);
-		ncclResult_t ne = ncclSuccess;
-		if (he == hipSuccess) he = hipMemcpyAsync(d + R.rank, &mine, sizeof(mine), hipMemcpyHostToDevice, R.xs);
-		if (he == hipSuccess) ne = ncclAllGather(d + R.rank, d, 1, ncclUint64, R.comm, R.xs);
-		if (he == hipSuccess && ne == ncclSuccess) he = hipMemcpyAsync(all.data(), d, sizeof(unsigned long long) * (size_t)g->n_ranks, hipMemcpyDeviceToHost, R.xs);
-		if (he == hipSuccess && ne == ncclSuccess) he = hipStreamSynchronize(R.xs);
-		if (he != hipSuccess || ne != ncclSuccess) { bfcg_set_error("all-gather of the ranks' batch sizes failed"); return -1; }
+		std::vector<uint64_t> all((size_t)g->n_ranks, 0);
+		const uint64_t mine = local_pos; // (two words a rank; N * (nb1 + 1) words >= 2 N)
+		if (all_gather_words(g, g->r[0], reinterpret_cast<const uint32_t *>(&mine), 2, reinterpret_cast<uint32_t *>(all.data()))) { bfcg_set_error("all-gather of the ranks' batch sizes failed"); return -1; }
 		total = 0;
 		for (auto v : all) total += v;
 	}
 	double warm = 1e30;
-	for (auto &R : g->r) { const double w = bfcg_mg_warm_factor(R.ctx); if (w < warm) warm = w; }
+	for (auto &R : g->r) { const double w = mg_warm_factor(R.ctx); if (w < warm) warm = w; }
 	const double per_rank = 0.8 * (double)total / (double)g->n_ranks, limit = (double)g->kmer_limit * warm * 0.9;
 	int r = per_rank <= limit * 7.0 / 6.0 ? 1 : (int)(per_rank / limit) + 1; // (just above the limit a few slow regions cost less than another pass over filter and table)
 	if (getenv("BFCG_MG_ROUNDS")) r = atoi(getenv("BFCG_MG_ROUNDS"));
@@ -900,6 +886,13 @@ extern "C" int bfcg_group_count_batch_dev(bfcg_group_t *g, const uint8_t *const 
 	return 0;
 }
 
+// a cut at e > lo of a host stream of n bytes, moved forward to just behind the next byte that ends a k-mer (not ACGT) -- or to the end
+static uint64_t host_cut(const uint8_t *h_seq, uint64_t lo, uint64_t e, uint64_t n)
+{
+	while (e < n && e > lo && is_acgt(h_seq[e - 1])) ++e;
+	return e;
+}
+
 // One global batch from host memory (all ranks local): the stream is cut into n_ranks contiguous shares at separator bytes (no k-mer spans
 // one) -- rank r takes the r-th share, which is the rank-major file order the exchange assumes.
 static int group_host_piece(bfcg_group_t *g, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos)
@@ -909,7 +902,7 @@ static int group_host_piece(bfcg_group_t *g, const uint8_t *h_seq, const uint8_t
 	for (int i = 0; i < N; ++i) {
 		uint64_t e = i + 1 == N ? n_pos : n_pos * (uint64_t)(i + 1) / (uint64_t)N;
 		if (e < o) e = o;
-		while (e < n_pos && e > o && is_acgt(h_seq[e - 1])) ++e; // forward to just behind the next byte that ends a k-mer
+		e = host_cut(h_seq, o, e, n_pos);
 		if (i + 1 == N) e = n_pos;
 		g->r[i].in_seq = h_seq + o; g->r[i].in_qual = h_qual ? h_qual + o : 0; g->r[i].in_pos = e - o; g->r[i].in_host = 1;
 		o = e;
@@ -925,7 +918,7 @@ extern "C" int bfcg_group_count_batch_host(bfcg_group_t *g, const uint8_t *h_seq
 	for (int r = 0; r < rounds && a < n_pos; ++r) {
 		uint64_t e = r + 1 == rounds ? n_pos : n_pos / (uint64_t)rounds * (uint64_t)(r + 1);
 		if (e < a) e = a;
-		while (e < n_pos && e > a && is_acgt(h_seq[e - 1])) ++e;
+		e = host_cut(h_seq, a, e, n_pos);
 		if (e > a && group_host_piece(g, h_seq + a, h_qual ? h_qual + a : 0, e - a) != 0) return -1;
 		a = e;
 	}

@@ -203,6 +203,7 @@ def test_group_rccl_single_rank_as_one_process_of_many(gpu_lib, g1):
     half = (rs.n_reads // 2) * (rs.L + 1)
     grp.count_dev([ds], [dq], [half])
     grp.count_dev([ds + half], [dq + half], [len(s) - half])
+    grp.sync()  # (bfcg_group_sync: the all-gather of the ranks' status)
     st, ost = grp.stats(), oc.stats()
     assert (st["n_kmers"], st["n_high"], st["n_seen"]) == (ost["n_kmers"], ost["n_high"], ost["n_seen"])
     assert np.array_equal(c.bloom_bytes(), oc.bloom_bytes())
@@ -267,12 +268,18 @@ def test_group_level2_slab_overflow_is_replayed(gpu_lib, n_ranks, fm):
     grp.close(); oc.close()
 
 
-@pytest.mark.parametrize("n_ranks,fm", [(2, 0), (4, 1)] + ([(4, 0), (2, 1)] if os.environ.get("BFC_TEST_MORE") else []))
-def test_group_level1_slab_overflow_falls_back_to_two_passes(gpu_lib, n_ranks, fm):
+_L1_OVERFLOW = [(2, 0, 1), (4, 1, 1)] + ([(4, 0, 1), (2, 1, 1)] if os.environ.get("BFC_TEST_MORE") else []) + [(2, 0, 0)]
+
+
+@pytest.mark.parametrize("n_ranks,fm,lazy", _L1_OVERFLOW, ids=["%d-%d%s" % (n, f, "" if z else "-lazy0") for n, f, z in _L1_OVERFLOW])
+def test_group_level1_slab_overflow_falls_back_to_two_passes(gpu_lib, n_ranks, fm, lazy, monkeypatch):
     """Stage A of a rank is one pass into slabs (round 4).  First a clean global batch (100 000 reads of a 50 Mbp genome: slab mode stays on), then
     200 000 reads of a 400-base genome -- few, often repeated k-mers overflow a level-1 slab on some rank: EVERY rank repeats its stage A of
     that batch through the two-pass partition (its k-mers are not counted twice), the exchange carries exact bucket sizes again, the run stays
-    with two passes until the reset -- and a third, clean batch behind it: the oracle's filter(s), statistics and table throughout."""
+    with two passes until the reset -- and a third, clean batch behind it: the oracle's filter(s), statistics and table throughout.
+    lazy=0 (BFCG_MG_LAZY=0): the same through round 4's protocol, where the host has stage A's sizes -- and the overflow -- before the exchange."""
+    if not lazy:
+        monkeypatch.setenv("BFCG_MG_LAZY", "0")
     rng = np.random.default_rng(900 + n_ranks + fm)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
     L = 150
@@ -304,18 +311,23 @@ def test_group_level1_slab_overflow_falls_back_to_two_passes(gpu_lib, n_ranks, f
     grp.close(); oc.close()
 
 
-@pytest.mark.parametrize("fm", [0, 1])
-def test_group_overloaded_ranks_process_sources_in_groups(gpu_lib, g1, fm):
+@pytest.mark.parametrize("fm,slabs", [(0, None), (1, None), (0, 0)], ids=["0", "1", "0-slabs0"])
+def test_group_overloaded_ranks_process_sources_in_groups(gpu_lib, g1, fm, slabs, monkeypatch):
     """-b24 over 4 ranks: 32 bloom regions per rank take ~80 000 k-mers per pass at full speed, a global batch brings each rank 200 000.  The
     first batch (empty filter) is applied in groups of sources -- several stage B passes per rank, the result that of one batch because the
     receive buffer is source-major and file order rank-major; the later ones (most k-mers seen again: a region takes three times as many) in
-    fewer passes.  No region on the slow path, and the oracle's filter(s), statistics and table."""
+    fewer passes.  No region on the slow path, and the oracle's filter(s), statistics and table.
+    slabs=0 (BFCG_MG_SLABS=0): two-pass batches with exact buckets, where a group of sources begins at its accumulated offset in the receive buffer."""
+    if slabs is not None:
+        monkeypatch.setenv("BFCG_MG_SLABS", str(slabs))
     rs, (seq, qual, off) = g1
     k, b, N = 31, 24, 4
     oc = _oracle(k, b, seq, qual, off, filter_mode=fm)
     n = rs.n_reads
     per = n // 3 + 1
     grp = gpu_lib.GpuGroup(k, b, [0] * N, max_batch_pos=per * (rs.L + 1) // N + 4096, filter_mode=fm)
+    if slabs == 0:
+        assert grp.info()["slab_mode"] == 0
     launches = []
     for a in range(0, n, per):
         e = min(n, a + per)
