@@ -13,10 +13,12 @@ import numpy as np
 import pytest
 
 import oracle
+from ec_corpus import KS, conditions, corpus, count_set, edge_reads, histogram, write_reads
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 GOLD = json.load(open(os.path.join(HERE, "golden", "ec_goldens.json")))
+PATHS_GOLD = os.path.join(HERE, "golden", "ec_paths_goldens.json")  # read by its test: make_ec_paths_goldens.py imports this module to write it
 BFC_REF = os.path.join(oracle.REF_DIR, "bfc-ref")
 REF_EC = os.path.join(oracle.REF_DIR, "libbfcref_ec.so")
 needs_ref = pytest.mark.skipif(not (os.path.exists(BFC_REF) and os.path.exists(REF_EC)),
@@ -74,86 +76,13 @@ def host_correct(dump, fn, opts):
     return out, a, a2
 
 
-def write_reads(fn, seqs, quals=None):
-    with open(fn, "wb") as f:
-        for i, s in enumerate(seqs):
-            if quals is None:
-                f.write(b">r%d\n%s\n" % (i, s))
-            else:
-                f.write(b"@r%d c%d\n%s\n+\n%s\n" % (i, i, s, quals[i]))
-
-
-def _genome(rng, G):
-    return bytes(b"ACGT"[c] for c in rng.integers(0, 4, G))
-
-
-def count_file(rng, genome, n, L=120, err=0.004):
-    """reads from both strands at high coverage: the table the corrections are checked with"""
-    comp = bytes.maketrans(b"ACGT", b"TGCA")
-    out = []
-    for _ in range(n):
-        p = int(rng.integers(0, len(genome) - L))
-        s = bytearray(genome[p:p + L])
-        for j in np.nonzero(rng.random(L) < err)[0]:
-            s[j] = b"ACGT"[int(rng.integers(0, 4))]
-        s = bytes(s)
-        out.append(s.translate(comp)[::-1] if rng.random() < 0.5 else s)
-    return out
-
-
-def edge_reads(rng, genome, k):
-    """every path of bfc_ec1: clean and erroneous reads, reads shorter than k, N-rich reads, N runs inside solid stretches, reads with no
-    solid k-mer (errors every k/2 bases: the brute path), lower case and IUPAC codes, random reads"""
-    G = len(genome)
-    reads = []
-
-    def pick(L):
-        p = int(rng.integers(0, G - L))
-        return bytearray(genome[p:p + L])
-    for _ in range(60):                                         # sequencing errors, 0-6 per read, some close together
-        s = pick(int(rng.integers(k + 5, 250)))
-        for _ in range(int(rng.integers(0, 7))):
-            s[int(rng.integers(0, len(s)))] = b"ACGT"[int(rng.integers(0, 4))]
-        reads.append(s)
-    for _ in range(10):
-        reads.append(pick(int(rng.integers(1, k))))             # shorter than k
-    for _ in range(10):                                         # N-rich
-        s = pick(150)
-        for j in rng.integers(0, 150, 12):
-            s[j] = ord("N")
-        reads.append(s)
-    for _ in range(15):                                         # one N or a short N run inside
-        s = pick(200)
-        j = int(rng.integers(k, 200 - k))
-        s[j:j + int(rng.integers(1, 4))] = b"N" * 3
-        reads.append(s[:200])
-    for _ in range(20):                                         # no solid k-mer: an error every k/2 bases
-        s = pick(int(rng.integers(k + 2, 2 * k + 10)))
-        for j in range(int(rng.integers(0, k // 2)), len(s), max(2, k // 2)):
-            s[j] = b"ACGT"[(b"ACGT".index(s[j]) + 1) % 4]
-        reads.append(s)
-    for _ in range(10):                                         # lower case, IUPAC codes
-        s = pick(180)
-        s[int(rng.integers(0, 180))] = b"RYKMSWBDHVN"[int(rng.integers(0, 11))]
-        if rng.random() < 0.5:
-            s = bytearray(bytes(s).lower())
-        else:
-            s[10:60] = bytes(s[10:60]).lower()
-        reads.append(s)
-    for _ in range(5):
-        reads.append(bytearray(b"ACGT"[c] for c in rng.integers(0, 4, 150)))
-    return [bytes(s) for s in reads]
-
-
 @pytest.fixture(scope="module")
 def edge_env(tmp_path_factory):
     """one genome, one counting file, one dump per k, one file of edge reads per k"""
     d = tmp_path_factory.mktemp("ec_host")
-    rng = np.random.default_rng(11)
-    genome = _genome(rng, 4000)
+    rng, genome, reads, quals = count_set()
     cnt = str(d / "count.fq")
-    reads = count_file(rng, genome, 1500)
-    write_reads(cnt, reads, [bytes(rng.integers(40, 74, len(s)).astype(np.uint8)) for s in reads])
+    write_reads(cnt, reads, quals)
     return d, rng, genome, cnt
 
 
@@ -193,6 +122,53 @@ def test_edge_reads_vs_reference(edge_env, k):
     assert {0, 2, 3} <= codes, codes                            # corrected, MANY_N, NO_SOLID
     assert (aux >> 3 & 1).any()                                 # the brute path took a read
     assert (aux >> 18).sum() > 20                               # bases changed
+
+
+@pytest.fixture(scope="module")
+def corpus_tables(tmp_path_factory):
+    """the counting file's table per k without the reference: counted by the CPU restatement (oracle.Counter, held to the reference's
+    table by tests/test_oracle.py), dumped in bfc_ch_dump's format"""
+    d = tmp_path_factory.mktemp("ec_paths")
+    _, genome, reads, quals = count_set()
+    off = np.zeros(len(reads) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(s) for s in reads])
+    seq, qual = np.frombuffer(b"".join(reads), dtype=np.uint8), np.frombuffer(b"".join(quals), dtype=np.uint8)
+    made = {}
+
+    def get(k):
+        if k not in made:
+            c = oracle.Counter(k, 22)
+            c.count(seq, qual, off)
+            made[k] = str(d / ("k%d.hash" % k))
+            c.dump(made[k])
+            c.close()
+        return made[k]
+    return d, genome, get
+
+
+@pytest.mark.parametrize("fmt", ["fq", "fa"])
+@pytest.mark.parametrize("k", KS)
+def test_corpus_paths_golden(corpus_tables, edge_env, k, fmt):
+    """edge_reads + exit_reads (ec_corpus.corpus) through the host instance: the bytes of the reference's bfc_correct as recorded in
+    tests/golden/ec_paths_goldens.json, its reads per ec_code and its brute count; the corpus reaches ec_code 0, 2, 3, 4 and 5 and the
+    brute path (ec_corpus.conditions).  Where oracle/_ref is built, the live reference on its own table gives the same bytes."""
+    d, genome, table = corpus_tables
+    g = json.load(open(PATHS_GOLD))["k%d_%s" % (k, fmt)]
+    seqs, quals = corpus(genome, k)
+    fn = str(d / ("corpus_k%d.%s" % (k, fmt)))
+    write_reads(fn, seqs, quals if fmt == "fq" else None)
+    got, aux, aux2 = host_correct(table(k), fn, {"k": k})
+    hist, brute = histogram(aux)
+    print("k %d %s: ec_code histogram %s, brute %d" % (k, fmt, hist, brute))
+    assert hashlib.md5(got).hexdigest() == g["stdout_md5"]
+    conditions(aux)
+    assert len(seqs) == g["n_reads"] and hist == g["ec_code_hist"]
+    assert int(((aux >> 3 & 1 == 1) & (aux & 7 == 0)).sum()) == g["brute_code0"]
+    if os.path.exists(BFC_REF) and os.path.exists(REF_EC):
+        dump = str(edge_env[0] / ("k%d.hash" % k))
+        if not os.path.exists(dump):
+            ref_dump(edge_env[3], k, dump)
+        assert got == ref_correct(dump, fn, {"k": k})
 
 
 @needs_ref
