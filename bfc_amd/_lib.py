@@ -168,6 +168,11 @@ SYMBOLS = {
     "bfcg_kmers_read_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
     "bfcg_read_stats_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]),
     "bfcg_read_stats_format": (C.c_uint64, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_kmers_joint_hist": (C.c_int, [C.c_void_p, C.c_void_p, u64p, u64p]),
+    "bfcg_kmers_list_vs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "bfcg_kmers_union": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "bfcg_kmers_export": (C.c_void_p, [C.c_void_p, u64p]),
+    "bfcg_kmers_format_vs": (C.c_uint64, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "bfcg_hash_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_seen_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
 }

@@ -743,9 +743,93 @@ class GpuKmers:
         self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
         return out
 
+    # ---- two tables (bfcg_tabcmp.hip): `other` is a GpuKmers of the same k and l_pre on the same device, of either form; self is allowed
+
+    @classmethod
+    def _adopt(cls, t, keep):
+        """A GpuKmers around a bfcg_kmers_t the library made (a union); `keep` is what must outlive it."""
+        self = cls.__new__(cls)
+        self.L, self._keep, self.t = _lib.load(), keep, t
+        info = (C.c_int * 3)()
+        self.L.bfcg_kmers_info(self.t, info)
+        self.k, self.l_pre, self.cshift = info[0], info[1], info[2]
+        self._ms, self.n_found = float(self.L.bfcg_kmers_last_ms(t)), 0
+        return self
+
+    def joint_hist(self, other):
+        """(joint u64 (256, 256), shared, only_self, only_other): joint[i, j] = the keys counted i times here and j times in `other`,
+        0 = absent (joint[0, 0] is 0).  Every k up to 63."""
+        joint, n = np.zeros((256, 256), dtype=np.uint64), (C.c_uint64 * 3)()
+        if self.L.bfcg_kmers_joint_hist(self.t, other.t, joint.ctypes.data_as(u64p), n) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return joint, int(n[0]), int(n[1]), int(n[2])
+
+    def list_vs_raw(self, other, min_cnt, min_diff, other_min, other_max, sub_lo, sub_hi, cap):
+        """One bfcg_kmers_list_vs call: (rc, n, y (cap, 2) u64, cnt_high u16 (cap), other i16 (cap))."""
+        y, ch, oth = np.zeros((cap, 2), dtype=np.uint64), np.zeros(cap, dtype=np.uint16), np.zeros(cap, dtype=np.int16)
+        n = C.c_uint64()
+        rc = self.L.bfcg_kmers_list_vs(self.t, other.t, int(min_cnt), int(min_diff), int(other_min), int(other_max), int(sub_lo), int(sub_hi),
+                                       y.ctypes.data, ch.ctypes.data, oth.ctypes.data, cap, C.byref(n))
+        if rc < 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        return rc, int(n.value), y, ch, oth
+
+    def pieces_vs(self, other, min_cnt=0, min_diff=0, other_min=0, other_max=255, sub_lo=0, sub_hi=None, piece=1 << 24, sizes=None):
+        """pieces() against `other`: yields (y, cnt_high, other i16) per piece of whole sub-tables, each sized from this table's
+        sub-table sizes (an upper bound: the filters only drop)."""
+        sub_hi = (1 << self.l_pre) if sub_hi is None else sub_hi
+        self.list_vs_raw(other, min_cnt, min_diff, other_min, other_max, sub_lo, sub_lo, 0)  # an empty range: the library's refusals, before any work
+        ends = np.cumsum((self.sub_sizes() if sizes is None else sizes)[sub_lo:sub_hi], dtype=np.uint64)
+        max_subs = max(1, self.MAX_SLOTS >> self.cshift)
+        self._ms, lo, done = 0.0, sub_lo, 0
+        while lo < sub_hi:
+            hi = sub_lo + int(np.searchsorted(ends, done + piece, side="right"))
+            hi = min(max(hi, lo + 1), lo + max_subs, sub_hi)
+            cap = int(ends[hi - 1 - sub_lo]) - done
+            rc, n, y, ch, oth = self.list_vs_raw(other, min_cnt, min_diff, other_min, other_max, lo, hi, cap)
+            if rc != 0:
+                raise BfcGpuError("sub-tables [%d, %d) hold %d k-mers, their sizes said %d: the table changed under the listing" % (lo, hi, n, cap))
+            self._ms += float(self.L.bfcg_kmers_last_ms(self.t))
+            yield y[:n], ch[:n], oth[:n]
+            lo, done = hi, done + cap
+
+    def list_vs(self, other, min_cnt=0, min_diff=0, other_min=0, other_max=255, sub_lo=0, sub_hi=None, piece=1 << 24):
+        """list() with the k-mers' counts in `other`: (y (n, 2) u64, count u8, high u8, other i16).  A k-mer is kept only if its count in
+        `other` (0 where absent) lies in [other_min, other_max]: (0, 0) private to this table, (1, 255) shared, (0, 255) everything;
+        other[i] is what other.lookup(y[i]) answers, -1 or high << 8 | count."""
+        parts = list(self.pieces_vs(other, min_cnt, min_diff, other_min, other_max, sub_lo, sub_hi, piece))
+        y = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 2), dtype=np.uint64)
+        ch = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.uint16)
+        oth = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, dtype=np.int16)
+        return y, (ch & 0xff).astype(np.uint8), (ch >> 8).astype(np.uint8), oth
+
+    def format_vs(self, y, cnt_high, other):
+        """The lines of a piece of list_vs, "kmer count high count_in_other high_in_other", formatted in C: bytes."""
+        y, cnt_high = np.ascontiguousarray(y, dtype=np.uint64), np.ascontiguousarray(cnt_high, dtype=np.uint16)
+        other = np.ascontiguousarray(other, dtype=np.int16)
+        buf = C.create_string_buffer(max(1, len(cnt_high) * (self.k + 16)))
+        n = self.L.bfcg_kmers_format_vs(self.k, y.ctypes.data, cnt_high.ctypes.data, other.ctypes.data, len(cnt_high), buf)
+        return buf.raw[:n]
+
+    def union(self, other):
+        """A new GpuKmers that owns its table: every key of either table, the counts of a key in both added, saturating at 255 / 63
+        (bfc_ch_union).  Its last_ms() is the time of the call's kernels."""
+        t = self.L.bfcg_kmers_union(self.t, other.t)
+        if not t:
+            raise BfcGpuError("bfcg_kmers_union failed: " + self.L.bfcg_last_error().decode())
+        return GpuKmers._adopt(t, None)
+
+    def to_host(self):
+        """The table as a HostTable (one copy, no order stamps): to dump, to correct with, to ask with get()."""
+        p = self.L.bfcg_kmers_export(self.t, None)
+        if not p:
+            raise BfcGpuError("bfcg_kmers_export failed: " + self.L.bfcg_last_error().decode())
+        return HostTable(p)
+
     def last_ms(self):
         """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces,
-        read_stats() its two kernels."""
+        read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces; of a union() result, its size passes and fill."""
         return self._ms
 
 

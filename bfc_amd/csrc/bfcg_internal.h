@@ -44,6 +44,10 @@ struct bfcg_kmers {
 	ulonglong2 *d_qy; int16_t *d_qout; uint64_t q_cap;              // a lookup's staging, q_cap k-mers a piece (BFCG_LOOKUP_CAP at creation), allocated by the first lookup
 	uint8_t *d_pseq; uint64_t pseq_cap; int16_t *d_pout; uint64_t pout_cap; // a profile's stream and result (grown on demand)
 	unsigned long long *d_roff; uint64_t roff_cap; int32_t *d_rout; uint64_t rout_cap; // the reads' offsets and eight words per read of bfcg_kmers_read_stats (bfcg_readstats.hip; grown on demand)
+	int16_t *d_oth; uint64_t oth_cap;   // a listing's third column, what the other table answered (bfcg_tabcmp.hip; grown on demand, in bytes)
+	uint32_t *d_jpart; uint64_t jpart_cap; // the 128 x 128 corner of a joint spectrum per workgroup (bfcg_tabcmp.hip; grown on demand, in bytes)
+	unsigned long long *d_joint;        // 256 x 256 bins of a joint spectrum and the two counters of a union (bfcg_tabcmp.hip; allocated by the first call)
+	uint64_t n_keys; int has_keys;      // the keys of a table this object built and owns (bfcg_kmers_union counts them on the device)
 	float last_ms;
 };
 
@@ -186,6 +190,8 @@ BFCG_LOCAL double mg_warm_factor(::bfcg_ctx *c); // times the cold limit this ra
 // a coverage pass's table, probe parameters and device, for the corrector behind it (bfcg_query.hip)
 const unsigned long long *kcov_table(::bfcg_kcov *t, KParams *P, int *device);
 int kcov_adopted(::bfcg_kcov *t);
+// a read-out object without a table yet (bfcg_kmers.hip): stream, events, the histogram's and the sizes' buffers; NULL with the message set
+BFCG_LOCAL ::bfcg_kmers *kmers_new(int k, int l_pre, int cshift, int device);
 // k-mers a lookup stages per piece (bfcg_lookup.hip): a few million, or what BFCG_LOOKUP_CAP says
 BFCG_LOCAL uint64_t lookup_cap();
 // a profile's first half (bfcg_lookup.hip): the stream staged in d_pseq if it is the host's, d_pout grown, t->e0 recorded and k_profile launched

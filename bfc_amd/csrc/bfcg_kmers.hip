@@ -5,9 +5,8 @@
 // 0 = empty.  Both kernels stream it once, 16 bytes per lane:
 //   k_tab_hist   the 256 + 64 bins in LDS (eight copies per wave: the spectrum is peaked, neighbouring lanes hit the same bin), flushed
 //                with 64-bit atomics; the non-empty slots of every region in the same pass (wave ballots)
-//   k_tab_list   a range of sub-tables in blocks of LIST_BLK slots: k_list_count counts the slots that pass the filter per block,
-//                k_list_scan turns the counts into offsets, k_list_emit decodes (bfcg_kdec.h) and stores in slot order -- sub-tables
-//                ascending, because a sub-table is a contiguous run of slots
+//   k_tab_list   a range of sub-tables in blocks of LIST_BLK slots, count / scan / emit: bfcg_klist.h, shared with bfcg_tabcmp.hip's
+//                listing against a second table
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -17,14 +16,11 @@
 #include "bfcg_internal.h"
 #include "bfc_host.h"
 #include "bfcg_kdec.h"
+#include "bfcg_klist.h"
 
 namespace {
 
-enum { BT = 256, WAVES = BT / 64, HIST_BINS = 256 + 64, HIST_COPIES = 8 /* per wave */, HIST_UNROLL = 4 };
-enum { LIST_STEPS = 8, LIST_WAVE = LIST_STEPS * 128 /* slots a wave owns */, LIST_BLK = WAVES * LIST_WAVE /* slots per workgroup: 4096 */ };
-enum { SCAN_BT = 1024, SCAN_PER = 8 };
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
+enum { HIST_BINS = 256 + 64, HIST_COPIES = 8 /* per wave */, HIST_UNROLL = 4 }; // BT, WAVES, lane_id: bfcg_klist.h
 
 // ---- k_tab_hist -----------------------------------------------------------------------------------------------------------------
 // A wave owns one contiguous span of slots (a multiple of 128 * HIST_UNROLL) and walks it 128 slots at a time, lane l holding slots
@@ -83,113 +79,6 @@ __global__ __launch_bounds__(BT) void k_tab_hist(const ulonglong2 *__restrict__ 
 	}
 }
 
-// ---- k_tab_list -----------------------------------------------------------------------------------------------------------------
-// Slots [s_lo, s_hi) of the table in blocks of LIST_BLK, block 0 starting at s_lo rounded down to a pair; a wave owns LIST_WAVE
-// consecutive slots of its block, a lane slots 2l, 2l + 1 of each of its LIST_STEPS steps.
-struct ListGeom { uint64_t s_lo, s_hi, base; int k, l_pre, cshift, min_cnt, min_diff; };
-
-__device__ __forceinline__ void list_load(const ulonglong2 *__restrict__ tab, const ListGeom &G, uint64_t wave_first, ulonglong2 v[LIST_STEPS])
-{
-	const int lane = lane_id();
-#pragma unroll
-	for (int j = 0; j < LIST_STEPS; ++j) {
-		const uint64_t s = wave_first + (uint64_t)j * 128 + 2 * lane; // even
-		ulonglong2 w = make_ulonglong2(0, 0);
-		if (s < G.s_hi) w = tab[s >> 1];   // s_hi is even or the table's end is beyond it: the pair lies inside the table
-		if (s < G.s_lo || !kdec::keep(w.x, G.min_cnt, G.min_diff)) w.x = 0;
-		if (s + 1 < G.s_lo || s + 1 >= G.s_hi || !kdec::keep(w.y, G.min_cnt, G.min_diff)) w.y = 0;
-		v[j] = w;
-	}
-}
-
-__global__ __launch_bounds__(BT) void k_list_count(const ulonglong2 *__restrict__ tab, ListGeom G, uint32_t *__restrict__ blk_cnt)
-{
-	__shared__ uint32_t wsum[WAVES];
-	const int wave = threadIdx.x >> 6;
-	ulonglong2 v[LIST_STEPS];
-	list_load(tab, G, G.base + (uint64_t)blockIdx.x * LIST_BLK + (uint64_t)wave * LIST_WAVE, v);
-	uint32_t n = 0;
-#pragma unroll
-	for (int j = 0; j < LIST_STEPS; ++j) n += __popcll(__ballot(v[j].x != 0)) + __popcll(__ballot(v[j].y != 0));
-	if (lane_id() == 0) wsum[wave] = n;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint32_t s = 0;
-		for (int w = 0; w < WAVES; ++w) s += wsum[w];
-		blk_cnt[blockIdx.x] = s;
-	}
-}
-
-// exclusive scan of cnt[0, n_pad) (n_pad a multiple of SCAN_BT * SCAN_PER, the padding zero) into 64-bit offsets; off[n_pad] = total.  One workgroup:
-// the array has one entry per 4096 slots.
-__global__ __launch_bounds__(SCAN_BT) void k_list_scan(const uint32_t *__restrict__ cnt, uint64_t n_pad, unsigned long long *__restrict__ off)
-{
-	__shared__ unsigned long long wtot[SCAN_BT / 64];
-	__shared__ unsigned long long carry_s;
-	const int lane = lane_id(), wave = threadIdx.x >> 6;
-	unsigned long long carry = 0;
-	for (uint64_t base = 0; base < n_pad; base += SCAN_BT * SCAN_PER) {
-		const uint64_t i0 = base + (uint64_t)threadIdx.x * SCAN_PER;
-		uint32_t c[SCAN_PER];
-		unsigned long long mine = 0;
-#pragma unroll
-		for (int j = 0; j < SCAN_PER; ++j) { c[j] = cnt[i0 + j]; mine += c[j]; }
-		unsigned long long incl = mine; // inclusive scan over the wave
-#pragma unroll
-		for (int d = 1; d < 64; d <<= 1) {
-			const unsigned long long o = __shfl_up(incl, d, 64);
-			if (lane >= d) incl += o;
-		}
-		if (lane == 63) wtot[wave] = incl;
-		__syncthreads();
-		unsigned long long before = carry;
-		for (int w = 0; w < wave; ++w) before += wtot[w];
-		if (threadIdx.x == SCAN_BT - 1) carry_s = before + incl;
-		unsigned long long o = before + incl - mine;
-#pragma unroll
-		for (int j = 0; j < SCAN_PER; ++j) { off[i0 + j] = o; o += c[j]; }
-		__syncthreads();
-		carry = carry_s;
-	}
-	if (threadIdx.x == 0) off[n_pad] = carry;
-}
-
-__global__ __launch_bounds__(BT) void k_list_emit(const ulonglong2 *__restrict__ tab, ListGeom G, const unsigned long long *__restrict__ blk_off,
-                                                  ulonglong2 *__restrict__ out_y, uint16_t *__restrict__ out_ch, uint64_t cap)
-{
-	__shared__ uint32_t wsum[WAVES];
-	const int lane = lane_id(), wave = threadIdx.x >> 6;
-	const uint64_t wave_first = G.base + (uint64_t)blockIdx.x * LIST_BLK + (uint64_t)wave * LIST_WAVE;
-	ulonglong2 v[LIST_STEPS];
-	list_load(tab, G, wave_first, v);
-	uint64_t bx[LIST_STEPS], by[LIST_STEPS];
-	uint32_t n = 0;
-#pragma unroll
-	for (int j = 0; j < LIST_STEPS; ++j) { bx[j] = __ballot(v[j].x != 0); by[j] = __ballot(v[j].y != 0); n += __popcll(bx[j]) + __popcll(by[j]); }
-	if (lane == 0) wsum[wave] = n;
-	__syncthreads();
-	uint64_t pos = blk_off[blockIdx.x];
-	for (int w = 0; w < wave; ++w) pos += wsum[w];
-	const uint64_t below = (1ULL << lane) - 1;
-#pragma unroll
-	for (int j = 0; j < LIST_STEPS; ++j) {
-		const uint64_t s = wave_first + (uint64_t)j * 128 + 2 * lane;
-		uint64_t o = pos + __popcll(bx[j] & below) + __popcll(by[j] & below); // slot order: lane-major, x before y
-		if (v[j].x) {
-			uint64_t a, b;
-			kdec::decode(G.k, G.l_pre, (uint32_t)(s >> G.cshift), v[j].x, a, b);
-			if (o < cap) { out_y[o] = make_ulonglong2(a, b); out_ch[o] = (uint16_t)(v[j].x & 0x3fff); }
-			++o;
-		}
-		if (v[j].y) {
-			uint64_t a, b;
-			kdec::decode(G.k, G.l_pre, (uint32_t)((s + 1) >> G.cshift), v[j].y, a, b);
-			if (o < cap) { out_y[o] = make_ulonglong2(a, b); out_ch[o] = (uint16_t)(v[j].y & 0x3fff); }
-		}
-		pos += __popcll(bx[j]) + __popcll(by[j]);
-	}
-}
-
 } // namespace
 
 // ---- the context ------------------------------------------------------------------------------------------------------------------
@@ -198,7 +87,7 @@ __global__ __launch_bounds__(BT) void k_list_emit(const ulonglong2 *__restrict__
 
 // a failure after the calloc frees what was made so far (bfcg_kmers_destroy takes a half-built object)
 
-static bfcg_kmers_t *kmers_new(int k, int l_pre, int cshift, int device)
+bfcg_kmers_t *bfcg::kmers_new(int k, int l_pre, int cshift, int device)
 {
 	if (l_pre + cshift < 1 || l_pre + cshift > 40) { bfcg::fail("a count table of 2^%d slots cannot be read out", l_pre + cshift); return NULL; }
 	BFCG_CKN((void)0, hipSetDevice(device));
@@ -218,7 +107,7 @@ extern "C" bfcg_kmers_t *bfcg_kmers_create(const bfc_ch_t *ch, int device)
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { bfcg::fail("no HIP device available: the table read-out has no CPU fallback here"); return NULL; }
 	if (!ch || device < 0 || device >= ndev) { bfcg::fail("bad arguments to bfcg_kmers_create"); return NULL; }
-	bfcg_kmers_t *t = kmers_new(bfc_ch_get_k(ch), bfc_ch_get_lpre(ch), bfc_ch_raw_cshift(ch), device);
+	bfcg_kmers_t *t = bfcg::kmers_new(bfc_ch_get_k(ch), bfc_ch_get_lpre(ch), bfc_ch_raw_cshift(ch), device);
 	if (!t) return NULL;
 	const uint64_t bytes = 8ULL << (t->l_pre + t->cshift);
 	unsigned long long *tab = NULL;
@@ -234,7 +123,7 @@ extern "C" bfcg_kmers_t *bfcg_kmers_attach(bfcg_ctx_t *c)
 	bfcg::KParams P; int device;
 	const unsigned long long *tab = bfcg::ctx_borrow_table(c, &P, &device);
 	if (!tab) return NULL;
-	bfcg_kmers_t *t = kmers_new(P.k, P.l_pre, P.tab_cshift, device);
+	bfcg_kmers_t *t = bfcg::kmers_new(P.k, P.l_pre, P.tab_cshift, device);
 	if (!t) return NULL;
 	t->table = tab;
 	return t;
@@ -248,6 +137,7 @@ extern "C" void bfcg_kmers_destroy(bfcg_kmers_t *t)
 	if (t->owns_table) (void)hipFree((void *)t->table);
 	(void)hipFree(t->d_hist); (void)hipFree(t->d_sizes); (void)hipFree(t->d_cnt); (void)hipFree(t->d_off); (void)hipFree(t->d_y); (void)hipFree(t->d_ch);
 	(void)hipFree(t->d_qy); (void)hipFree(t->d_qout); (void)hipFree(t->d_pseq); (void)hipFree(t->d_pout); (void)hipFree(t->d_roff); (void)hipFree(t->d_rout);
+	(void)hipFree(t->d_oth); (void)hipFree(t->d_joint); (void)hipFree(t->d_jpart);
 	if (t->e0) (void)hipEventDestroy(t->e0);
 	if (t->e1) (void)hipEventDestroy(t->e1);
 	if (t->st) (void)hipStreamDestroy(t->st);
@@ -311,52 +201,7 @@ extern "C" int bfcg_kmers_sub_sizes(bfcg_kmers_t *t, uint32_t *sizes)
 extern "C" int bfcg_kmers_list(bfcg_kmers_t *t, int min_cnt, int min_diff, uint32_t sub_lo, uint32_t sub_hi, uint64_t *y, uint16_t *cnt_high, uint64_t cap, uint64_t *n)
 {
 	if (!t || !n) return bfcg::fail("bad arguments to bfcg_kmers_list");
-	if (!kdec::decodable(t->k)) return bfcg::fail("k-mers cannot be listed for k=%d: the table's key is lossless only for k <= %d (sizes and histogram work for any k)", t->k, (int)kdec::MAX_K);
-	if (sub_lo > sub_hi || (uint64_t)sub_hi > 1ULL << t->l_pre) return bfcg::fail("sub-table range [%u, %u) outside [0, 2^%d]", sub_lo, sub_hi, t->l_pre);
-	if (cap && (!y || !cnt_high)) return bfcg::fail("bfcg_kmers_list needs output buffers for cap=%llu", (unsigned long long)cap);
-	*n = 0; t->last_ms = 0;
-	if (sub_lo == sub_hi) return 0;
-	BFCG_CK(hipSetDevice(t->device));
-	ListGeom G;
-	G.s_lo = (uint64_t)sub_lo << t->cshift; G.s_hi = (uint64_t)sub_hi << t->cshift; G.base = G.s_lo & ~1ULL;
-	G.k = t->k; G.l_pre = t->l_pre; G.cshift = t->cshift; G.min_cnt = min_cnt; G.min_diff = min_diff;
-	const uint64_t n_blk = (G.s_hi - G.base + LIST_BLK - 1) / LIST_BLK, per = SCAN_BT * SCAN_PER, n_pad = (n_blk + per - 1) / per * per;
-	if (n_blk >= 1ULL << 24) return bfcg::fail("sub-table range of %llu slots is too large for one listing: walk it in pieces", (unsigned long long)(G.s_hi - G.s_lo)); // a launch has fewer than 2^32 threads
-	if (n_pad > t->blk_cap) {
-		(void)hipFree(t->d_cnt); (void)hipFree(t->d_off); t->d_cnt = NULL; t->d_off = NULL; t->blk_cap = 0;
-		BFCG_CK(hipMalloc(&t->d_cnt, n_pad * 4)); BFCG_CK(hipMalloc(&t->d_off, (n_pad + 1) * 8));
-		t->blk_cap = n_pad;
-	}
-	float ms1 = 0, ms2 = 0;
-	if (n_pad > n_blk) BFCG_CK(hipMemsetAsync(t->d_cnt + n_blk, 0, (n_pad - n_blk) * 4, t->st)); // the scan's padding
-	BFCG_CK(hipEventRecord(t->e0, t->st));
-	hipLaunchKernelGGL(k_list_count, dim3((unsigned)n_blk), dim3(BT), 0, t->st, (const ulonglong2 *)t->table, G, t->d_cnt);
-	hipLaunchKernelGGL(k_list_scan, dim3(1), dim3(SCAN_BT), 0, t->st, t->d_cnt, n_pad, t->d_off);
-	BFCG_CK(hipEventRecord(t->e1, t->st));
-	BFCG_CK(hipGetLastError());
-	unsigned long long total = 0;
-	BFCG_CK(hipMemcpyAsync(&total, t->d_off + n_pad, 8, hipMemcpyDeviceToHost, t->st));
-	BFCG_CK(hipStreamSynchronize(t->st));
-	BFCG_CK(hipEventElapsedTime(&ms1, t->e0, t->e1));
-	t->last_ms = ms1;
-	*n = total;
-	if (total > cap) return 1; // nothing is written: the caller comes back with room for *n
-	if (total == 0) return 0;
-	if (total > t->out_cap) {
-		(void)hipFree(t->d_y); (void)hipFree(t->d_ch); t->d_y = NULL; t->d_ch = NULL; t->out_cap = 0;
-		BFCG_CK(hipMalloc(&t->d_y, total * 16)); BFCG_CK(hipMalloc(&t->d_ch, total * 2));
-		t->out_cap = total;
-	}
-	BFCG_CK(hipEventRecord(t->e0, t->st));
-	hipLaunchKernelGGL(k_list_emit, dim3((unsigned)n_blk), dim3(BT), 0, t->st, (const ulonglong2 *)t->table, G, t->d_off, t->d_y, t->d_ch, (uint64_t)total);
-	BFCG_CK(hipEventRecord(t->e1, t->st));
-	BFCG_CK(hipGetLastError());
-	BFCG_CK(hipMemcpyAsync(y, t->d_y, total * 16, hipMemcpyDeviceToHost, t->st));
-	BFCG_CK(hipMemcpyAsync(cnt_high, t->d_ch, total * 2, hipMemcpyDeviceToHost, t->st));
-	BFCG_CK(hipStreamSynchronize(t->st));
-	BFCG_CK(hipEventElapsedTime(&ms2, t->e0, t->e1));
-	t->last_ms = ms1 + ms2;
-	return 0;
+	return list_run(t, "bfcg_kmers_list", NoOther(), min_cnt, min_diff, sub_lo, sub_hi, y, cnt_high, NULL, cap, n);
 }
 
 extern "C" float bfcg_kmers_last_ms(bfcg_kmers_t *t) { return t ? t->last_ms : 0.0f; }
@@ -397,6 +242,24 @@ extern "C" uint64_t bfcg_kmers_format(int k, const uint64_t *y, const uint16_t *
 		p += k; *p++ = '\t';
 		p = put_u32(p, cnt_high[i] & 0xff); *p++ = '\t';
 		p = put_u32(p, cnt_high[i] >> 8 & 0x3f); *p++ = '\n';
+	}
+	return (uint64_t)(p - buf);
+}
+
+// a listing against a second table (bfcg_kmers_list_vs), "%s\t%d\t%d\t%d\t%d\n" per k-mer: count, high, and the two in the other table
+// (0 0 where it is absent there), into buf (n * (k + 16) bytes at most); returns the bytes written
+extern "C" uint64_t bfcg_kmers_format_vs(int k, const uint64_t *y, const uint16_t *cnt_high, const int16_t *other, uint64_t n, char *buf)
+{
+	char *p = buf;
+	for (uint64_t i = 0; i < n; ++i) {
+		const uint64_t a = y[2 * i], b = y[2 * i + 1];
+		const uint32_t o = other[i] < 0 ? 0 : (uint32_t)other[i];
+		for (int l = 0; l < k; ++l) p[k - 1 - l] = "ACGT"[(b >> l & 1) << 1 | (a >> l & 1)];
+		p += k; *p++ = '\t';
+		p = put_u32(p, cnt_high[i] & 0xff); *p++ = '\t';
+		p = put_u32(p, cnt_high[i] >> 8 & 0x3f); *p++ = '\t';
+		p = put_u32(p, o & 0xff); *p++ = '\t';
+		p = put_u32(p, o >> 8 & 0x3f); *p++ = '\n';
 	}
 	return (uint64_t)(p - buf);
 }

@@ -391,6 +391,25 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *                         n_reads = 0 or n_pos = 0: 0, nothing written.  On either form of the object, for every k up to 63;
  *                         bfcg_kmers_last_ms covers both kernels.  One wavefront walks one read: made for reads of 50 to 300 bases; a
  *                         megabase contig comes out right, at the pace of one wave.
+ * Two tables compared and merged (bfcg_tabcmp.hip).  a and b are two objects of either form, in any mix, of equal k and l_pre on one
+ * device (cshift may differ; a == b is allowed).  Anything else -- NULL, another k, another l_pre, another device -- is refused before
+ * any launch with a message, and the objects stay usable.  Equal k and l_pre mean equal sub-table index and key, so nothing is hashed or
+ * decoded and every k up to 63 works, except where planes are handed out.
+ *   bfcg_kmers_joint_hist joint[i * 256 + j] = the keys with count i in a and j in b, 0 = absent (joint[0] is 0);
+ *                         n = { shared, only in a, only in b }.  0, or -1 on error; bfcg_kmers_last_ms(a) is the time of its two launches
+ *   bfcg_kmers_list_vs    bfcg_kmers_list on a -- the same order, planes, cap / *n protocol, return codes and refusal of k > 37 -- with a
+ *                         slot kept only if its count in b (0 where b does not hold the key) lies in [other_min, other_max]: [0, 0] lists
+ *                         what is private to a, [1, 255] what is shared, [0, 255] everything.  other[i] = what bfcg_kmers_lookup would
+ *                         answer for k-mer i in b: -1, or high << 8 | count
+ *   bfcg_kmers_union      a new object that owns its table: a's k and l_pre, every key of either input, counts and high counts of a key in
+ *                         both added and saturated at 255 and 63 (bfc_ch_union, htab.c:74-79).  Its cshift is the smallest value >= 2
+ *                         with 2^(l_pre + cshift) >= 2 (keys_a + keys_b) and 2^cshift >= the largest size_a[s] + size_b[s], taken from one
+ *                         size pass over each input: no region can overflow, nothing is retried.  The order inside a sub-table is
+ *                         unspecified.  NULL on error; bfcg_kmers_last_ms(result) covers the size passes and the fill
+ *   bfcg_kmers_export     a host bfc_ch_t from any bfcg_kmers_t (one copy, no order stamps; *n_keys, which may be NULL, = its keys): to be
+ *                         dumped, handed to bfcg_ec_create, asked with bfc_ch_get; the caller destroys it.  NULL on error
+ *   bfcg_kmers_format_vs  a piece of bfcg_kmers_list_vs as lines "%s\t%d\t%d\t%d\t%d\n": k-mer, count, high, count in b, high in b (0 0 for
+ *                         an absent one); at most k + 16 bytes each
  * Their host twins and the text forms use no GPU:
  *   bfcg_kmer_from_str    the inverse of bfcg_kmer_2str; -1 unless s has exactly k bytes of ACGTacgt
  *   bfcg_kmer_occ_host    bfc_ch_kmer_occ on listing-style planes of either strand (the four planes of bfc_kmer_t built from the two)
@@ -430,6 +449,12 @@ int   bfcg_kmers_read_stats(bfcg_kmers_t *t, const uint8_t *h_seq, const uint8_t
                             int min_cov, int32_t *out);
 int   bfcg_read_stats_host(const bfc_ch_t *ch, const uint8_t *seq, uint64_t n_pos, const uint64_t *off, uint64_t n_reads, int min_cov, int32_t *out);
 uint64_t bfcg_read_stats_format(const int32_t *out, uint64_t n_reads, char *buf);
+int   bfcg_kmers_joint_hist(bfcg_kmers_t *a, bfcg_kmers_t *b, uint64_t joint[256 * 256], uint64_t n[3]);
+int   bfcg_kmers_list_vs(bfcg_kmers_t *a, bfcg_kmers_t *b, int min_cnt, int min_diff, int other_min, int other_max,
+                         uint32_t sub_lo, uint32_t sub_hi, uint64_t *y, uint16_t *cnt_high, int16_t *other, uint64_t cap, uint64_t *n);
+bfcg_kmers_t *bfcg_kmers_union(bfcg_kmers_t *a, bfcg_kmers_t *b);
+bfc_ch_t     *bfcg_kmers_export(bfcg_kmers_t *t, uint64_t *n_keys);
+uint64_t bfcg_kmers_format_vs(int k, const uint64_t *y, const uint16_t *cnt_high, const int16_t *other, uint64_t n, char *buf);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);

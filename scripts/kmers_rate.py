@@ -2,13 +2,16 @@
 from the attached context, kernels only, against the path it replaces for the spectrum -- bfcg_export_table followed by the host's
 bfc_ch_hist.  Not the headline bench; numbers quoted in profiles/kmers_rate.md.
 
-    python scripts/kmers_rate.py [--lookup | --readstats] [k] [bf_shift] [genome size] [coverage]
+    python scripts/kmers_rate.py [--lookup | --readstats | --compare] [k] [bf_shift] [genome size] [coverage]
 
 --lookup measures the other direction instead (bfcg_lookup.hip): lookup() of every listed k-mer in shuffled order, and profile() over a
 prefix of the reads that built the table, each next to the host's loop over bfc_ch_kmer_occ on the same input (bfcg_kmers_occ_host,
 one thread) and to the chip's rate of independent 8-byte gathers from HBM (scripts/probes/gather_probe.hip).
 --readstats measures read_stats() (bfcg_readstats.hip) over a prefix of the reads of about 2^25 positions: its two kernels, the call's
 wall time with its D2H, and next to them the way to the same numbers without it -- profile() and a numpy reduction per read.
+--compare measures two tables against each other (bfcg_tabcmp.hip): the table of all reads and the table of the first half of the reads,
+both resident; joint_hist(), a full list_vs() and union(), kernels only, against the bytes of both tables at the copy rate, and next to
+them the route without them -- export both tables, bfc_ch_union on the host (one thread).
 """
 import os
 import sys
@@ -27,6 +30,9 @@ if LOOKUP:
 READSTATS = "--readstats" in sys.argv
 if READSTATS:
     sys.argv.remove("--readstats")
+COMPARE = "--compare" in sys.argv
+if COMPARE:
+    sys.argv.remove("--compare")
 arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
 k, b, G, cov = arg(1, 31), arg(2, 33), arg(3, 4_600_000), arg(4, 100)
 rs = gen.ReadSet(seed=2, G=G, cov=cov)
@@ -154,6 +160,68 @@ def readstats_rates(min_cov=3):
     print("best wall: read_stats %.1f ms; profile %.1f ms + numpy %.1f ms = %.1f ms (%.1fx)"
           % (min(wall), min(pwall), min(hwall), min(pwall) + min(hwall), (min(pwall) + min(hwall)) / min(wall)))
 
+
+def compare_rates():
+    import ctypes as C
+    half = rs.n_reads // 2
+    g2 = bfc_amd.GpuCounter(k, b, max_batch_pos=br * stride)
+    for r0 in range(0, half, br):
+        r1 = min(half, r0 + br)
+        g2.count_host(s_seq[r0 * stride:r1 * stride], s_qual[r0 * stride:r1 * stride])
+    kb = bfc_amd.GpuKmers(g2)
+    slots_b = 1 << (kb.l_pre + kb.cshift)
+    both = (slots + slots_b) * 8
+    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
+    vs = lambda ms: "%.3f ms; both tables once (%.1f MiB) in that time = %.2f TB/s = %.2f of the %.1f TB/s copy rate" % (ms, both / 2**20, both / ms / 1e9, both / ms / 1e9 / COPY_TBS, COPY_TBS)  # noqa: E731
+    print("build %s" % bfc_amd._lib.build_id())
+    print("table B (first %d reads): 2^%d sub-tables of 2^%d slots = %.1f MiB, %d keys" % (half, kb.l_pre, kb.cshift, slots_b * 8 / 2**20, g2.stats()["n_keys"]))
+    jms = []
+    for rep in range(5):
+        joint, shared, only_a, only_b = km.joint_hist(kb)
+        jms.append(km.last_ms())
+    print("joint_hist (two launches of k_tab_join + k_join_sum), 5 runs (ms): %s; shared %d, only A %d, only B %d; %d keys in cells outside the 64 x 64 corner, %d outside the 128 x 128 one"
+          % (f(jms), shared, only_a, only_b, int(joint.sum() - joint[:64, :64].sum()), int(joint.sum() - joint[:128, :128].sum())))
+    print("joint_hist best: " + vs(min(jms)))
+    lms = []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        y, c, h, o = km.list_vs(kb)
+        wall = time.perf_counter() - t0
+        lms.append(km.last_ms())
+    assert len(c) == shared + only_a and int((o >= 0).sum()) == shared
+    print("list_vs (all %d k-mers of A annotated; count + scan + emit, B probed in both passes), 3 runs (ms): %s; wall of the last with copies %.1f ms" % (len(c), f(lms), wall * 1e3))
+    km.list()
+    print("list_vs best: " + vs(min(lms)) + "; list() of A alone: %.3f ms" % km.last_ms())
+    ums = []
+    for rep in range(3):
+        u = km.union(kb)
+        ums.append(u.last_ms())
+        if rep < 2:
+            u.close()
+    uhist = u.hist()
+    print("union (two size passes, zero-fill and two launches of k_tab_union into 2^%d x 2^%d slots = %.1f MiB), 3 runs (ms): %s" % (u.l_pre, u.cshift, 8 * 2.0**(u.l_pre + u.cshift - 20), f(ums)))
+    print("union best: " + vs(min(ums)))
+    t0 = time.perf_counter()
+    ta, tb = g.export_table(), g2.export_table()
+    t1 = time.perf_counter()
+    hu = bfc_amd.HostTable(bfc_amd._lib.load().bfc_ch_union((C.c_void_p * 2)(ta.ptr, tb.ptr), 2))
+    t2 = time.perf_counter()
+    hh = hu.hist()
+    assert hu.count() == shared + only_a + only_b == int(uhist[1].sum()) and np.array_equal(hh[1], uhist[1]) and np.array_equal(hh[2], uhist[2])
+    print("export both + host bfc_ch_union: %.1f ms + %.1f ms = %.1f ms (same key count and spectrum as the device's union: %.0fx its kernels)"
+          % ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t2 - t0) * 1e3, (t2 - t0) * 1e3 / min(ums)))
+    t0 = time.perf_counter()
+    th = u.to_host()
+    print("to_host() of the union: %.1f ms" % ((time.perf_counter() - t0) * 1e3))
+    for x in (th, hu, ta, tb, u, kb, g2):
+        x.close()
+
+
+if COMPARE:
+    compare_rates()
+    km.close()
+    g.close()
+    sys.exit(0)
 
 if READSTATS:
     readstats_rates()
