@@ -173,6 +173,15 @@ SYMBOLS = {
     "bfcg_kmers_union": (C.c_void_p, [C.c_void_p, C.c_void_p]),
     "bfcg_kmers_export": (C.c_void_p, [C.c_void_p, u64p]),
     "bfcg_kmers_format_vs": (C.c_uint64, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_kmers_neighbors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_kmers_graph_census": (C.c_int, [C.c_void_p, C.c_int, u64p]),
+    "bfcg_kmers_list_graph": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "bfcg_kmers_extend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bfcg_kmer_revcomp": (C.c_int, [C.c_int, u64p, u64p]),
+    "bfcg_neighbors_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "bfcg_graph_census_host": (C.c_int, [C.c_void_p, C.c_int, u64p]),
+    "bfcg_graph_nb_host": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bfcg_extend_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bfcg_hash_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_seen_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
 }

@@ -87,6 +87,42 @@ def format_read_stats(out):
     return buf.raw[:n]
 
 
+# ---- the table as a de Bruijn graph (bfcg_graph.hip): degree cells and their masks ------------------------------------------------------
+# cell 5 * o + i: o present successors, i present predecessors, on the strand the table stores; the four classes below are symmetric in
+# (o, i), so they mean the same on either strand
+GRAPH_MASKS = {
+    "tips": sum(1 << (5 * o + i) for o in range(5) for i in range(5) if (o == 0) != (i == 0)),
+    "isolated": 1,
+    "branching": sum(1 << (5 * o + i) for o in range(5) for i in range(5) if o >= 2 or i >= 2),
+    "simple": 1 << 6,
+    "all": (1 << 25) - 1,
+}
+
+_POP4 = np.array([bin(i).count("1") for i in range(16)], dtype=np.int64)
+
+
+def kmer_revcomp(k, y):
+    """The planes of the reverse complements of y (n, 2) u64 (bfcg_kmer_revcomp; no GPU)."""
+    y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 2)
+    out, L = np.zeros_like(y), _lib.load()
+    for i in range(len(y)):
+        if L.bfcg_kmer_revcomp(int(k), y[i].ctypes.data_as(u64p), out[i].ctypes.data_as(u64p)) != 0:
+            raise BfcGpuError("k=%d is outside [1, 63]" % k)
+    return out
+
+
+def nb_text(nb):
+    """The neighbour bits of one k-mer as text, "successors<TAB>predecessors": the bases present on each side, '.' for none."""
+    nb = int(nb)
+    return "%s\t%s" % ("".join("ACGT"[c] for c in range(4) if nb >> c & 1) or ".", "".join("ACGT"[c] for c in range(4) if nb >> (4 + c) & 1) or ".")
+
+
+def _graph_seeds(y, max_len):
+    """(y (n, 2) u64, bases (n, max_len) u8, len_stop (n, 2) i32) of an extend() call"""
+    y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 2)
+    return y, np.zeros((len(y), max(0, int(max_len))), dtype=np.uint8), np.zeros((len(y), 2), dtype=np.int32)
+
+
 class HostTable:
     """A host-resident ``bfc_ch_t`` (opaque, htab.h:10-23)."""
 
@@ -139,6 +175,53 @@ class HostTable:
         if self.L.bfcg_read_stats_host(self.ptr, s.ctypes.data, len(s), off.ctypes.data, len(off) - 1, int(min_cov), out.ctypes.data) != 0:
             raise BfcGpuError(self.L.bfcg_last_error().decode())
         return out
+
+    def neighbors(self, y):
+        """The values of the eight de Bruijn neighbours of k-mers y (n, 2) u64: int16 (n, 8), columns 0-3 succ by A C G T, 4-7 pred.
+        The host twin of GpuKmers.neighbors (bfcg_neighbors_host)."""
+        y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 2)
+        out = np.empty((len(y), 8), dtype=np.int16)
+        if self.L.bfcg_neighbors_host(self.ptr, y.ctypes.data, len(y), out.ctypes.data) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        return out
+
+    def graph_census(self, min_cnt=1):
+        """u64 (5, 5): [o, i] = the k-mers with count >= min_cnt that have o present successors and i present predecessors
+        (bfcg_graph_census_host)."""
+        deg = np.zeros(25, dtype=np.uint64)
+        if self.L.bfcg_graph_census_host(self.ptr, int(min_cnt), deg.ctypes.data_as(u64p)) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        return deg.reshape(5, 5)
+
+    def graph_nb(self, min_cnt=1):
+        """(y (n, 2) u64, nb u8 (n)) for every slot of export_sorted(), in its order: the planes and the neighbour bits (0 where the
+        count is below min_cnt): bfcg_graph_nb_host."""
+        n = self.L.bfcg_graph_nb_host(self.ptr, int(min_cnt), None, None)
+        if n < 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        y, nb = np.zeros((n, 2), dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        if self.L.bfcg_graph_nb_host(self.ptr, int(min_cnt), y.ctypes.data, nb.ctypes.data) != n:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        return y, nb
+
+    def list_graph(self, min_cnt=1, cell_mask=GRAPH_MASKS["all"]):
+        """(y, count u8, high u8, nb u8) of the k-mers with count >= min_cnt whose degree cell is in cell_mask, in export_sorted()'s
+        order: the host twin of GpuKmers.list_graph, from graph_nb()."""
+        if not 0 < int(cell_mask) < 1 << 25:
+            raise BfcGpuError("cell_mask 0x%x names no cell or one beyond bit 24" % int(cell_mask))
+        y, nb = self.graph_nb(min_cnt)
+        slots = self.export_sorted()[1]
+        cnt = (slots & np.uint64(0xff)).astype(np.uint8)
+        cell = 5 * _POP4[nb & 15] + _POP4[nb >> 4]
+        keep = (cnt >= min_cnt) & ((np.uint32(cell_mask) >> cell.astype(np.uint32)) & np.uint32(1)).astype(bool)
+        return y[keep], cnt[keep], (slots >> np.uint64(8) & np.uint64(0x3f)).astype(np.uint8)[keep], nb[keep]
+
+    def extend(self, y, min_cnt=1, max_len=300):
+        """(bases u8 (n, max_len), length i32, stop i32): GpuKmers.extend's host twin (bfcg_extend_host)."""
+        y, bases, ls = _graph_seeds(y, max_len)
+        if self.L.bfcg_extend_host(self.ptr, y.ctypes.data, len(y), int(min_cnt), int(max_len), bases.ctypes.data, ls.ctypes.data) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        return bases, ls[:, 0].copy(), ls[:, 1].copy()
 
     def insert(self, y0, y1, is_high, forced=1):
         return self.L.bfc_ch_insert(self.ptr, (C.c_uint64 * 2)(y0, y1), int(is_high), forced)
@@ -827,9 +910,79 @@ class GpuKmers:
             raise BfcGpuError("bfcg_kmers_export failed: " + self.L.bfcg_last_error().decode())
         return HostTable(p)
 
+    # ---- the table as a de Bruijn graph (bfcg_graph.hip): include/bfc_gpu.h defines succ, pred, value, present, node and the degrees
+
+    def neighbors(self, y):
+        """The values of the eight neighbours of k-mers y (n, 2) u64, on the strand given: int16 (n, 8), columns 0-3 = succ by A C G T,
+        4-7 = pred by A C G T; -1 or high << 8 | count as lookup().  Every k up to 63."""
+        y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, 2)
+        out = np.empty((len(y), 8), dtype=np.int16)
+        if self.L.bfcg_kmers_neighbors(self.t, y.ctypes.data, len(y), out.ctypes.data) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return out
+
+    def graph_census(self, min_cnt=1):
+        """u64 (5, 5): [o, i] = the k-mers with count >= min_cnt that have o present successors and i present predecessors, on the strand
+        the table stores (fold [o, i] with [i, o] for a strand-free view).  One streaming pass; k <= 37."""
+        deg = np.zeros(25, dtype=np.uint64)
+        if self.L.bfcg_kmers_graph_census(self.t, int(min_cnt), deg.ctypes.data_as(u64p)) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return deg.reshape(5, 5)
+
+    def list_graph_raw(self, min_cnt, cell_mask, sub_lo, sub_hi, cap):
+        """One bfcg_kmers_list_graph call: (rc, n, y (cap, 2) u64, cnt_high u16 (cap), nb u8 (cap))."""
+        y, ch, nb = np.zeros((cap, 2), dtype=np.uint64), np.zeros(cap, dtype=np.uint16), np.zeros(cap, dtype=np.uint8)
+        n = C.c_uint64()
+        rc = self.L.bfcg_kmers_list_graph(self.t, int(min_cnt), int(cell_mask), int(sub_lo), int(sub_hi), y.ctypes.data, ch.ctypes.data, nb.ctypes.data, cap, C.byref(n))
+        if rc < 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        return rc, int(n.value), y, ch, nb
+
+    def pieces_graph(self, min_cnt=1, cell_mask=GRAPH_MASKS["all"], sub_lo=0, sub_hi=None, piece=1 << 24, sizes=None):
+        """pieces() with the graph predicate: yields (y, cnt_high, nb u8) per piece of whole sub-tables, each sized from the sub-table
+        sizes (an upper bound: the predicate only drops)."""
+        sub_hi = (1 << self.l_pre) if sub_hi is None else sub_hi
+        self.list_graph_raw(min_cnt, cell_mask, sub_lo, sub_lo, 0)  # an empty range: the library's refusals, before any work
+        ends = np.cumsum((self.sub_sizes() if sizes is None else sizes)[sub_lo:sub_hi], dtype=np.uint64)
+        max_subs = max(1, self.MAX_SLOTS >> self.cshift)
+        self._ms, lo, done = 0.0, sub_lo, 0
+        while lo < sub_hi:
+            hi = sub_lo + int(np.searchsorted(ends, done + piece, side="right"))
+            hi = min(max(hi, lo + 1), lo + max_subs, sub_hi)
+            cap = int(ends[hi - 1 - sub_lo]) - done
+            rc, n, y, ch, nb = self.list_graph_raw(min_cnt, cell_mask, lo, hi, cap)
+            if rc != 0:
+                raise BfcGpuError("sub-tables [%d, %d) hold %d k-mers, their sizes said %d: the table changed under the listing" % (lo, hi, n, cap))
+            self._ms += float(self.L.bfcg_kmers_last_ms(self.t))
+            yield y[:n], ch[:n], nb[:n]
+            lo, done = hi, done + cap
+
+    def list_graph(self, min_cnt=1, cell_mask=GRAPH_MASKS["all"], sub_lo=0, sub_hi=None, piece=1 << 24):
+        """(y (n, 2) u64, count u8, high u8, nb u8): the k-mers with count >= min_cnt whose degree cell 5 * o + i is a set bit of cell_mask
+        (GRAPH_MASKS names some), sub-tables ascending; nb bit c: succ by base c is present, bit 4 + c: pred by base c."""
+        parts = list(self.pieces_graph(min_cnt, cell_mask, sub_lo, sub_hi, piece))
+        y = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 2), dtype=np.uint64)
+        ch = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.uint16)
+        nb = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, dtype=np.uint8)
+        return y, (ch & 0xff).astype(np.uint8), (ch >> 8).astype(np.uint8), nb
+
+    def extend(self, y, min_cnt=1, max_len=300):
+        """The unambiguous path to the right of every seed y (n, 2) u64: (bases u8 (n, max_len) of 'A' 'C' 'G' 'T', zero beyond the
+        length; length i32; stop i32: 0 max_len reached, 1 no successor, 2 several successors, 3 the successor has a second predecessor,
+        4 the seed is absent, 5 back at the seed).  One lane walks one seed: for thousands of seeds of a few hundred bases.  A walk to
+        the left is extend(kmer_revcomp(k, y)), read as the reverse complement."""
+        y, bases, ls = _graph_seeds(y, max_len)
+        if self.L.bfcg_kmers_extend(self.t, y.ctypes.data, len(y), int(min_cnt), int(max_len), bases.ctypes.data, ls.ctypes.data) != 0:
+            raise BfcGpuError(self.L.bfcg_last_error().decode())
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return bases, ls[:, 0].copy(), ls[:, 1].copy()
+
     def last_ms(self):
         """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces,
-        read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces; of a union() result, its size passes and fill."""
+        read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces, neighbors() / list_graph() / extend() all their pieces, graph_census() one pass; of a union() result,
+        its size passes and fill."""
         return self._ms
 
 

@@ -1,4 +1,4 @@
-// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_mg.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip):
+// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_mg.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip, bfcg_graph.hip):
 // kernel parameters and launchers, the one error channel, the resident registry, what the satellites and the group layer borrow from a context
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,7 +37,7 @@ struct bfcg_kmers {
 	hipStream_t st;
 	hipEvent_t e0, e1;
 	const unsigned long long *table;
-	unsigned long long *d_hist;      // 256 + 64
+	unsigned long long *d_hist;      // 256 + 64 (bfcg_kmers_graph_census: its 25 cells)
 	uint32_t *d_sizes;               // 2^l_pre
 	uint32_t *d_cnt; unsigned long long *d_off; uint64_t blk_cap;   // per-block counts / offsets of a listing (grown on demand)
 	ulonglong2 *d_y; uint16_t *d_ch; uint64_t out_cap;              // a listing's device result (grown on demand)
@@ -47,6 +47,8 @@ struct bfcg_kmers {
 	int16_t *d_oth; uint64_t oth_cap;   // a listing's third column, what the other table answered (bfcg_tabcmp.hip; grown on demand, in bytes)
 	uint32_t *d_jpart; uint64_t jpart_cap; // the 128 x 128 corner of a joint spectrum per workgroup (bfcg_tabcmp.hip; grown on demand, in bytes)
 	unsigned long long *d_joint;        // 256 x 256 bins of a joint spectrum and the two counters of a union (bfcg_tabcmp.hip; allocated by the first call)
+	uint8_t *d_gout; uint64_t gout_cap; // a graph call's answers: eight values per k-mer of bfcg_kmers_neighbors, the paths of bfcg_kmers_extend (bfcg_graph.hip; grown on demand, in bytes)
+	int32_t *d_gls; uint64_t gls_cap;   // length and stop code per seed of bfcg_kmers_extend (bfcg_graph.hip; grown on demand, in bytes)
 	uint64_t n_keys; int has_keys;      // the keys of a table this object built and owns (bfcg_kmers_union counts them on the device)
 	float last_ms;
 };
@@ -194,6 +196,8 @@ int kcov_adopted(::bfcg_kcov *t);
 BFCG_LOCAL ::bfcg_kmers *kmers_new(int k, int l_pre, int cshift, int device);
 // k-mers a lookup stages per piece (bfcg_lookup.hip): a few million, or what BFCG_LOOKUP_CAP says
 BFCG_LOCAL uint64_t lookup_cap();
+// a lookup's staging buffers d_qy / d_qout of q_cap k-mers, allocated by the first call that needs them (bfcg_lookup.hip; bfcg_graph.hip stages its k-mers in d_qy)
+BFCG_LOCAL int lookup_stage(::bfcg_kmers *t);
 // a profile's first half (bfcg_lookup.hip): the stream staged in d_pseq if it is the host's, d_pout grown, t->e0 recorded and k_profile launched
 // into d_pout on t->st.  The caller records t->e1 behind the last kernel of its call and checks hipGetLastError.
 BFCG_LOCAL int profile_launch(::bfcg_kmers *t, const uint8_t *h_seq, const uint8_t *d_seq, uint64_t n_pos);

@@ -1,8 +1,11 @@
-// bfcg_klist.h -- the listing of a count table, k_tab_list, for the two files that list: bfcg_kmers.hip (bfcg_kmers_list, the table alone) and
-// bfcg_tabcmp.hip (bfcg_kmers_list_vs, the table filtered and annotated by a second one).  The three kernels and the host sequence around
-// them are written once, as templates over what the second table says about a slot:
+// bfcg_klist.h -- the listing of a count table, k_tab_list, for the files that list: bfcg_kmers.hip (bfcg_kmers_list, the table alone),
+// bfcg_tabcmp.hip (bfcg_kmers_list_vs, the table filtered and annotated by a second one) and bfcg_graph.hip (bfcg_kmers_list_graph, by
+// its own graph).  The three kernels and the host sequence around them are written once, as templates over what a predicate says about
+// a slot:
 //   NoOther        nothing: every slot that passes -m / -d is kept, no third output
-//   a probing type (bfcg_tabcmp.hip: VsOther) keep(sub, slot, o): o = the slot's key looked up in the other table, kept or not by its count
+//   a probing type keep(sub, slot, o): a third output column of its col_t per k-mer
+//     VsOther   (bfcg_tabcmp.hip) o = the slot's key looked up in the other table, kept or not by its count
+//     GraphPred (bfcg_graph.hip)  o = which of the slot's eight de Bruijn neighbours the table holds, kept or not by its degree cell
 //
 //   k_tab_list   a range of sub-tables in blocks of LIST_BLK slots: k_list_count counts the slots that pass the filter per block,
 //                k_list_scan turns the counts into offsets, k_list_emit decodes (bfcg_kdec.h) and stores in slot order -- sub-tables
@@ -21,7 +24,7 @@ enum { SCAN_BT = 1024, SCAN_PER = 8 };
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
-struct NoOther { static constexpr bool probes = false; };
+struct NoOther { static constexpr bool probes = false; using col_t = int16_t; };
 
 // Slots [s_lo, s_hi) of the table in blocks of LIST_BLK, block 0 starting at s_lo rounded down to a pair; a wave owns LIST_WAVE
 // consecutive slots of its block, a lane slots 2l, 2l + 1 of each of its LIST_STEPS steps.
@@ -30,7 +33,7 @@ struct ListGeom { uint64_t s_lo, s_hi, base; int k, l_pre, cshift, min_cnt, min_
 // ov[2j], ov[2j + 1]: what the other table answered for the two slots of step j (0 without one)
 template <class O>
 __device__ __forceinline__ void list_load(const ulonglong2 *__restrict__ tab, const ListGeom &G, const O &other, uint64_t wave_first, ulonglong2 v[LIST_STEPS],
-                                          int16_t ov[2 * LIST_STEPS])
+                                          typename O::col_t ov[2 * LIST_STEPS])
 {
 	const int lane = lane_id();
 #pragma unroll
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(BT) void k_list_count(const ulonglong2 *__restrict_
 	__shared__ uint32_t wsum[WAVES];
 	const int wave = threadIdx.x >> 6;
 	ulonglong2 v[LIST_STEPS];
-	int16_t ov[2 * LIST_STEPS];
+	typename O::col_t ov[2 * LIST_STEPS];
 	list_load(tab, G, other, G.base + (uint64_t)blockIdx.x * LIST_BLK + (uint64_t)wave * LIST_WAVE, v, ov);
 	uint32_t n = 0;
 #pragma unroll
@@ -105,13 +108,13 @@ __global__ __launch_bounds__(SCAN_BT) void k_list_scan(const uint32_t *__restric
 
 template <class O>
 __global__ __launch_bounds__(BT) void k_list_emit(const ulonglong2 *__restrict__ tab, ListGeom G, O other, const unsigned long long *__restrict__ blk_off,
-                                                  ulonglong2 *__restrict__ out_y, uint16_t *__restrict__ out_ch, int16_t *__restrict__ out_other, uint64_t cap)
+                                                  ulonglong2 *__restrict__ out_y, uint16_t *__restrict__ out_ch, typename O::col_t *__restrict__ out_other, uint64_t cap)
 {
 	__shared__ uint32_t wsum[WAVES];
 	const int lane = lane_id(), wave = threadIdx.x >> 6;
 	const uint64_t wave_first = G.base + (uint64_t)blockIdx.x * LIST_BLK + (uint64_t)wave * LIST_WAVE;
 	ulonglong2 v[LIST_STEPS];
-	int16_t ov[2 * LIST_STEPS];
+	typename O::col_t ov[2 * LIST_STEPS];
 	list_load(tab, G, other, wave_first, v, ov);
 	uint64_t bx[LIST_STEPS], by[LIST_STEPS];
 	uint32_t n = 0;
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(BT) void k_list_emit(const ulonglong2 *__restrict__
 // count + scan, the total read back, then -- if it fits `cap` -- emit and the copies.  0 / 1 / -1 as bfcg_kmers_list.
 template <class O>
 int list_run(bfcg_kmers_t *t, const char *who, const O &other, int min_cnt, int min_diff, uint32_t sub_lo, uint32_t sub_hi, uint64_t *y, uint16_t *cnt_high,
-             int16_t *oth, uint64_t cap, uint64_t *n)
+             typename O::col_t *oth, uint64_t cap, uint64_t *n)
 {
 	if (!kdec::decodable(t->k)) return bfcg::fail("k-mers cannot be listed for k=%d: the table's key is lossless only for k <= %d (sizes and histogram work for any k)", t->k, (int)kdec::MAX_K);
 	if (sub_lo > sub_hi || (uint64_t)sub_hi > 1ULL << t->l_pre) return bfcg::fail("sub-table range [%u, %u) outside [0, 2^%d]", sub_lo, sub_hi, t->l_pre);
@@ -189,14 +192,14 @@ int list_run(bfcg_kmers_t *t, const char *who, const O &other, int min_cnt, int 
 		BFCG_CK(hipMalloc(&t->d_y, total * 16)); BFCG_CK(hipMalloc(&t->d_ch, total * 2));
 		t->out_cap = total;
 	}
-	if (O::probes && bfcg::grow(t->d_oth, t->oth_cap, total * 2, "a listing's annotation") != 0) return -1;
+	if (O::probes && bfcg::grow(t->d_oth, t->oth_cap, total * sizeof(typename O::col_t), "a listing's annotation") != 0) return -1;
 	BFCG_CK(hipEventRecord(t->e0, t->st));
-	hipLaunchKernelGGL((k_list_emit<O>), dim3((unsigned)n_blk), dim3(BT), 0, t->st, (const ulonglong2 *)t->table, G, other, t->d_off, t->d_y, t->d_ch, t->d_oth, (uint64_t)total);
+	hipLaunchKernelGGL((k_list_emit<O>), dim3((unsigned)n_blk), dim3(BT), 0, t->st, (const ulonglong2 *)t->table, G, other, t->d_off, t->d_y, t->d_ch, (typename O::col_t *)t->d_oth, (uint64_t)total);
 	BFCG_CK(hipEventRecord(t->e1, t->st));
 	BFCG_CK(hipGetLastError());
 	BFCG_CK(hipMemcpyAsync(y, t->d_y, total * 16, hipMemcpyDeviceToHost, t->st));
 	BFCG_CK(hipMemcpyAsync(cnt_high, t->d_ch, total * 2, hipMemcpyDeviceToHost, t->st));
-	if (O::probes) BFCG_CK(hipMemcpyAsync(oth, t->d_oth, total * 2, hipMemcpyDeviceToHost, t->st));
+	if (O::probes) BFCG_CK(hipMemcpyAsync(oth, t->d_oth, total * sizeof(typename O::col_t), hipMemcpyDeviceToHost, t->st));
 	BFCG_CK(hipStreamSynchronize(t->st));
 	BFCG_CK(hipEventElapsedTime(&ms2, t->e0, t->e1));
 	t->last_ms = ms1 + ms2;

@@ -137,7 +137,7 @@ extern "C" void bfcg_kmers_destroy(bfcg_kmers_t *t)
 	if (t->owns_table) (void)hipFree((void *)t->table);
 	(void)hipFree(t->d_hist); (void)hipFree(t->d_sizes); (void)hipFree(t->d_cnt); (void)hipFree(t->d_off); (void)hipFree(t->d_y); (void)hipFree(t->d_ch);
 	(void)hipFree(t->d_qy); (void)hipFree(t->d_qout); (void)hipFree(t->d_pseq); (void)hipFree(t->d_pout); (void)hipFree(t->d_roff); (void)hipFree(t->d_rout);
-	(void)hipFree(t->d_oth); (void)hipFree(t->d_joint); (void)hipFree(t->d_jpart);
+	(void)hipFree(t->d_oth); (void)hipFree(t->d_joint); (void)hipFree(t->d_jpart); (void)hipFree(t->d_gout); (void)hipFree(t->d_gls);
 	if (t->e0) (void)hipEventDestroy(t->e0);
 	if (t->e1) (void)hipEventDestroy(t->e1);
 	if (t->st) (void)hipStreamDestroy(t->st);

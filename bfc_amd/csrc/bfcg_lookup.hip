@@ -25,21 +25,12 @@ __global__ __launch_bounds__(LOOKUP_BT) void k_lookup(int k, int l_pre, int cshi
                                                       const ulonglong2 *__restrict__ y, uint64_t n, int16_t *__restrict__ out)
 {
 	constexpr int nb = 8 * (int)sizeof(W);
-	const W m = kmask<W>(k);
 	for (uint64_t i = (uint64_t)blockIdx.x * LOOKUP_BT + threadIdx.x; i < n; i += (uint64_t)gridDim.x * LOOKUP_BT) {
 		const ulonglong2 v = y[i];
 		// a plane has the base at the 3' end in bit 0, a window of the stream the oldest base: the given strand's windows
 		const W w_lo = brev_w((W)v.x) >> (nb - k), w_hi = brev_w((W)v.y) >> (nb - k);
 		uint64_t y0, y1;
-		if constexpr (sizeof(W) == 8) {
-			U2 a, b;
-			kmer_hash_from_windows2<0>(k, (uint32_t)w_lo, (uint32_t)(w_lo >> 32), (uint32_t)w_hi, (uint32_t)(w_hi >> 32), a, b);
-			y0 = u2_join(a); y1 = u2_join(b);
-		} else {
-			W a, b;
-			kmer_hash_from_windows<W>(k, w_lo, w_hi, m, a, b);
-			y0 = a; y1 = b;
-		}
+		kmer_hash_windows<W>(k, w_lo, w_hi, y0, y1);
 		out[i] = (int16_t)ch_get_dev(k, l_pre, cshift, tab, y0, y1);
 	}
 }
@@ -53,8 +44,10 @@ __global__ __launch_bounds__(BT) void k_profile(KParams P, const uint8_t *__rest
 	occ_tile<W, TILE, BT>(P, seq, n_pos, tab, planes, [&](int64_t e, int occ) { out[e] = (int16_t)occ; });
 }
 
+} // namespace
+
 // the staging buffers of a lookup, both or none
-int lookup_stage(bfcg_kmers_t *t)
+int bfcg::lookup_stage(bfcg_kmers_t *t)
 {
 	if (t->d_qy) return 0;
 	ulonglong2 *qy = NULL; int16_t *qout = NULL;
@@ -67,8 +60,6 @@ int lookup_stage(bfcg_kmers_t *t)
 	t->d_qy = qy; t->d_qout = qout;
 	return 0;
 }
-
-} // namespace
 
 uint64_t bfcg::lookup_cap()
 {
@@ -84,7 +75,7 @@ extern "C" int bfcg_kmers_lookup(bfcg_kmers_t *t, const uint64_t *y, uint64_t n,
 	t->last_ms = 0;
 	if (n == 0) return 0;
 	BFCG_CK(hipSetDevice(t->device));
-	if (lookup_stage(t) != 0) return -1;
+	if (bfcg::lookup_stage(t) != 0) return -1;
 	float total = 0;
 	for (uint64_t done = 0; done < n; ) {
 		const uint64_t m = n - done < t->q_cap ? n - done : t->q_cap;

@@ -103,6 +103,7 @@ __global__ __launch_bounds__(JOIN_SUM_BT) void k_join_sum(const uint32_t *__rest
 // ---- the listing's predicate ------------------------------------------------------------------------------------------------------
 struct VsOther {
 	static constexpr bool probes = true;
+	using col_t = int16_t;
 	const unsigned long long *tab; int cshift, lo, hi;
 	__device__ __forceinline__ bool keep(uint32_t sub, uint64_t slot, int16_t &o) const
 	{

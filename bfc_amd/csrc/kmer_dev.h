@@ -126,6 +126,21 @@ template <int KC> __device__ __forceinline__ void kmer_hash_from_windows2(int k_
 	y1 = h1;
 }
 
+// the table hash of a k-mer from its two forward windows, for either width: W = uint32_t serves k <= 32, W = uint64_t (on halves) k <= 63
+// (k_lookup, bfcg_lookup.hip; the graph kernels, bfcg_graph.hip)
+template <typename W> __device__ __forceinline__ void kmer_hash_windows(int k, W w_lo, W w_hi, uint64_t &y0, uint64_t &y1)
+{
+	if constexpr (sizeof(W) == 8) {
+		U2 a, b;
+		kmer_hash_from_windows2<0>(k, (uint32_t)w_lo, (uint32_t)(w_lo >> 32), (uint32_t)w_hi, (uint32_t)(w_hi >> 32), a, b);
+		y0 = u2_join(a); y1 = u2_join(b);
+	} else {
+		W a, b;
+		kmer_hash_from_windows<W>(k, w_lo, w_hi, kmask<W>(k), a, b);
+		y0 = a; y1 = b;
+	}
+}
+
 // the bloom hash as a function of y (kmer.h:85-86 solved for h0): hash = (h0^h1)<<k | (h0+h1)&m
 template <typename W> __device__ __forceinline__ uint64_t bloom_hash(int k, W y0, W y1, W m)
 {

@@ -1,0 +1,118 @@
+"""A `bfc -d` dump read as a de Bruijn graph on the GPU: how many k-mers are dead ends, how many branch, and what lies around a k-mer.
+
+    python -m bfc_amd.kmergraph [-m INT] [-t|-b] [-x FILE] [-l INT] table.dump
+
+The dump is restored with bfc_ch_restore and uploaded.  A k-mer is PRESENT if the table holds it with count >= INT (-m, default 1); a NODE
+is a k-mer of the table with such a count, on the strand the table stores (the one hash2cnt prints); its out-degree o is the number of
+bases whose successor is present, its in-degree i that of the predecessors (include/bfc_gpu.h states all of it).  The reference has no
+such tool, so the output format is this project's.  Standard output, in this order:
+
+    deg<TAB>o<TAB>n0<TAB>n1<TAB>n2<TAB>n3<TAB>n4
+                          five lines, o = 0..4: the nodes with out-degree o and in-degree 0..4 (bfcg_kmers_graph_census; k <= 37).  A
+                          node stored as its reverse complement has the two degrees swapped; the five lines below count classes that are
+                          symmetric in (o, i): cell (o, i) is folded with (i, o), so they mean the same on either strand
+    nodes<TAB>N           all of them
+    isolated<TAB>N        o = 0 and i = 0
+    tips<TAB>N            exactly one of o, i is 0 (dead ends; a tip that also branches is counted under both)
+    simple<TAB>N          o = 1 and i = 1
+    branching<TAB>N       o >= 2 or i >= 2
+    kmer<TAB>count<TAB>high<TAB>successors<TAB>predecessors
+                          under -t / -b: the tips / the branching k-mers (bfcg_kmers_list_graph), sub-table by sub-table, with the bases
+                          whose successor / predecessor is present ('.' for none)
+    seed<TAB>unitig<TAB>left_len<TAB>left_stop<TAB>right_len<TAB>right_stop
+                          under -x FILE (one k-mer per line, '>' lines and empty lines skipped; every k up to 63): the unambiguous
+                          sequence around each k-mer, walked both ways for at most INT bases (-l, default 10000) by bfcg_kmers_extend --
+                          to the left as the same walk on the reverse complement.  Stop codes: 0 the limit, 1 no next k-mer, 2 several,
+                          3 the next one has another way in, 4 the seed is absent, 5 back at the seed
+"""
+import ctypes as C
+import getopt
+import sys
+
+import numpy as np
+
+USAGE = """Usage: kmergraph [options] <table.dump>
+Options:
+  -m INT   a k-mer is present with occ >= INT [1]
+  -t       list the tips
+  -b       list the branching k-mers
+  -x FILE  extend the k-mers of FILE both ways and print the unitig around each
+  -l INT   at most INT bases each way [10000]
+"""
+
+_COMP = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def _atoi(s):
+    try:
+        return int(s)
+    except ValueError:
+        return 0
+
+
+def summary(deg):
+    """(nodes, isolated, tips, simple, branching) of a (5, 5) census"""
+    from .api import GRAPH_MASKS
+    flat = [int(v) for v in np.asarray(deg).reshape(25)]
+    pick = lambda name: sum(v for b, v in enumerate(flat) if GRAPH_MASKS[name] >> b & 1)
+    return sum(flat), pick("isolated"), pick("tips"), pick("simple"), pick("branching")
+
+
+def _extend_file(api, km, fn, min_cnt, max_len, out):
+    text = open(fn, "rb").read()
+    y, bad = np.zeros((text.count(b"\n") + 1, 2), dtype=np.uint64), C.c_uint64()
+    n = km.L.bfcg_kmers_parse(km.k, text, len(text), y.ctypes.data, len(y), C.byref(bad))
+    if bad.value:
+        sys.stderr.write("ERROR: line %d of %s is not a %d-mer of ACGT\n" % (bad.value, fn, km.k))
+        return 1
+    y = y[:n]
+    rb, rl, rs = km.extend(y, min_cnt, max_len)
+    lb, ll, ls = km.extend(api.kmer_revcomp(km.k, y), min_cnt, max_len)
+    for i, seed in enumerate(km.strings(y)):
+        left = lb[i, :ll[i]].tobytes().translate(_COMP)[::-1]
+        out.write(b"%s\t%s\t%d\t%d\t%d\t%d\n" % (seed.encode(), left + seed.encode() + rb[i, :rl[i]].tobytes(), ll[i], ls[i], rl[i], rs[i]))
+    return 0
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    try:
+        opts, args = getopt.getopt(argv, "tbm:x:l:")
+    except getopt.GetoptError:
+        opts, args = [], []
+    o = dict(opts)
+    modes = [f for f in ("-t", "-b") if f in o]
+    if len(args) != 1 or len(modes) > 1:
+        sys.stderr.write(USAGE)
+        return 1
+    from . import api
+    t = api.HostTable.restore(args[0])
+    if t is None:
+        return 1
+    min_cnt, max_len = _atoi(o.get("-m", "1")), _atoi(o.get("-l", "10000"))
+    out = sys.stdout.buffer
+    km = api.GpuKmers(t)
+    rc = 0
+    try:
+        if t.k <= 37 or "-x" not in o:   # (k > 37 with -x alone: the walks need no decode)
+            deg = km.graph_census(min_cnt)
+            out.write("".join("deg\t%d\t%s\n" % (i, "\t".join(str(int(v)) for v in deg[i])) for i in range(5)).encode())
+            out.write(b"nodes\t%d\nisolated\t%d\ntips\t%d\nsimple\t%d\nbranching\t%d\n" % summary(deg))
+        if modes:
+            mask = api.GRAPH_MASKS["tips" if modes[0] == "-t" else "branching"]
+            for y, ch, nb in km.pieces_graph(min_cnt, mask):
+                lines = km.format(y, ch).split(b"\n")[:-1]
+                out.write(b"".join(ln + b"\t" + api.nb_text(v).encode() + b"\n" for ln, v in zip(lines, nb)))
+        if "-x" in o:
+            rc = _extend_file(api, km, o["-x"], min_cnt, max_len, out)
+    except api.BfcGpuError as e:
+        sys.stderr.write("ERROR: %s\n" % e)
+        rc = 1
+    out.flush()
+    km.close()
+    t.close()
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -410,6 +410,37 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *                         dumped, handed to bfcg_ec_create, asked with bfc_ch_get; the caller destroys it.  NULL on error
  *   bfcg_kmers_format_vs  a piece of bfcg_kmers_list_vs as lines "%s\t%d\t%d\t%d\t%d\n": k-mer, count, high, count in b, high in b (0 0 for
  *                         an absent one); at most k + 16 bytes each
+ * The table read as a de Bruijn graph (bfcg_graph.hip), on either form of the object.  With m = 2^k - 1 and a base c in 0..3 (A C G T):
+ *   succ(x, c)  both planes shifted left by one and masked with m, bit 0 of the low plane c & 1, of the high plane c >> 1: the base at
+ *               the 5' end falls out, c is the new base at the 3' end
+ *   pred(x, c)  both planes shifted right by one, bit k - 1 of the low plane c & 1, of the high plane c >> 1
+ * The VALUE of a k-mer is what bfcg_kmers_lookup answers for it on the strand as constructed: -1, or high << 8 | count (for even k the
+ * caveat stated there holds for neighbours as for any other k-mer: nothing is special-cased).  A k-mer is PRESENT at min_cnt if its
+ * value is >= 0 and value & 0xff >= min_cnt.  A NODE is a slot of the table with count >= min_cnt, on the strand the decode yields (the
+ * one a listing prints); its out-degree o is the number of c with succ(x, c) present, its in-degree i that of pred(x, c).  Both refer
+ * to the stored strand: a node stored as its reverse complement has the two swapped, and a caller who wants a strand-free view folds
+ * cell (o, i) with (i, o).  Every call sets bfcg_kmers_last_ms; every refusal below happens before any launch, leaves the outputs
+ * untouched and the object usable, and puts a message in bfcg_last_error.  min_cnt outside [1, 255] is refused wherever it is taken.
+ *   bfcg_kmers_neighbors  y as for bfcg_kmers_lookup, every k up to 63; out (host) int16_t[8 n]: out[8 i + c] = the value of
+ *                         succ(x_i, c), out[8 i + 4 + c] = that of pred(x_i, c).  16 bytes in and 16 bytes out per k-mer: the eight
+ *                         neighbours are built in registers.  n above the lookup's staging capacity is cut inside the call
+ *   bfcg_kmers_graph_census  one streaming pass: deg[5 o + i] = the nodes with out-degree o and in-degree i.  k > 37 is refused with the
+ *                         listing's message (a node has to be decoded)
+ *   bfcg_kmers_list_graph bfcg_kmers_list -- the same order, planes, cap / *n protocol, return codes and refusal of k > 37 -- of the nodes
+ *                         whose cell is named by cell_mask (bit 5 o + i; 0, or a bit at or above 2^25, is refused), with nb[j] per
+ *                         k-mer: bit c set if succ by c is present, bit 4 + c if pred by c is.  Tips are the cells where exactly one
+ *                         of o, i is 0, isolated k-mers cell (0, 0), branching ones o >= 2 or i >= 2, simple ones cell (1, 1)
+ *   bfcg_kmers_extend     the unambiguous path to the right of each of n seeds, every k up to 63: bases (host) uint8_t[n * max_len]
+ *                         gets 'A' 'C' 'G' 'T', zero beyond a seed's length; len_stop int32_t[2 n] the length and the stop code.  The
+ *                         rule, in order: a seed that is not present stops with code 4 and length 0; else repeat: the length equals
+ *                         max_len: code 0; o = the present successors of the current k-mer: o = 0 code 1, o >= 2 code 2; nxt = the one
+ *                         present successor: two or more present predecessors, counted on nxt as constructed: code 3; nxt equals the
+ *                         seed's planes: code 5; else its base is appended and the walk goes on from nxt.  max_len outside [1, 65535]
+ *                         is refused; n * max_len above the staging room (16 bytes per k-mer of the lookup's capacity, one path at
+ *                         least) is cut inside the call.  One lane walks one seed with sequential probes, as the corrector's kernel
+ *                         walks a read: made for thousands of seeds and paths of a few hundred bases, not for one long contig.  A walk
+ *                         to the left is the same call on the reverse complement
+ *   bfcg_kmer_revcomp     the planes of the reverse complement (no GPU); -1 for k outside [1, 63]
  * Their host twins and the text forms use no GPU:
  *   bfcg_kmer_from_str    the inverse of bfcg_kmer_2str; -1 unless s has exactly k bytes of ACGTacgt
  *   bfcg_kmer_occ_host    bfc_ch_kmer_occ on listing-style planes of either strand (the four planes of bfc_kmer_t built from the two)
@@ -422,7 +453,13 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *   bfcg_read_stats_host  bfcg_kmers_read_stats's eight words per read from bfc_ch_kmer_occ on the k-mers rolled from the stream's bytes;
  *                         the same refusals
  *   bfcg_read_stats_format one line per read, "%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n": n_kmers n_present n_solid sum min median max
- *                         streak start end (at most 110 bytes each) */
+ *                         streak start end (at most 110 bytes each)
+ *   bfcg_neighbors_host   bfcg_kmers_neighbors from eight bfcg_kmer_occ_host per k-mer
+ *   bfcg_graph_census_host  bfcg_kmers_graph_census over bfc_ch_export_sorted's slots, decoded by bfcg_kmer_decode_host's code
+ *   bfcg_graph_nb_host    the listing's twin, per exported slot: y[2 i], y[2 i + 1] (may be NULL) = the planes of slot i of
+ *                         bfc_ch_export_sorted, nb[i] (may be NULL) = its neighbour bits as bfcg_kmers_list_graph gives them, 0 for a slot
+ *                         with count < min_cnt; returns the number of slots (with both NULL nothing else), -1 refused (k > 37, min_cnt)
+ *   bfcg_extend_host      bfcg_kmers_extend by the same rule (one piece of code for both) on bfcg_kmer_occ_host */
 typedef struct bfcg_kmers bfcg_kmers_t;
 bfcg_kmers_t *bfcg_kmers_create(const bfc_ch_t *ch, int device);
 bfcg_kmers_t *bfcg_kmers_attach(bfcg_ctx_t *ctx);
@@ -455,6 +492,16 @@ int   bfcg_kmers_list_vs(bfcg_kmers_t *a, bfcg_kmers_t *b, int min_cnt, int min_
 bfcg_kmers_t *bfcg_kmers_union(bfcg_kmers_t *a, bfcg_kmers_t *b);
 bfc_ch_t     *bfcg_kmers_export(bfcg_kmers_t *t, uint64_t *n_keys);
 uint64_t bfcg_kmers_format_vs(int k, const uint64_t *y, const uint16_t *cnt_high, const int16_t *other, uint64_t n, char *buf);
+int   bfcg_kmers_neighbors(bfcg_kmers_t *t, const uint64_t *y, uint64_t n, int16_t *out);
+int   bfcg_kmers_graph_census(bfcg_kmers_t *t, int min_cnt, uint64_t deg[25]);
+int   bfcg_kmers_list_graph(bfcg_kmers_t *t, int min_cnt, uint32_t cell_mask, uint32_t sub_lo, uint32_t sub_hi, uint64_t *y, uint16_t *cnt_high, uint8_t *nb,
+                            uint64_t cap, uint64_t *n);
+int   bfcg_kmers_extend(bfcg_kmers_t *t, const uint64_t *y, uint64_t n, int min_cnt, int max_len, uint8_t *bases, int32_t *len_stop);
+int   bfcg_kmer_revcomp(int k, const uint64_t y_in[2], uint64_t y_out[2]);
+int   bfcg_neighbors_host(const bfc_ch_t *ch, const uint64_t *y, uint64_t n, int16_t *out);
+int   bfcg_graph_census_host(const bfc_ch_t *ch, int min_cnt, uint64_t deg[25]);
+int64_t bfcg_graph_nb_host(const bfc_ch_t *ch, int min_cnt, uint64_t *y, uint8_t *nb);
+int   bfcg_extend_host(const bfc_ch_t *ch, const uint64_t *y, uint64_t n, int min_cnt, int max_len, uint8_t *bases, int32_t *len_stop);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);

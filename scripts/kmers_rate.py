@@ -2,7 +2,7 @@
 from the attached context, kernels only, against the path it replaces for the spectrum -- bfcg_export_table followed by the host's
 bfc_ch_hist.  Not the headline bench; numbers quoted in profiles/kmers_rate.md.
 
-    python scripts/kmers_rate.py [--lookup | --readstats | --compare] [k] [bf_shift] [genome size] [coverage]
+    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph] [k] [bf_shift] [genome size] [coverage]
 
 --lookup measures the other direction instead (bfcg_lookup.hip): lookup() of every listed k-mer in shuffled order, and profile() over a
 prefix of the reads that built the table, each next to the host's loop over bfc_ch_kmer_occ on the same input (bfcg_kmers_occ_host,
@@ -12,6 +12,9 @@ wall time with its D2H, and next to them the way to the same numbers without it 
 --compare measures two tables against each other (bfcg_tabcmp.hip): the table of all reads and the table of the first half of the reads,
 both resident; joint_hist(), a full list_vs() and union(), kernels only, against the bytes of both tables at the copy rate, and next to
 them the route without them -- export both tables, bfc_ch_union on the host (one thread).
+--graph measures the table read as a de Bruijn graph (bfcg_graph.hip): graph_census(), a full list_graph() and neighbors() of 2^20 listed
+k-mers, kernels only.  A census is eight random 8-byte probes per node: 8 x nodes / time is put next to the chip's gather rate, and the
+census next to the route without it -- export the table, bfcg_graph_census_host on the CPU (one thread).
 """
 import os
 import sys
@@ -33,6 +36,9 @@ if READSTATS:
 COMPARE = "--compare" in sys.argv
 if COMPARE:
     sys.argv.remove("--compare")
+GRAPH = "--graph" in sys.argv
+if GRAPH:
+    sys.argv.remove("--graph")
 arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
 k, b, G, cov = arg(1, 31), arg(2, 33), arg(3, 4_600_000), arg(4, 100)
 rs = gen.ReadSet(seed=2, G=G, cov=cov)
@@ -216,6 +222,54 @@ def compare_rates():
     for x in (th, hu, ta, tb, u, kb, g2):
         x.close()
 
+
+def graph_rates(min_cnt=1):
+    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
+    print("build %s" % bfc_amd._lib.build_id())
+    cms = []
+    for rep in range(5):
+        deg = km.graph_census(min_cnt)
+        cms.append(km.last_ms())
+    nodes, best = int(deg.sum()), min(cms)
+    print("graph_census (min_cnt %d; one pass, decode + eight probes per node), 5 runs (ms): %s" % (min_cnt, f(cms)))
+    print("census:\n%s" % "\n".join("\t".join(str(int(v)) for v in row) for row in deg))
+    print("graph_census best: %.3f ms; %d nodes, 8 probes each = %.2f G probes/s = %.3f of the %.1f G gathers/s ceiling; the table once in that time = %.2f TB/s"
+          % (best, nodes, 8 * nodes / best / 1e6, 8 * nodes / best / 1e6 / GATHER_G, GATHER_G, slots * 8 / best / 1e9))
+    lms = []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        y, c, h, nb = km.list_graph(min_cnt)
+        wall = time.perf_counter() - t0
+        lms.append(km.last_ms())
+    assert len(c) == nodes
+    km.list()
+    print("list_graph (all %d nodes with nb; count + scan + emit, eight probes per node in both passes), 3 runs (ms): %s; wall of the last with copies %.1f ms; list() alone: %.3f ms"
+          % (nodes, f(lms), wall * 1e3, km.last_ms()))
+    print("list_graph best: %.3f ms = %.2f G probes/s = %.3f of the gather ceiling" % (min(lms), 16 * nodes / min(lms) / 1e6, 16 * nodes / min(lms) / 1e6 / GATHER_G))
+    q = np.ascontiguousarray(y[np.random.default_rng(1).permutation(len(y))[:1 << 20]])
+    nms, nwall = [], []
+    for rep in range(4):
+        t0 = time.perf_counter()
+        nv = km.neighbors(q)
+        nwall.append((time.perf_counter() - t0) * 1e3)
+        nms.append(km.last_ms())
+    print("neighbors (%d listed k-mers, shuffled), 4 runs, kernel only (ms): %s; wall with the copies: %s" % (len(q), f(nms), " ".join("%.1f" % v for v in nwall)))
+    print("neighbors best: %.3f ms = %.2f G probes/s = %.3f of the gather ceiling" % (min(nms), 8 * len(q) / min(nms) / 1e6, 8 * len(q) / min(nms) / 1e6 / GATHER_G))
+    t0 = time.perf_counter()
+    t = g.export_table()
+    t1 = time.perf_counter()
+    hdeg = t.graph_census(min_cnt)
+    t2 = time.perf_counter()
+    assert np.array_equal(hdeg, deg) and np.array_equal(t.neighbors(q[:4096]), nv[:4096])
+    print("export + host bfcg_graph_census_host, one thread: %.1f ms + %.1f ms = %.1f ms (the same census: %.0fx the kernel)" % ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t2 - t0) * 1e3, (t2 - t0) * 1e3 / best))
+    t.close()
+
+
+if GRAPH:
+    graph_rates()
+    km.close()
+    g.close()
+    sys.exit(0)
 
 if COMPARE:
     compare_rates()
