@@ -182,6 +182,8 @@ SYMBOLS = {
     "bfcg_graph_census_host": (C.c_int, [C.c_void_p, C.c_int, u64p]),
     "bfcg_graph_nb_host": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bfcg_extend_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bfcg_kmers_unitigs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "bfcg_unitigs_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_hash_positions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "bfcg_seen_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
 }

@@ -123,6 +123,27 @@ def _graph_seeds(y, max_len):
     return y, np.zeros((len(y), max(0, int(max_len))), dtype=np.uint8), np.zeros((len(y), 2), dtype=np.int32)
 
 
+def _unitigs(L, fn, obj, min_cnt):
+    """(seq u8, off u64 (n + 1), n_kmers u32, cnt_sum u64, ends u8) of bfcg_kmers_unitigs / bfcg_unitigs_host on `obj`: the sizing call
+    with caps of 0, then the call that writes."""
+    n = (C.c_uint64 * 2)()
+    rc = fn(obj, int(min_cnt), None, 0, None, None, None, None, 0, n)
+    if rc < 0:
+        raise BfcGpuError(L.bfcg_last_error().decode())
+    seq, off = np.zeros(n[1], dtype=np.uint8), np.zeros(n[0] + 1, dtype=np.uint64)
+    nk, cs, ends = np.zeros(n[0], dtype=np.uint32), np.zeros(n[0], dtype=np.uint64), np.zeros(n[0], dtype=np.uint8)
+    if rc == 1 and fn(obj, int(min_cnt), seq.ctypes.data, len(seq), off.ctypes.data, nk.ctypes.data, cs.ctypes.data, ends.ctypes.data, len(nk), n) != 0:
+        raise BfcGpuError(L.bfcg_last_error().decode() or "the table changed between the sizing call and the call that writes")
+    return seq, off, nk, cs, ends
+
+
+def unitig_rows(seq, off, n_kmers, cnt_sum, ends):
+    """The five arrays of unitigs() as a sorted list of (sequence bytes, n_kmers, cnt_sum, left stop, right stop, cycle 0 / 1)."""
+    s = np.asarray(seq, dtype=np.uint8).tobytes()
+    return sorted((s[int(off[i]):int(off[i + 1])], int(n_kmers[i]), int(cnt_sum[i]), int(ends[i]) & 7, int(ends[i]) >> 3 & 7, int(ends[i]) >> 6 & 1)
+                  for i in range(len(n_kmers)))
+
+
 class HostTable:
     """A host-resident ``bfc_ch_t`` (opaque, htab.h:10-23)."""
 
@@ -222,6 +243,10 @@ class HostTable:
         if self.L.bfcg_extend_host(self.ptr, y.ctypes.data, len(y), int(min_cnt), int(max_len), bases.ctypes.data, ls.ctypes.data) != 0:
             raise BfcGpuError(self.L.bfcg_last_error().decode())
         return bases, ls[:, 0].copy(), ls[:, 1].copy()
+
+    def unitigs(self, min_cnt=1):
+        """(seq u8, off u64 (n + 1), n_kmers u32, cnt_sum u64, ends u8): GpuKmers.unitigs's host twin (bfcg_unitigs_host)."""
+        return _unitigs(self.L, self.L.bfcg_unitigs_host, self.ptr, min_cnt)
 
     def insert(self, y0, y1, is_high, forced=1):
         return self.L.bfc_ch_insert(self.ptr, (C.c_uint64 * 2)(y0, y1), int(is_high), forced)
@@ -979,9 +1004,19 @@ class GpuKmers:
         self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
         return bases, ls[:, 0].copy(), ls[:, 1].copy()
 
+    def unitigs(self, min_cnt=1):
+        """The compacted graph, every maximal non-branching path exactly once (odd k <= 37; include/bfc_gpu.h defines link, path, cycle
+        and the spelling emitted): (seq u8 of 'A' 'C' 'G' 'T', the unitigs back to back; off u64 (n + 1), unitig i = seq[off[i]:off[i + 1]];
+        n_kmers u32; cnt_sum u64, the sum of its k-mers' counts; ends u8 = left stop | right stop << 3 | 64 for a cycle).  Stop codes:
+        1 no next k-mer, 2 several, 3 the next one has another way in, 6 the only way on leads back into the node itself.  The order is
+        unspecified (unitig_rows() sorts).  Two calls: one that sizes, one that writes; last_ms() is the second's."""
+        out = _unitigs(self.L, self.L.bfcg_kmers_unitigs, self.t, min_cnt)
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return out
+
     def last_ms(self):
         """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces,
-        read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces, neighbors() / list_graph() / extend() all their pieces, graph_census() one pass; of a union() result,
+        read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces, neighbors() / list_graph() / extend() all their pieces, graph_census() one pass, unitigs() the call that writes; of a union() result,
         its size passes and fill."""
         return self._ms
 

@@ -1,12 +1,9 @@
 // bfcg_graph.hip -- the count table read as a de Bruijn graph where it lies in HBM: which of a k-mer's eight neighbours the table holds, the
 // degree census of all its k-mers, the k-mers of chosen degree cells, the unambiguous path from a seed.  DESIGN.md section 6d.
 //
-// A k-mer is the two planes a listing hands out (bit l = the base l from the 3' end); succ(x, c) shifts both planes left and puts base c
-// at the 3' end, pred(x, c) shifts them right and puts c at the 5' end.  The VALUE of a k-mer is what bfcg_kmers_lookup answers for it, on
-// the strand as constructed.  A kernel holds a k-mer as k_lookup does, as the two windows of its strand (oldest base at bit 0): a
-// neighbour's windows are the k-mer's shifted by one with one bit pair replaced, so the bit reversal is done once per k-mer and the
-// eight hashes start from there (kmer_hash_windows, kmer_dev.h).  All eight home slots are loaded before the first is looked at.
-//   k_neighbors     one k-mer per lane, eight values out as one 16-byte store (every k: only the forward hash is needed)
+// The k-mer in registers, the probes of its neighbours and the table asked by planes on the device and on the host are bfcg_gprobe.h's,
+// shared with bfcg_unitigs.hip (the compacted graph).
+//   k_neighbors    one k-mer per lane, eight values out as one 16-byte store (every k: only the forward hash is needed)
 //   k_graph_census  k_tab_hist's walk (a wave on a contiguous span, 16 bytes per lane); a slot that is a node is decoded (bfcg_kdec.h,
 //                   k <= 37), its neighbours probed, cell 5 o + i counted in the wave's 25 LDS bins; a workgroup flushes its non-zero
 //                   bins with one 64-bit atomic each
@@ -23,6 +20,7 @@
 #include "bfc_host.h"
 #include "kmer_dev.h"
 #include "bfcg_klist.h"
+#include "bfcg_gprobe.h"
 
 namespace {
 
@@ -30,93 +28,6 @@ enum { NB_BT = 256, NB_GRID_MAX = 256 * 8 /* eight workgroups on each of the 256
 enum { CENSUS_UNROLL = 2, CENSUS_CELLS = 25, CENSUS_ROW = 32 /* a wave's bins, padded */, CENSUS_GRID_MAX = 1024 }; // BT, WAVES, lane_id: bfcg_klist.h
 enum { EXT_BT = 64 /* a lane walks a seed: short workgroups spread few seeds over many CUs */, EXT_MAX_LEN = 65535 };
 
-struct TabRef { const unsigned long long *tab; int k, l_pre, cshift; };
-
-__host__ __device__ __forceinline__ bool present(int v, int min_cnt) { return v >= 0 && (v & 0xff) >= min_cnt; }
-
-// ---- a k-mer as windows, its neighbours, the probes -------------------------------------------------------------------------------
-template <typename W> struct Win { W lo, hi; }; // low / high code bit, the base at the 5' end in bit 0; bits at and above k are 0
-
-template <typename W> __device__ __forceinline__ Win<W> win_of_planes(int k, uint64_t a, uint64_t b) // bits of the planes at and above k fall out
-{
-	constexpr int nb = 8 * (int)sizeof(W);
-	Win<W> w;
-	w.lo = bfcg::brev_w((W)a) >> (nb - k); w.hi = bfcg::brev_w((W)b) >> (nb - k);
-	return w;
-}
-template <typename W> __device__ __forceinline__ Win<W> win_succ(int k, const Win<W> w, int c) // the 5' base falls out, c is the new 3' base
-{
-	Win<W> r;
-	r.lo = (w.lo >> 1) | (W)(c & 1) << (k - 1); r.hi = (w.hi >> 1) | (W)(c >> 1) << (k - 1);
-	return r;
-}
-template <typename W> __device__ __forceinline__ Win<W> win_pred(int k, const Win<W> w, int c) // the 3' base falls out, c is the new 5' base
-{
-	const W m = bfcg::kmask<W>(k);
-	Win<W> r;
-	r.lo = ((w.lo << 1) & m) | (W)(c & 1); r.hi = ((w.hi << 1) & m) | (W)(c >> 1);
-	return r;
-}
-
-// ch_get_dev (kmer_dev.h) in two halves: the hash, the home slot and its load; then the rest of the chain.  A caller starts all its
-// probes before it finishes the first.
-struct Probe { const unsigned long long *reg; uint64_t key; uint32_t pos, cmask; unsigned long long cur; };
-
-template <typename W> __device__ __forceinline__ Probe probe_first(const TabRef &T, const Win<W> w)
-{
-	uint64_t y0, y1, key;
-	bfcg::kmer_hash_windows<W>(T.k, w.lo, w.hi, y0, y1);
-	const uint32_t sub = bfcg::ch_subkey(T.k, T.l_pre, y0, y1, key);
-	Probe p;
-	p.key = key >> 14; p.cmask = (1u << T.cshift) - 1;
-	p.reg = T.tab + ((uint64_t)sub << T.cshift);
-	p.pos = (uint32_t)p.key & p.cmask;
-	p.cur = p.reg[p.pos];
-	return p;
-}
-__device__ __forceinline__ int probe_rest(Probe p) // -1, or high << 8 | count: it ends at the key, at an empty slot, or after a whole region
-{
-	for (uint32_t probe = 0;;) {
-		if (p.cur == 0) return -1;
-		if ((p.cur >> 14) == p.key) return (int)(p.cur & 0x3fff);
-		if (++probe > p.cmask) return -1;
-		p.pos = (p.pos + 1) & p.cmask;
-		p.cur = p.reg[p.pos];
-	}
-}
-
-// v[c] = the value of succ(x, c), v[4 + c] = that of pred(x, c)
-template <typename W> __device__ __forceinline__ void values8(const TabRef &T, const Win<W> w, int v[8])
-{
-	Probe p[8];
-#pragma unroll
-	for (int c = 0; c < 4; ++c) { p[c] = probe_first<W>(T, win_succ<W>(T.k, w, c)); p[4 + c] = probe_first<W>(T, win_pred<W>(T.k, w, c)); }
-#pragma unroll
-	for (int j = 0; j < 8; ++j) v[j] = probe_rest(p[j]);
-}
-// bit c: succ(x, c) is present at min_cnt (pred = 0), or pred(x, c) (pred = 1)
-template <typename W> __device__ __forceinline__ int present4(const TabRef &T, const Win<W> w, int pred, int min_cnt)
-{
-	Probe p[4];
-#pragma unroll
-	for (int c = 0; c < 4; ++c) p[c] = probe_first<W>(T, pred ? win_pred<W>(T.k, w, c) : win_succ<W>(T.k, w, c));
-	int r = 0;
-#pragma unroll
-	for (int c = 0; c < 4; ++c) r |= (int)present(probe_rest(p[c]), min_cnt) << c;
-	return r;
-}
-// the neighbour bits of the k-mer in `slot` of sub-table `sub`: bit c succ by c present, bit 4 + c pred by c present
-template <typename W> __device__ __forceinline__ uint32_t node_nb(const TabRef &T, uint32_t sub, uint64_t slot, int min_cnt)
-{
-	uint64_t a, b;
-	kdec::decode(T.k, T.l_pre, sub, slot, a, b);
-	int v[8];
-	values8<W>(T, win_of_planes<W>(T.k, a, b), v);
-	uint32_t nb = 0;
-#pragma unroll
-	for (int j = 0; j < 8; ++j) nb |= (uint32_t)present(v[j], min_cnt) << j;
-	return nb;
-}
 __host__ __device__ __forceinline__ int cell_of(uint32_t nb) { return 5 * __builtin_popcount(nb & 15) + __builtin_popcount(nb >> 4); }
 
 // ---- k_neighbors ------------------------------------------------------------------------------------------------------------------
@@ -205,15 +116,6 @@ __host__ __device__ __forceinline__ void extend_rule(const T &tab, int k, uint64
 	len_stop[0] = len; len_stop[1] = stop;
 }
 
-template <typename W> struct DevGraph {
-	TabRef T;
-	__device__ __forceinline__ bool present(uint64_t a, uint64_t b, int min_cnt) const
-	{
-		return ::present(probe_rest(probe_first<W>(T, win_of_planes<W>(T.k, a, b))), min_cnt);
-	}
-	__device__ __forceinline__ int present4(uint64_t a, uint64_t b, int pred, int min_cnt) const { return ::present4<W>(T, win_of_planes<W>(T.k, a, b), pred, min_cnt); }
-};
-
 template <typename W>
 __global__ __launch_bounds__(EXT_BT) void k_extend(TabRef T, const ulonglong2 *__restrict__ y, uint64_t n, int min_cnt, int max_len, uint8_t *__restrict__ bases,
                                                    int32_t *__restrict__ len_stop)
@@ -225,23 +127,6 @@ __global__ __launch_bounds__(EXT_BT) void k_extend(TabRef T, const ulonglong2 *_
 	extend_rule(g, T.k, x.x, x.y, min_cnt, max_len, bases + i * (uint64_t)max_len, len_stop + 2 * i);
 }
 
-TabRef tab_ref(const bfcg_kmers_t *t)
-{
-	TabRef T;
-	T.tab = t->table; T.k = t->k; T.l_pre = t->l_pre; T.cshift = t->cshift;
-	return T;
-}
-
-int check_min_cnt(const char *who, int min_cnt)
-{
-	if (min_cnt < 1 || min_cnt > 255) return bfcg::fail("%s: min_cnt %d is outside [1, 255]: a count is 8 bits, and a key the table holds was counted at least once", who, min_cnt);
-	return 0;
-}
-int check_decodable(int k)
-{
-	if (!kdec::decodable(k)) return bfcg::fail("k-mers cannot be listed for k=%d: the table's key is lossless only for k <= %d (sizes and histogram work for any k)", k, (int)kdec::MAX_K);
-	return 0;
-}
 int check_cell_mask(const char *who, uint32_t cell_mask)
 {
 	if (cell_mask == 0 || cell_mask >> CENSUS_CELLS) return bfcg::fail("%s: cell_mask 0x%x names no cell or one beyond bit 24 (bit 5 o + i: o successors, i predecessors)", who, cell_mask);
@@ -365,33 +250,6 @@ extern "C" int bfcg_kmers_extend(bfcg_kmers_t *t, const uint64_t *y, uint64_t n,
 
 // ---- the host twins: no GPU ---------------------------------------------------------------------------------------------------------
 
-namespace {
-
-struct HostGraph {
-	const bfc_ch_t *ch; int k;
-	bool present(uint64_t a, uint64_t b, int min_cnt) const
-	{
-		const uint64_t y[2] = { a, b };
-		return ::present(bfcg_kmer_occ_host(ch, y), min_cnt);
-	}
-	int value(uint64_t a, uint64_t b, int pred, int c) const // of succ or pred by c
-	{
-		const uint64_t m = kdec::mask(k);
-		a &= m; b &= m;
-		const uint64_t y[2] = { pred ? a >> 1 | (uint64_t)(c & 1) << (k - 1) : (a << 1 | (uint64_t)(c & 1)) & m,
-		                        pred ? b >> 1 | (uint64_t)(c >> 1) << (k - 1) : (b << 1 | (uint64_t)(c >> 1)) & m };
-		return bfcg_kmer_occ_host(ch, y);
-	}
-	int present4(uint64_t a, uint64_t b, int pred, int min_cnt) const
-	{
-		int r = 0;
-		for (int c = 0; c < 4; ++c) r |= (int)::present(value(a, b, pred, c), min_cnt) << c;
-		return r;
-	}
-};
-
-} // namespace
-
 extern "C" int bfcg_kmer_revcomp(int k, const uint64_t y_in[2], uint64_t y_out[2])
 {
 	if (k < 1 || k > 63 || !y_in || !y_out) return -1;
@@ -414,26 +272,6 @@ extern "C" int bfcg_neighbors_host(const bfc_ch_t *ch, const uint64_t *y, uint64
 			out[8 * i + 4 + c] = (int16_t)g.value(y[2 * i], y[2 * i + 1], 1, c);
 		}
 	return 0;
-}
-
-// every slot of bfc_ch_export_sorted, in its order: fn(i, slot, a, b) with the slot's planes.  The number of slots, or -1 with the message set
-template <class F> static int64_t each_slot_host(const bfc_ch_t *ch, const F &fn)
-{
-	const int k = bfc_ch_get_k(ch), l_pre = bfc_ch_get_lpre(ch);
-	const uint64_t n = bfc_ch_export_sorted(ch, NULL, NULL);
-	uint32_t *sizes = (uint32_t *)malloc(4ULL << l_pre);
-	uint64_t *slots = (uint64_t *)malloc(n ? n * 8 : 8);
-	if (!sizes || !slots) { free(sizes); free(slots); return bfcg::fail("out of host memory"); }
-	bfc_ch_export_sorted(ch, sizes, slots);
-	uint64_t i = 0;
-	for (uint64_t s = 0; s < 1ULL << l_pre; ++s)
-		for (uint32_t j = 0; j < sizes[s]; ++j, ++i) {
-			uint64_t a, b;
-			kdec::decode(k, l_pre, (uint32_t)s, slots[i], a, b);
-			fn(i, slots[i], a, b);
-		}
-	free(sizes); free(slots);
-	return (int64_t)n;
 }
 
 extern "C" int64_t bfcg_graph_nb_host(const bfc_ch_t *ch, int min_cnt, uint64_t *y, uint8_t *nb)

@@ -1,4 +1,4 @@
-// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_mg.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip, bfcg_graph.hip):
+// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_mg.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip, bfcg_graph.hip, bfcg_unitigs.hip):
 // kernel parameters and launchers, the one error channel, the resident registry, what the satellites and the group layer borrow from a context
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +32,7 @@ extern "C" int bfcg_resident_register(const void *bf, void *dev, int device, int
 
 /* the table read-out's object (include/bfc_gpu.h: bfcg_kmers_t): made and destroyed in bfcg_kmers.hip, which lists the table; bfcg_lookup.hip probes it,
    bfcg_readstats.hip reduces a profile per read */
+#define BFCG_UT_NBUF 20
 struct bfcg_kmers {
 	int k, l_pre, cshift, device, owns_table;
 	hipStream_t st;
@@ -49,7 +50,9 @@ struct bfcg_kmers {
 	unsigned long long *d_joint;        // 256 x 256 bins of a joint spectrum and the two counters of a union (bfcg_tabcmp.hip; allocated by the first call)
 	uint8_t *d_gout; uint64_t gout_cap; // a graph call's answers: eight values per k-mer of bfcg_kmers_neighbors, the paths of bfcg_kmers_extend (bfcg_graph.hip; grown on demand, in bytes)
 	int32_t *d_gls; uint64_t gls_cap;   // length and stop code per seed of bfcg_kmers_extend (bfcg_graph.hip; grown on demand, in bytes)
-	uint64_t n_keys; int has_keys;      // the keys of a table this object built and owns (bfcg_kmers_union counts them on the device)
+	void *d_ut[BFCG_UT_NBUF]; uint64_t ut_bytes[BFCG_UT_NBUF]; // bfcg_kmers_unitigs's buffers, named in bfcg_unitigs.hip (grown on demand, in bytes)
+	uint64_t ut_cap;                    // starts a walk kernel of bfcg_kmers_unitigs takes per launch (BFCG_UNITIG_CAP at creation)
+	uint64_t n_keys; int has_keys;     // the keys of a table this object built and owns (bfcg_kmers_union counts them on the device)
 	float last_ms;
 };
 
@@ -196,6 +199,8 @@ int kcov_adopted(::bfcg_kcov *t);
 BFCG_LOCAL ::bfcg_kmers *kmers_new(int k, int l_pre, int cshift, int device);
 // k-mers a lookup stages per piece (bfcg_lookup.hip): a few million, or what BFCG_LOOKUP_CAP says
 BFCG_LOCAL uint64_t lookup_cap();
+// starts a walk kernel of bfcg_kmers_unitigs takes per launch (bfcg_unitigs.hip): 2^22, or what BFCG_UNITIG_CAP says
+BFCG_LOCAL uint64_t unitig_cap();
 // a lookup's staging buffers d_qy / d_qout of q_cap k-mers, allocated by the first call that needs them (bfcg_lookup.hip; bfcg_graph.hip stages its k-mers in d_qy)
 BFCG_LOCAL int lookup_stage(::bfcg_kmers *t);
 // a profile's first half (bfcg_lookup.hip): the stream staged in d_pseq if it is the host's, d_pout grown, t->e0 recorded and k_profile launched

@@ -1,11 +1,12 @@
 // bfcg_klist.h -- the listing of a count table, k_tab_list, for the files that list: bfcg_kmers.hip (bfcg_kmers_list, the table alone),
-// bfcg_tabcmp.hip (bfcg_kmers_list_vs, the table filtered and annotated by a second one) and bfcg_graph.hip (bfcg_kmers_list_graph, by
+// bfcg_unitigs.hip (the ends of the graph's paths, left on the device: list_dev), bfcg_tabcmp.hip (bfcg_kmers_list_vs, the table filtered and annotated by a second one) and bfcg_graph.hip (bfcg_kmers_list_graph, by
 // its own graph).  The three kernels and the host sequence around them are written once, as templates over what a predicate says about
 // a slot:
 //   NoOther        nothing: every slot that passes -m / -d is kept, no third output
 //   a probing type keep(sub, slot, o): a third output column of its col_t per k-mer
 //     VsOther   (bfcg_tabcmp.hip) o = the slot's key looked up in the other table, kept or not by its count
 //     GraphPred (bfcg_graph.hip)  o = which of the slot's eight de Bruijn neighbours the table holds, kept or not by its degree cell
+//     EndPred   (bfcg_unitigs.hip) o = the stop codes of a node's two sides, kept if one of them is open
 //
 //   k_tab_list   a range of sub-tables in blocks of LIST_BLK slots: k_list_count counts the slots that pass the filter per block,
 //                k_list_scan turns the counts into offsets, k_list_emit decodes (bfcg_kdec.h) and stores in slot order -- sub-tables
@@ -150,15 +151,16 @@ __global__ __launch_bounds__(BT) void k_list_emit(const ulonglong2 *__restrict__
 	}
 }
 
-// The host's side of one listing of sub-tables [sub_lo, sub_hi) of t, the arguments checked by the caller (`who` names it in messages):
-// count + scan, the total read back, then -- if it fits `cap` -- emit and the copies.  0 / 1 / -1 as bfcg_kmers_list.
+
+// The device's side of one listing of sub-tables [sub_lo, sub_hi) of t, the arguments checked by the caller (`who` names it in messages;
+// `have_bufs`: the caller has somewhere to put `cap` rows): count + scan, the total read back, then -- if it fits `cap` -- emit, after
+// which the rows lie in t->d_y / d_ch / d_oth and the stream is idle.  0 / 1 / -1 as bfcg_kmers_list; t->last_ms = its kernels.
 template <class O>
-int list_run(bfcg_kmers_t *t, const char *who, const O &other, int min_cnt, int min_diff, uint32_t sub_lo, uint32_t sub_hi, uint64_t *y, uint16_t *cnt_high,
-             typename O::col_t *oth, uint64_t cap, uint64_t *n)
+int list_dev(bfcg_kmers_t *t, const char *who, const O &other, int min_cnt, int min_diff, uint32_t sub_lo, uint32_t sub_hi, bool have_bufs, uint64_t cap, uint64_t *n)
 {
 	if (!kdec::decodable(t->k)) return bfcg::fail("k-mers cannot be listed for k=%d: the table's key is lossless only for k <= %d (sizes and histogram work for any k)", t->k, (int)kdec::MAX_K);
 	if (sub_lo > sub_hi || (uint64_t)sub_hi > 1ULL << t->l_pre) return bfcg::fail("sub-table range [%u, %u) outside [0, 2^%d]", sub_lo, sub_hi, t->l_pre);
-	if (cap && (!y || !cnt_high || (O::probes && !oth))) return bfcg::fail("%s needs output buffers for cap=%llu", who, (unsigned long long)cap);
+	if (cap && !have_bufs) return bfcg::fail("%s needs output buffers for cap=%llu", who, (unsigned long long)cap);
 	*n = 0; t->last_ms = 0;
 	if (sub_lo == sub_hi) return 0;
 	BFCG_CK(hipSetDevice(t->device));
@@ -197,12 +199,23 @@ int list_run(bfcg_kmers_t *t, const char *who, const O &other, int min_cnt, int 
 	hipLaunchKernelGGL((k_list_emit<O>), dim3((unsigned)n_blk), dim3(BT), 0, t->st, (const ulonglong2 *)t->table, G, other, t->d_off, t->d_y, t->d_ch, (typename O::col_t *)t->d_oth, (uint64_t)total);
 	BFCG_CK(hipEventRecord(t->e1, t->st));
 	BFCG_CK(hipGetLastError());
-	BFCG_CK(hipMemcpyAsync(y, t->d_y, total * 16, hipMemcpyDeviceToHost, t->st));
-	BFCG_CK(hipMemcpyAsync(cnt_high, t->d_ch, total * 2, hipMemcpyDeviceToHost, t->st));
-	if (O::probes) BFCG_CK(hipMemcpyAsync(oth, t->d_oth, total * sizeof(typename O::col_t), hipMemcpyDeviceToHost, t->st));
 	BFCG_CK(hipStreamSynchronize(t->st));
 	BFCG_CK(hipEventElapsedTime(&ms2, t->e0, t->e1));
 	t->last_ms = ms1 + ms2;
+	return 0;
+}
+
+// ... and the host's: list_dev, then the rows copied out
+template <class O>
+int list_run(bfcg_kmers_t *t, const char *who, const O &other, int min_cnt, int min_diff, uint32_t sub_lo, uint32_t sub_hi, uint64_t *y, uint16_t *cnt_high,
+             typename O::col_t *oth, uint64_t cap, uint64_t *n)
+{
+	const int rc = list_dev(t, who, other, min_cnt, min_diff, sub_lo, sub_hi, y && cnt_high && (!O::probes || oth), cap, n);
+	if (rc != 0 || *n == 0) return rc;
+	BFCG_CK(hipMemcpyAsync(y, t->d_y, *n * 16, hipMemcpyDeviceToHost, t->st));
+	BFCG_CK(hipMemcpyAsync(cnt_high, t->d_ch, *n * 2, hipMemcpyDeviceToHost, t->st));
+	if (O::probes) BFCG_CK(hipMemcpyAsync(oth, t->d_oth, *n * sizeof(typename O::col_t), hipMemcpyDeviceToHost, t->st));
+	BFCG_CK(hipStreamSynchronize(t->st));
 	return 0;
 }
 

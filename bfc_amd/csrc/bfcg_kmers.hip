@@ -94,7 +94,7 @@ bfcg_kmers_t *bfcg::kmers_new(int k, int l_pre, int cshift, int device)
 	bfcg_kmers_t *t = (bfcg_kmers_t *)calloc(1, sizeof(bfcg_kmers_t));
 	if (!t) { bfcg::fail("out of host memory"); return NULL; }
 	t->k = k; t->l_pre = l_pre; t->cshift = cshift; t->device = device;
-	t->q_cap = bfcg::lookup_cap();
+	t->q_cap = bfcg::lookup_cap(); t->ut_cap = bfcg::unitig_cap();
 	BFCG_CKN(bfcg_kmers_destroy(t), hipStreamCreate(&t->st));
 	BFCG_CKN(bfcg_kmers_destroy(t), hipEventCreate(&t->e0)); BFCG_CKN(bfcg_kmers_destroy(t), hipEventCreate(&t->e1));
 	BFCG_CKN(bfcg_kmers_destroy(t), hipMalloc(&t->d_hist, HIST_BINS * 8));
@@ -138,6 +138,7 @@ extern "C" void bfcg_kmers_destroy(bfcg_kmers_t *t)
 	(void)hipFree(t->d_hist); (void)hipFree(t->d_sizes); (void)hipFree(t->d_cnt); (void)hipFree(t->d_off); (void)hipFree(t->d_y); (void)hipFree(t->d_ch);
 	(void)hipFree(t->d_qy); (void)hipFree(t->d_qout); (void)hipFree(t->d_pseq); (void)hipFree(t->d_pout); (void)hipFree(t->d_roff); (void)hipFree(t->d_rout);
 	(void)hipFree(t->d_oth); (void)hipFree(t->d_joint); (void)hipFree(t->d_jpart); (void)hipFree(t->d_gout); (void)hipFree(t->d_gls);
+	for (int i = 0; i < BFCG_UT_NBUF; ++i) (void)hipFree(t->d_ut[i]);
 	if (t->e0) (void)hipEventDestroy(t->e0);
 	if (t->e1) (void)hipEventDestroy(t->e1);
 	if (t->st) (void)hipStreamDestroy(t->st);

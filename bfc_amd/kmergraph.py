@@ -1,6 +1,6 @@
 """A `bfc -d` dump read as a de Bruijn graph on the GPU: how many k-mers are dead ends, how many branch, and what lies around a k-mer.
 
-    python -m bfc_amd.kmergraph [-m INT] [-t|-b] [-x FILE] [-l INT] table.dump
+    python -m bfc_amd.kmergraph [-m INT] [-t|-b] [-u] [-x FILE] [-l INT] table.dump
 
 The dump is restored with bfc_ch_restore and uploaded.  A k-mer is PRESENT if the table holds it with count >= INT (-m, default 1); a NODE
 is a k-mer of the table with such a count, on the strand the table stores (the one hash2cnt prints); its out-degree o is the number of
@@ -24,6 +24,13 @@ such tool, so the output format is this project's.  Standard output, in this ord
                           sequence around each k-mer, walked both ways for at most INT bases (-l, default 10000) by bfcg_kmers_extend --
                           to the left as the same walk on the reverse complement.  Stop codes: 0 the limit, 1 no next k-mer, 2 several,
                           3 the next one has another way in, 4 the seed is absent, 5 back at the seed
+    unitigs<TAB>N, cycles<TAB>N, n50<TAB>N
+                          under -u (odd k <= 37), after the census lines: the compacted graph (bfcg_kmers_unitigs) -- its unitigs, how many
+                          of them are cycles, and the N50 of their lengths in bases; then one line per unitig, sorted by sequence:
+    unitig<TAB>seq<TAB>n_kmers<TAB>mean_count<TAB>left_stop<TAB>right_stop<TAB>circular
+                          mean_count with two decimals; the stop codes of the two ends are 1, 2, 3 as above and 6, the only way on
+                          leads back into the node itself (its own k-mer or its reverse complement); a cycle has 0 0 1 and repeats its
+                          first k - 1 bases at the end
 """
 import ctypes as C
 import getopt
@@ -36,6 +43,7 @@ Options:
   -m INT   a k-mer is present with occ >= INT [1]
   -t       list the tips
   -b       list the branching k-mers
+  -u       list the unitigs of the compacted graph (odd k <= 37)
   -x FILE  extend the k-mers of FILE both ways and print the unitig around each
   -l INT   at most INT bases each way [10000]
 """
@@ -74,10 +82,25 @@ def _extend_file(api, km, fn, min_cnt, max_len, out):
     return 0
 
 
+def n50(lengths):
+    """the length L such that unitigs of at least L bases hold half of all bases"""
+    total, run = sum(lengths), 0
+    for v in sorted(lengths, reverse=True):
+        run += v
+        if 2 * run >= total:
+            return v
+    return 0
+
+
+def _unitig_lines(rows, out):
+    out.write(b"unitigs\t%d\ncycles\t%d\nn50\t%d\n" % (len(rows), sum(r[5] for r in rows), n50([len(r[0]) for r in rows])))
+    out.write(b"".join(b"unitig\t%s\t%d\t%.2f\t%d\t%d\t%d\n" % (s, nk, cs / nk, left, right, cyc) for s, nk, cs, left, right, cyc in rows))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     try:
-        opts, args = getopt.getopt(argv, "tbm:x:l:")
+        opts, args = getopt.getopt(argv, "tbum:x:l:")
     except getopt.GetoptError:
         opts, args = [], []
     o = dict(opts)
@@ -94,10 +117,13 @@ def main(argv=None):
     km = api.GpuKmers(t)
     rc = 0
     try:
+        rows = api.unitig_rows(*km.unitigs(min_cnt)) if "-u" in o else None   # (an even k or k > 37 is refused here, before any output)
         if t.k <= 37 or "-x" not in o:   # (k > 37 with -x alone: the walks need no decode)
             deg = km.graph_census(min_cnt)
             out.write("".join("deg\t%d\t%s\n" % (i, "\t".join(str(int(v)) for v in deg[i])) for i in range(5)).encode())
             out.write(b"nodes\t%d\nisolated\t%d\ntips\t%d\nsimple\t%d\nbranching\t%d\n" % summary(deg))
+        if rows is not None:
+            _unitig_lines(rows, out)
         if modes:
             mask = api.GRAPH_MASKS["tips" if modes[0] == "-t" else "branching"]
             for y, ch, nb in km.pieces_graph(min_cnt, mask):

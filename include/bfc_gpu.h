@@ -441,6 +441,53 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *                         walks a read: made for thousands of seeds and paths of a few hundred bases, not for one long contig.  A walk
  *                         to the left is the same call on the reverse complement
  *   bfcg_kmer_revcomp     the planes of the reverse complement (no GPU); -1 for k outside [1, 63]
+ * The compacted graph (bfcg_unitigs.hip): every maximal non-branching path of the graph exactly once, on either form of the object.
+ * Only ODD k <= 37 is served.  For even k the reference's strand rule (kmer.h:81) leaves some k-mers undecided, a k-mer and its reverse
+ * complement can be two keys and there is no strand-free graph to compact; for k > 37 a node cannot be decoded.  Both are refused before
+ * any launch with a message, as is min_cnt outside [1, 255]; a refusal leaves every output untouched and the object usable.
+ *   NODES       for odd k, x and rc(x) (its reverse complement) have one slot and one value.  A node is a slot with count >= min_cnt.  It
+ *               has two oriented k-mers, x and rc(x), and two sides: its right side is where succ(x, .) leaves, its left side is the
+ *               right side of rc(x)
+ *   link(x)     for an oriented k-mer x, with o = the present successors of x, the rules in this order:
+ *                 1. o is empty: no link, stop code 1
+ *                 2. o has more than one: no link, stop code 2
+ *                 3. y is the single one; two or more predecessors of y are present, counted on y as constructed: no link, stop code 3
+ *                 4. y == x or y == rc(x) -- the only way on leads back into the node itself: no link, stop code 6
+ *                 5. otherwise link(x) = y
+ *               Codes 1 to 3 are bfcg_kmers_extend's; 6 is new (extend keeps its own rule: it walks through a hairpin and reports a
+ *               seed's self-loop as 5).  A side without a link is OPEN and carries its stop code
+ *   UNITIGS     for odd k, link(x) = y holds exactly when link(rc(y)) = rc(x): every side has at most one partner, and the components are
+ *               simple paths and simple cycles of nodes.  Each component is one unitig, of n k-mers and k + n - 1 bases
+ *   a path      starts at the oriented k-mer s whose left side is open (link(rc(s)) is none); each link adds one base, up to the oriented
+ *               k-mer e whose right side is open.  Read from the other end it is the reverse complement, from rc(e) to rc(s).  The
+ *               spelling emitted is the one whose first k-mer is smaller as text (A < C < G < T, compared from the 5' end): s against
+ *               rc(e), which cannot be equal for odd k.  A node with both sides open is a unitig of one k-mer, spelled on the smaller of
+ *               its two strands
+ *   a cycle     has every side linked.  It is spelled from its smallest oriented k-mer over both strands, once round: k + n - 1 bases,
+ *               the last k - 1 of which are the first k - 1 of the next lap
+ *               So: an isolated k-mer is one unitig of k bases with ends (1, 1); the k-mer of a run of A's, whose only successor is
+ *               itself, is one unitig "AAA...A" with ends (6, 6); a node whose only successor on one side is its own reverse
+ *               complement (a hairpin, u P comp(u) with P a reverse palindrome of k - 1 bases) has code 6 on that side, and a path
+ *               that runs into it ends there with 6; a cycle has ends 0 and the cycle bit
+ *   bfcg_kmers_unitigs    seq (host) gets 'A' 'C' 'G' 'T', the unitigs back to back, unitig i at [off[i], off[i + 1]); off has n[0] + 1
+ *                         entries; n_kmers[i] and cnt_sum[i] = its k-mers and the sum of their counts; ends[i] = the stop code of the
+ *                         emitted spelling's left side | that of its right side << 3 | 64 for a cycle (whose codes are 0).  n[0] = the
+ *                         unitigs, n[1] = the bases.  The cap protocol is the listing's -- 0: written; 1: seq_cap < n[1] or n_cap <
+ *                         n[0], nothing is written, n[] holds what is needed (a first call with caps of 0 sizes the second); -1: refused,
+ *                         or an error.  The order of the unitigs is unspecified (it is that of the table's slots: paths by the slot of
+ *                         the end that emits, then cycles); the SET does not depend on the table's layout, so an attached table and the
+ *                         upload of its export give the same.  bfcg_kmers_last_ms covers all its kernels.
+ *                         How: a listing pass (bfcg_kmers_list's two kernels, the predicate = a node with an open side; both link rules
+ *                         are evaluated per node, up to 16 probes) yields the path ends; one lane per end and open side walks to the far
+ *                         end, counts, decides which end emits and marks every node it passes in a bitmap of one bit per slot; the
+ *                         nodes left unmarked are the cycles' and are collected by one streaming pass; one lane per such node walks its
+ *                         cycle and gives up at the first oriented k-mer smaller than its own smaller strand, so only the cycle's
+ *                         smallest completes the lap; a scan of the winners' lengths; a fill walk that writes the bases.  A walk kernel
+ *                         takes at most 2^22 starts a launch (BFCG_UNITIG_CAP in the environment when the object is made).  Device
+ *                         memory: one bit per slot, 56 bytes per side of a path end and per cycle node, and the output itself.  A walk is one
+ *                         lane's sequential probes: expected work is near-linear on ordinary sequence (a cycle node gives up after about
+ *                         ln n steps on average), but one unitig of millions of k-mers -- a path, or a cycle's leader on its lap -- runs
+ *                         at the pace of one lane, the caveat bfcg_kmers_read_stats makes for a megabase contig
  * Their host twins and the text forms use no GPU:
  *   bfcg_kmer_from_str    the inverse of bfcg_kmer_2str; -1 unless s has exactly k bytes of ACGTacgt
  *   bfcg_kmer_occ_host    bfc_ch_kmer_occ on listing-style planes of either strand (the four planes of bfc_kmer_t built from the two)
@@ -459,7 +506,9 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *   bfcg_graph_nb_host    the listing's twin, per exported slot: y[2 i], y[2 i + 1] (may be NULL) = the planes of slot i of
  *                         bfc_ch_export_sorted, nb[i] (may be NULL) = its neighbour bits as bfcg_kmers_list_graph gives them, 0 for a slot
  *                         with count < min_cnt; returns the number of slots (with both NULL nothing else), -1 refused (k > 37, min_cnt)
- *   bfcg_extend_host      bfcg_kmers_extend by the same rule (one piece of code for both) on bfcg_kmer_occ_host */
+ *   bfcg_extend_host      bfcg_kmers_extend by the same rule (one piece of code for both) on bfcg_kmer_occ_host
+ *   bfcg_unitigs_host     bfcg_kmers_unitigs -- outputs, cap protocol, refusals -- by the same link rule (one piece of code for both) on
+ *                         bfcg_kmer_occ_host, over bfc_ch_export_sorted's slots: every node walks, no bitmap */
 typedef struct bfcg_kmers bfcg_kmers_t;
 bfcg_kmers_t *bfcg_kmers_create(const bfc_ch_t *ch, int device);
 bfcg_kmers_t *bfcg_kmers_attach(bfcg_ctx_t *ctx);
@@ -502,6 +551,10 @@ int   bfcg_neighbors_host(const bfc_ch_t *ch, const uint64_t *y, uint64_t n, int
 int   bfcg_graph_census_host(const bfc_ch_t *ch, int min_cnt, uint64_t deg[25]);
 int64_t bfcg_graph_nb_host(const bfc_ch_t *ch, int min_cnt, uint64_t *y, uint8_t *nb);
 int   bfcg_extend_host(const bfc_ch_t *ch, const uint64_t *y, uint64_t n, int min_cnt, int max_len, uint8_t *bases, int32_t *len_stop);
+int   bfcg_kmers_unitigs(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
+                         uint64_t n_cap, uint64_t n[2]);
+int   bfcg_unitigs_host(const bfc_ch_t *ch, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
+                        uint64_t n_cap, uint64_t n[2]);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);

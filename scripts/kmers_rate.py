@@ -2,7 +2,7 @@
 from the attached context, kernels only, against the path it replaces for the spectrum -- bfcg_export_table followed by the host's
 bfc_ch_hist.  Not the headline bench; numbers quoted in profiles/kmers_rate.md.
 
-    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph] [k] [bf_shift] [genome size] [coverage]
+    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph | --unitigs] [k] [bf_shift] [genome size] [coverage]
 
 --lookup measures the other direction instead (bfcg_lookup.hip): lookup() of every listed k-mer in shuffled order, and profile() over a
 prefix of the reads that built the table, each next to the host's loop over bfc_ch_kmer_occ on the same input (bfcg_kmers_occ_host,
@@ -15,6 +15,9 @@ them the route without them -- export both tables, bfc_ch_union on the host (one
 --graph measures the table read as a de Bruijn graph (bfcg_graph.hip): graph_census(), a full list_graph() and neighbors() of 2^20 listed
 k-mers, kernels only.  A census is eight random 8-byte probes per node: 8 x nodes / time is put next to the chip's gather rate, and the
 census next to the route without it -- export the table, bfcg_graph_census_host on the CPU (one thread).
+--unitigs measures the compacted graph (bfcg_unitigs.hip): unitigs() -- the sizing call alone (listing of the path ends, counting walks,
+the pass for the cycles' nodes, scans) and the call that also fills -- kernels only, next to a census of the same table and to the route
+without it: export the table, bfcg_unitigs_host on the CPU (one thread).  The per-kernel split is a kernel trace of this script's run.
 """
 import os
 import sys
@@ -39,6 +42,9 @@ if COMPARE:
 GRAPH = "--graph" in sys.argv
 if GRAPH:
     sys.argv.remove("--graph")
+UNITIGS = "--unitigs" in sys.argv
+if UNITIGS:
+    sys.argv.remove("--unitigs")
 arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
 k, b, G, cov = arg(1, 31), arg(2, 33), arg(3, 4_600_000), arg(4, 100)
 rs = gen.ReadSet(seed=2, G=G, cov=cov)
@@ -264,6 +270,54 @@ def graph_rates(min_cnt=1):
     print("export + host bfcg_graph_census_host, one thread: %.1f ms + %.1f ms = %.1f ms (the same census: %.0fx the kernel)" % ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t2 - t0) * 1e3, (t2 - t0) * 1e3 / best))
     t.close()
 
+
+def unitig_rates(min_cnt=1):
+    import ctypes as C
+    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
+    print("build %s" % bfc_amd._lib.build_id())
+    cms = []
+    for rep in range(3):
+        deg = km.graph_census(min_cnt)
+        cms.append(km.last_ms())
+    nodes = int(deg.sum())
+    print("graph_census (min_cnt %d), 3 runs (ms): %s; %d nodes" % (min_cnt, f(cms), nodes))
+    sms, n = [], (C.c_uint64 * 2)()
+    for rep in range(3):
+        assert km.L.bfcg_kmers_unitigs(km.t, min_cnt, None, 0, None, None, None, None, 0, n) == 1
+        sms.append(float(km.L.bfcg_kmers_last_ms(km.t)))
+    print("unitigs, the sizing call (listing of the ends, counting walks, the cycles' pass and walks, scans), 3 runs (ms): %s -> %d unitigs, %d bases" % (f(sms), n[0], n[1]))
+    ums, wall = [], []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        seq_u, off_u, nk, cs, ends = km.unitigs(min_cnt)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ums.append(km.last_ms())
+    print("unitigs, the call that writes (the same and the fill walks), 3 runs (ms): %s; wall of sizing + writing call with the copies: %s" % (f(ums), " ".join("%.1f" % v for v in wall)))
+    assert int(nk.sum()) == nodes
+    lens = np.sort(np.diff(off_u).astype(np.int64))[::-1]
+    n50 = int(lens[np.searchsorted(np.cumsum(lens), (int(lens.sum()) + 1) // 2)])
+    print("%d unitigs over %d nodes: %d cycles, longest %d k-mers, N50 %d bases; ends with code 1 / 2 / 3 / 6: %s"
+          % (len(nk), nodes, int((ends >> 6).sum()), int(nk.max()), n50, " / ".join(str(int(((ends & 7) == c).sum() + ((ends >> 3 & 7) == c).sum())) for c in (1, 2, 3, 6))))
+    best = min(ums)
+    print("unitigs best: %.3f ms = %.1f censuses (%.3f ms) = %.2f ns per node; fill = %.3f ms of it" % (best, best / min(cms), min(cms), best * 1e6 / nodes, best - min(sms)))
+    t0 = time.perf_counter()
+    t = g.export_table()
+    t1 = time.perf_counter()
+    print("export: %.1f ms" % ((t1 - t0) * 1e3), flush=True)
+    h = t.unitigs(min_cnt)
+    t2 = time.perf_counter()
+    print("export + host bfcg_unitigs_host, one thread: %.1f ms + %.1f ms = %.1f ms (%.0fx the kernels, %.0fx the two calls' wall)"
+          % ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t2 - t0) * 1e3, (t2 - t0) * 1e3 / best, (t2 - t0) * 1e3 / min(wall)), flush=True)
+    assert bfc_amd.unitig_rows(*h) == bfc_amd.unitig_rows(seq_u, off_u, nk, cs, ends)
+    print("the host's sorted unitigs equal the device's")
+    t.close()
+
+
+if UNITIGS:
+    unitig_rates()
+    km.close()
+    g.close()
+    sys.exit(0)
 
 if GRAPH:
     graph_rates()
