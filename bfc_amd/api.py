@@ -98,6 +98,8 @@ GRAPH_MASKS = {
     "all": (1 << 25) - 1,
 }
 
+CLIP_ISLANDS = 1  # BFCG_CLIP_ISLANDS
+
 _POP4 = np.array([bin(i).count("1") for i in range(16)], dtype=np.int64)
 
 
@@ -135,6 +137,15 @@ def _unitigs(L, fn, obj, min_cnt):
     if rc == 1 and fn(obj, int(min_cnt), seq.ctypes.data, len(seq), off.ctypes.data, nk.ctypes.data, cs.ctypes.data, ends.ctypes.data, len(nk), n) != 0:
         raise BfcGpuError(L.bfcg_last_error().decode() or "the table changed between the sizing call and the call that writes")
     return seq, off, nk, cs, ends
+
+
+def _clip(L, fn, obj, k, min_cnt, max_tip, max_mean, islands, max_rounds):
+    """(pointer to the new table, stats u64 (rounds, 3)) of bfcg_kmers_clip / bfcg_clip_host on `obj`; max_tip None = 2 k"""
+    stats, n = np.zeros((max(0, min(int(max_rounds), 64)), 3), dtype=np.uint64), C.c_int(0)
+    p = fn(obj, int(min_cnt), 2 * k if max_tip is None else int(max_tip), int(max_mean), CLIP_ISLANDS if islands else 0, int(max_rounds), stats.ctypes.data, C.byref(n))
+    if not p:
+        raise BfcGpuError(L.bfcg_last_error().decode())
+    return p, stats[:n.value].copy()
 
 
 def unitig_rows(seq, off, n_kmers, cnt_sum, ends):
@@ -247,6 +258,11 @@ class HostTable:
     def unitigs(self, min_cnt=1):
         """(seq u8, off u64 (n + 1), n_kmers u32, cnt_sum u64, ends u8): GpuKmers.unitigs's host twin (bfcg_unitigs_host)."""
         return _unitigs(self.L, self.L.bfcg_unitigs_host, self.ptr, min_cnt)
+
+    def clip(self, min_cnt=1, max_tip=None, max_mean=255, islands=False, max_rounds=8):
+        """(HostTable, stats u64 (rounds, 3)): GpuKmers.clip's host twin (bfcg_clip_host)."""
+        p, stats = _clip(self.L, self.L.bfcg_clip_host, self.ptr, self.k, min_cnt, max_tip, max_mean, islands, max_rounds)
+        return HostTable(p), stats
 
     def insert(self, y0, y1, is_high, forced=1):
         return self.L.bfc_ch_insert(self.ptr, (C.c_uint64 * 2)(y0, y1), int(is_high), forced)
@@ -855,7 +871,7 @@ class GpuKmers:
 
     @classmethod
     def _adopt(cls, t, keep):
-        """A GpuKmers around a bfcg_kmers_t the library made (a union); `keep` is what must outlive it."""
+        """A GpuKmers around a bfcg_kmers_t the library made (a union, a clipped table); `keep` is what must outlive it."""
         self = cls.__new__(cls)
         self.L, self._keep, self.t = _lib.load(), keep, t
         info = (C.c_int * 3)()
@@ -1014,10 +1030,20 @@ class GpuKmers:
         self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
         return out
 
+    def clip(self, min_cnt=1, max_tip=None, max_mean=255, islands=False, max_rounds=8):
+        """The graph at min_cnt cleaned (odd k <= 37; include/bfc_gpu.h defines tip, island and round): (a new GpuKmers that owns its
+        table, stats u64 (rounds, 3)).  A round removes every unitig of at most max_tip k-mers (None: 2 k) and a mean count of at most
+        max_mean (255: any) that has one dead end and one attached end -- with `islands` also those with two dead ends -- and leaves
+        the nodes that survive; rounds repeat until one removes nothing or max_rounds have run.  stats has a row per round that removed
+        something: unitigs removed, k-mers removed, keys left.  max_rounds = 0 only drops the k-mers with a count below min_cnt.  This
+        table is not written.  The result's last_ms() is the time of all the call's kernels."""
+        p, stats = _clip(self.L, self.L.bfcg_kmers_clip, self.t, self.k, min_cnt, max_tip, max_mean, islands, max_rounds)
+        return GpuKmers._adopt(p, None), stats
+
     def last_ms(self):
         """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces,
         read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces, neighbors() / list_graph() / extend() all their pieces, graph_census() one pass, unitigs() the call that writes; of a union() result,
-        its size passes and fill."""
+        its size passes and fill; of a clip() result, every kernel of the call."""
         return self._ms
 
 

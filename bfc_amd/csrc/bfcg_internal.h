@@ -1,4 +1,4 @@
-// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_mg.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip, bfcg_graph.hip, bfcg_unitigs.hip):
+// bfcg_internal.h -- shared between the kernels (bfcg_kernels.hip, ...) and the host files (bfcg_ctx.hip, bfcg_query.hip, bfcg_mg.hip, bfcg_ec.hip, bfcg_kmers.hip, bfcg_lookup.hip, bfcg_readstats.hip, bfcg_graph.hip, bfcg_unitigs.hip, bfcg_clip.hip):
 // kernel parameters and launchers, the one error channel, the resident registry, what the satellites and the group layer borrow from a context
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,9 +50,9 @@ struct bfcg_kmers {
 	unsigned long long *d_joint;        // 256 x 256 bins of a joint spectrum and the two counters of a union (bfcg_tabcmp.hip; allocated by the first call)
 	uint8_t *d_gout; uint64_t gout_cap; // a graph call's answers: eight values per k-mer of bfcg_kmers_neighbors, the paths of bfcg_kmers_extend (bfcg_graph.hip; grown on demand, in bytes)
 	int32_t *d_gls; uint64_t gls_cap;   // length and stop code per seed of bfcg_kmers_extend (bfcg_graph.hip; grown on demand, in bytes)
-	void *d_ut[BFCG_UT_NBUF]; uint64_t ut_bytes[BFCG_UT_NBUF]; // bfcg_kmers_unitigs's buffers, named in bfcg_unitigs.hip (grown on demand, in bytes)
-	uint64_t ut_cap;                    // starts a walk kernel of bfcg_kmers_unitigs takes per launch (BFCG_UNITIG_CAP at creation)
-	uint64_t n_keys; int has_keys;     // the keys of a table this object built and owns (bfcg_kmers_union counts them on the device)
+	void *d_ut[BFCG_UT_NBUF]; uint64_t ut_bytes[BFCG_UT_NBUF]; // bfcg_kmers_unitigs's and bfcg_kmers_clip's buffers, named in bfcg_glink.h (grown on demand, in bytes)
+	uint64_t ut_cap;                    // starts a walk kernel of bfcg_kmers_unitigs / bfcg_kmers_clip takes per launch (BFCG_UNITIG_CAP at creation)
+	uint64_t n_keys; int has_keys;     // the keys of a table this object built and owns (bfcg_kmers_union and bfcg_kmers_clip count them on the device)
 	float last_ms;
 };
 

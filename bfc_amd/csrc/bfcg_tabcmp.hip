@@ -12,7 +12,7 @@
 //                 a thousand workgroups flushing into those with atomics took longer than the walk (profiles/kmers_rate.md)
 //   k_tab_list    bfcg_klist.h with VsOther: the probe of B is part of the predicate of both passes, its answer the third column
 //   k_tab_union   a lane per pair of source slots, inserted into the output's region from home (v >> 14) & cmask_U by table_upsert's
-//                 protocol (bfcg_kernels.hip) written on (sub, key); the output's geometry is fixed from the inputs' sub-table sizes
+//                 protocol (bfcg_kernels.hip) written on (sub, key): union_upsert, bfcg_upsert.h; the output's geometry is fixed from the inputs' sub-table sizes
 //                 before the launch, so a region cannot overflow and there is no retry
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +22,7 @@
 #include "bfcg_internal.h"
 #include "bfc_host.h"
 #include "bfcg_klist.h"
+#include "bfcg_upsert.h"
 
 namespace {
 
@@ -114,34 +115,6 @@ struct VsOther {
 };
 
 // ---- k_tab_union ------------------------------------------------------------------------------------------------------------------
-// table_upsert (bfcg_kernels.hip) on (sub, key), the increment a whole slot: 1 key created, 0 counts added (saturating, order
-// independent), 2 region full -- which the geometry rules out; the host checks the counter all the same
-__device__ __forceinline__ uint32_t union_upsert(unsigned long long *__restrict__ tab, int cshift, uint64_t sub, unsigned long long v)
-{
-	const uint64_t cmask = (1ULL << cshift) - 1;
-	unsigned long long *reg = tab + (sub << cshift);
-	uint64_t pos = (v >> 14) & cmask;
-	const uint32_t c = (uint32_t)(v & 0xff), h = (uint32_t)(v >> 8 & 0x3f);
-	for (uint64_t probe = 0; probe <= cmask; ++probe, pos = (pos + 1) & cmask) {
-		unsigned long long cur = __hip_atomic_load(&reg[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (cur == 0) {
-			cur = atomicCAS(&reg[pos], 0ULL, v);
-			if (cur == 0) return 1;
-		}
-		if ((cur >> 14) == (v >> 14)) {
-			for (;;) {
-				const uint32_t nc = (uint32_t)(cur & 0xff) + c, nh = (uint32_t)(cur >> 8 & 0x3f) + h;
-				const unsigned long long nv = (cur & ~0x3fffULL) | (nc < 255 ? nc : 255) | ((uint64_t)(nh < 63 ? nh : 63) << 8);
-				if (nv == cur) return 0;
-				const unsigned long long old = atomicCAS(&reg[pos], cur, nv);
-				if (old == cur) return 0;
-				cur = old;
-			}
-		}
-	}
-	return 2;
-}
-
 __global__ __launch_bounds__(BT) void k_tab_union(const ulonglong2 *__restrict__ src, uint64_t n_pairs, int cshift_src, unsigned long long *__restrict__ dst,
                                                   int cshift_dst, unsigned long long *__restrict__ ctr)
 {

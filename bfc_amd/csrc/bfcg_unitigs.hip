@@ -1,8 +1,8 @@
 // bfcg_unitigs.hip -- the compacted de Bruijn graph of the count table where it lies in HBM: every maximal non-branching path (unitig)
 // exactly once, as bases.  include/bfc_gpu.h defines nodes, link(x), paths, cycles and which spelling is emitted; DESIGN.md section 6d.
 // The k-mer in registers and the probes are bfcg_gprobe.h's, the compaction of the path ends is bfcg_klist.h's.
-//   link_rule        the rule that joins two nodes, written once for the kernels and bfcg_unitigs_host
-//   k_tab_list       bfcg_klist.h with EndPred: a node is kept if one of its sides is open; the two stop codes are the third column
+//   link_rule        (bfcg_glink.h) the rule that joins two nodes, written once for the kernels and bfcg_unitigs_host
+//   k_tab_list       bfcg_klist.h with EndPred (bfcg_glink.h): a node is kept if one of its sides is open; the two stop codes are the third column
 //   k_ut_path_count  one lane per (path end, side): an open side is a start; the lane walks to the far end, counts k-mers and counts,
 //                    marks every node it passes in a bitmap of one bit per slot (a plain vector atomicOr) and decides whether its end
 //                    emits (its first k-mer is smaller as text than the reverse complement of the far end's)
@@ -24,80 +24,17 @@
 #include "kmer_dev.h"
 #include "bfcg_klist.h"
 #include "bfcg_gprobe.h"
+#include "bfcg_glink.h"
 
 namespace {
 
-enum { UT_BT = 64 /* a lane walks a start: see above */, UT_CAP = 1 << 22, UT_GRID_MAX = 2048 };
+enum { UT_CAP = 1 << 22, UT_GRID_MAX = 2048 }; // UT_BT, the buffers B_*, link_rule, EndPred, set_mark: bfcg_glink.h
 enum { STOP_CYCLE = 64 };
-// the object's buffers (bfcg_kmers.d_ut): the marks, the cycles' nodes, counters; per set of starts (paths at +0, cycles at +SET) a
-// record, the winner flag, the length in bases and their scans; the call's five outputs
-enum { B_MARK, B_CAND, B_CTR, B_REC, B_WIN, B_LEN, B_UIDX, B_BOFF, SET = 5, B_SEQ = B_REC + 2 * SET, B_OFF, B_NK, B_SUM, B_ENDS, B_N };
-static_assert(B_N <= BFCG_UT_NBUF, "bfcg_kmers.d_ut is too short");
 enum { CTR_CAND = 0, CTR_ERR = 1, CTR_N = 2 };
 
 struct Start { uint64_t a, b, sum; uint32_t nk, ends; }; // a winner: the planes of its first oriented k-mer, the sum of the counts, the k-mers, the ends byte
 
-// ---- oriented k-mers as planes, for the device and the host ----------------------------------------------------------------------------
-__host__ __device__ __forceinline__ void rc_planes(int k, uint64_t a, uint64_t b, uint64_t &ra, uint64_t &rb) // a, b hold nothing at and above bit k
-{
-	ra = __builtin_bitreverse64(~a) >> (64 - k); rb = __builtin_bitreverse64(~b) >> (64 - k);
-}
-// x < y as text, A < C < G < T from the 5' end (bit k - 1 of the planes; the high plane is the high code bit)
-__host__ __device__ __forceinline__ bool text_less(uint64_t xa, uint64_t xb, uint64_t ya, uint64_t yb)
-{
-	const uint64_t d = (xa ^ ya) | (xb ^ yb);
-	if (d == 0) return false;
-	const int h = 63 - __builtin_clzll(d);
-	return ((xb >> h & 1) << 1 | (xa >> h & 1)) < ((yb >> h & 1) << 1 | (ya >> h & 1));
-}
-__host__ __device__ __forceinline__ void succ_planes(int k, uint64_t a, uint64_t b, int c, uint64_t &ya, uint64_t &yb)
-{
-	const uint64_t m = kdec::mask(k);
-	ya = (a << 1 | (uint64_t)(c & 1)) & m; yb = (b << 1 | (uint64_t)(c >> 1)) & m;
-}
 __host__ __device__ __forceinline__ uint8_t base_at(uint64_t a, uint64_t b, int l) { return (uint8_t)"ACGT"[(b >> l & 1) << 1 | (a >> l & 1)]; }
-
-// link(x) of include/bfc_gpu.h for the oriented k-mer (a, b), masked: 0 and y = (ya, yb), or the stop code 1, 2, 3, 6.  `tab` answers
-// present4(a, b, pred, min_cnt) as for extend_rule (bfcg_graph.hip)
-template <class T>
-__host__ __device__ __forceinline__ int link_rule(const T &tab, int k, uint64_t a, uint64_t b, int min_cnt, uint64_t &ya, uint64_t &yb)
-{
-	const int o = tab.present4(a, b, 0, min_cnt);
-	if (o == 0) return 1;
-	if (o & (o - 1)) return 2;
-	succ_planes(k, a, b, __builtin_ctz(o), ya, yb);
-	const int i = tab.present4(ya, yb, 1, min_cnt); // x is one of them
-	if (i & (i - 1)) return 3;
-	uint64_t ra, rb;
-	rc_planes(k, a, b, ra, rb);
-	if ((ya == a && yb == b) || (ya == ra && yb == rb)) return 6;
-	return 0;
-}
-// the next base of a walk that link_rule allowed: the single present successor (0 if the table changed meanwhile)
-template <class T> __host__ __device__ __forceinline__ int only_succ(const T &tab, uint64_t a, uint64_t b, int min_cnt)
-{
-	const int o = tab.present4(a, b, 0, min_cnt);
-	return o ? __builtin_ctz(o) : 0;
-}
-
-// ---- the listing's predicate: a node with an open side -----------------------------------------------------------------------------------
-template <typename W> struct EndPred {
-	static constexpr bool probes = true;
-	using col_t = uint8_t;
-	TabRef T; int min_cnt;
-	__device__ __forceinline__ bool keep(uint32_t sub, uint64_t slot, uint8_t &o) const // o = left stop | right stop << 3 of the stored strand
-	{
-		DevGraph<W> g; g.T = T;
-		uint64_t a, b, ra, rb, ya, yb;
-		kdec::decode(T.k, T.l_pre, sub, slot, a, b);
-		rc_planes(T.k, a, b, ra, rb);
-		const int right = link_rule(g, T.k, a, b, min_cnt, ya, yb), left = link_rule(g, T.k, ra, rb, min_cnt, ya, yb);
-		o = (uint8_t)(left | right << 3);
-		return o != 0;
-	}
-};
-
-__device__ __forceinline__ void set_mark(uint32_t *mark, uint64_t slot) { atomicOr(&mark[slot >> 5], 1u << (slot & 31)); }
 
 // ---- the counting walks ----------------------------------------------------------------------------------------------------------------
 // start i in [first, end): side i & 1 of listed node i >> 1 (0: the stored strand x, its left side; 1: rc(x), whose left side is x's right)
@@ -200,20 +137,12 @@ __global__ __launch_bounds__(UT_BT) void k_ut_fill(TabRef T, int min_cnt, const 
 	}
 }
 
-int check_unitig_k(const char *who, int k)
-{
-	if (k > (int)kdec::MAX_K) return check_decodable(k);
-	if (k % 2 == 0) return bfcg::fail("%s: k=%d is even: the strand rule leaves some k-mers undecided, a k-mer and its reverse complement can be two keys, and there is no strand-free graph to compact (odd k <= %d only)", who, k, (int)kdec::MAX_K);
-	return 0;
-}
 int check_unitig_bufs(const char *who, const uint8_t *seq, uint64_t seq_cap, const void *off, const void *n_kmers, const void *cnt_sum, const void *ends, uint64_t n_cap)
 {
 	if ((seq_cap && !seq) || (n_cap && (!off || !n_kmers || !cnt_sum || !ends))) return bfcg::fail("%s needs output buffers for seq_cap=%llu, n_cap=%llu", who, (unsigned long long)seq_cap, (unsigned long long)n_cap);
 	return 0;
 }
 
-template <typename T> T *ut_buf(bfcg_kmers_t *t, int which) { return (T *)t->d_ut[which]; }
-int ut_grow(bfcg_kmers_t *t, int which, uint64_t bytes, const char *what) { return bfcg::grow(t->d_ut[which], t->ut_bytes[which], bytes, what); }
 
 // the records, flags, lengths and scans of a set of n starts (flags and lengths zeroed: a start that does not emit writes nothing)
 int set_alloc(bfcg_kmers_t *t, int set, uint64_t n, uint64_t &n_pad)
@@ -249,15 +178,6 @@ template <typename W> int set_fill(bfcg_kmers_t *t, const TabRef &T, int min_cnt
 		                   ut_buf<uint8_t>(t, B_SEQ), ut_buf<unsigned long long>(t, B_OFF), ut_buf<uint32_t>(t, B_NK), ut_buf<unsigned long long>(t, B_SUM), ut_buf<uint8_t>(t, B_ENDS));
 	}
 	BFCG_CK(hipGetLastError());
-	return 0;
-}
-// the time between the object's two events added to *ms; the stream is idle afterwards
-int ut_lap(bfcg_kmers_t *t, float *ms)
-{
-	float d = 0;
-	BFCG_CK(hipStreamSynchronize(t->st));
-	BFCG_CK(hipEventElapsedTime(&d, t->e0, t->e1));
-	*ms += d;
 	return 0;
 }
 
@@ -372,8 +292,6 @@ extern "C" int bfcg_kmers_unitigs(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, ui
 
 namespace {
 
-struct Planes { uint64_t a, b; bool operator==(const Planes &o) const { return a == o.a && b == o.b; } };
-struct PlanesHash { size_t operator()(const Planes &p) const { return (size_t)kdec::mix(p.a ^ kdec::mix(p.b, ~0ULL), ~0ULL); } };
 
 struct HostUnitigs {
 	HostGraph g; int min_cnt;

@@ -1,12 +1,19 @@
 """A `bfc -d` dump read as a de Bruijn graph on the GPU: how many k-mers are dead ends, how many branch, and what lies around a k-mer.
 
-    python -m bfc_amd.kmergraph [-m INT] [-t|-b] [-u] [-x FILE] [-l INT] table.dump
+    python -m bfc_amd.kmergraph [-m INT] [-c INT [-a INT] [-i] [-r INT] [-o FILE]] [-t|-b] [-u] [-x FILE] [-l INT] table.dump
 
 The dump is restored with bfc_ch_restore and uploaded.  A k-mer is PRESENT if the table holds it with count >= INT (-m, default 1); a NODE
 is a k-mer of the table with such a count, on the strand the table stores (the one hash2cnt prints); its out-degree o is the number of
 bases whose successor is present, its in-degree i that of the predecessors (include/bfc_gpu.h states all of it).  The reference has no
 such tool, so the output format is this project's.  Standard output, in this order:
 
+    clip<TAB>round<TAB>unitigs<TAB>kmers<TAB>keys_left
+                          under -c INT, first: the graph is cleaned on the GPU (bfcg_kmers_clip; odd k <= 37) and EVERY line below then
+                          describes the cleaned table.  A round removes the tips -- unitigs of at most INT k-mers (0: 2 k) with one dead
+                          end and one end attached to a branch -- whose mean count is at most -a INT (default 255: any), with -i also the
+                          islands (both ends dead); it leaves the k-mers with a count of at least -m that survive.  Rounds repeat until
+                          one removes nothing or -r INT (default 8) have run.  One line per round that removed something, rounds from 1:
+                          the unitigs and k-mers it removed and the keys it left.  -o FILE writes the cleaned table as a dump
     deg<TAB>o<TAB>n0<TAB>n1<TAB>n2<TAB>n3<TAB>n4
                           five lines, o = 0..4: the nodes with out-degree o and in-degree 0..4 (bfcg_kmers_graph_census; k <= 37).  A
                           node stored as its reverse complement has the two degrees swapped; the five lines below count classes that are
@@ -41,6 +48,11 @@ import numpy as np
 USAGE = """Usage: kmergraph [options] <table.dump>
 Options:
   -m INT   a k-mer is present with occ >= INT [1]
+  -c INT   clip tips of at most INT k-mers first (0: 2k); all output describes the cleaned table (odd k <= 37)
+  -a INT   clip only unitigs whose mean count is at most INT [255]
+  -i       clip islands too
+  -r INT   at most INT rounds of clipping [8]
+  -o FILE  write the cleaned table as a dump (with -c)
   -t       list the tips
   -b       list the branching k-mers
   -u       list the unitigs of the compacted graph (odd k <= 37)
@@ -100,12 +112,12 @@ def _unitig_lines(rows, out):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     try:
-        opts, args = getopt.getopt(argv, "tbum:x:l:")
+        opts, args = getopt.getopt(argv, "tbuim:x:l:c:a:r:o:")
     except getopt.GetoptError:
         opts, args = [], []
     o = dict(opts)
     modes = [f for f in ("-t", "-b") if f in o]
-    if len(args) != 1 or len(modes) > 1:
+    if len(args) != 1 or len(modes) > 1 or ("-c" not in o and any(f in o for f in ("-a", "-i", "-r", "-o"))):
         sys.stderr.write(USAGE)
         return 1
     from . import api
@@ -117,6 +129,17 @@ def main(argv=None):
     km = api.GpuKmers(t)
     rc = 0
     try:
+        if "-c" in o:   # (refused, like -u, before any output)
+            clean, stats = km.clip(min_cnt, _atoi(o["-c"]) or None, _atoi(o.get("-a", "255")), "-i" in o, _atoi(o.get("-r", "8")))
+            km.close()
+            km = clean
+            out.write(b"".join(b"clip\t%d\t%d\t%d\t%d\n" % (i + 1, r[0], r[1], r[2]) for i, r in enumerate(stats)))
+            if "-o" in o:
+                h = km.to_host()
+                failed = h.dump(o["-o"]) != 0
+                h.close()
+                if failed:
+                    raise api.BfcGpuError("cannot write %s" % o["-o"])
         rows = api.unitig_rows(*km.unitigs(min_cnt)) if "-u" in o else None   # (an even k or k > 37 is refused here, before any output)
         if t.k <= 37 or "-x" not in o:   # (k > 37 with -x alone: the walks need no decode)
             deg = km.graph_census(min_cnt)

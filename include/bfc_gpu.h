@@ -488,7 +488,38 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *                         lane's sequential probes: expected work is near-linear on ordinary sequence (a cycle node gives up after about
  *                         ln n steps on average), but one unitig of millions of k-mers -- a path, or a cycle's leader on its lap -- runs
  *                         at the pace of one lane, the caveat bfcg_kmers_read_stats makes for a megabase contig
+ * The graph cleaned (bfcg_clip.hip): tips and islands clipped into a new table, on either form of the object.  The domain is that of
+ * bfcg_kmers_unitigs -- odd k <= 37, min_cnt in [1, 255] --, and nodes, link(x), unitigs and stop codes are exactly those defined above.
+ *   DEAD, ATTACHED  stop codes 1 and 6 are DEAD (nothing lies beyond but the node itself), 2 and 3 are ATTACHED
+ *   CLIPPABLE   a unitig of the graph at min_cnt is clippable at (max_tip, max_mean) if it is a path, not a cycle; n_kmers <= max_tip;
+ *               and cnt_sum <= max_mean * n_kmers (integer arithmetic; max_mean = 255 switches this rule off)
+ *   TIP, ISLAND a clippable unitig is a tip if one end is DEAD and the other ATTACHED, an island if both ends are DEAD.  A unitig with
+ *               both ends ATTACHED is never touched: bubbles stay
+ *   a ROUND     decides on its input graph only and removes all k-mers of all tips at once; with BFCG_CLIP_ISLANDS in flags those of the
+ *               islands too.  Unitigs are node-disjoint, so the result does not depend on any order.  Its output is a table of the
+ *               surviving NODES: slots with count < min_cnt are dropped as well; key, count and high count of a survivor are unchanged.
+ *               Rounds repeat on the previous round's output until one removes nothing or max_rounds rounds have run.  max_rounds = 0
+ *               gives the table of the nodes at min_cnt and nothing else: a threshold filter
+ *   bfcg_kmers_clip       a new object that owns its table, as bfcg_kmers_union's does (its keys are known): the input's k and l_pre; its
+ *                         cshift follows the union's rule applied to the survivors, the smallest value >= 2 with 2^(l_pre + cshift) >=
+ *                         2 * keys and 2^cshift >= the largest per-sub-table survivor count; the order inside a sub-table is
+ *                         unspecified.  An empty result (every node removed) is a valid table with zero keys.  The input is never
+ *                         written: an attached input stays attached and unchanged.  *n_rounds = the rounds that ran and removed
+ *                         something; stats (may be NULL, else room for 3 * max_rounds words) gets three words per such round: unitigs
+ *                         removed, k-mers removed, keys left.  Refused before any launch with a message, the outputs untouched and the
+ *                         object usable: even k and k > 37 (the unitigs' messages), min_cnt outside [1, 255], max_tip outside
+ *                         [1, 65535], max_mean outside [1, 255], max_rounds outside [0, 64], unknown flag bits.  NULL on refusal or
+ *                         error; bfcg_kmers_last_ms(result) covers every kernel of the call.
+ *                         How, per round: the unitigs' listing pass yields the nodes with an open side; one lane per DEAD side walks
+ *                         away from the dead end for at most max_tip k-mers, summing counts -- a lane that has not met an open side by
+ *                         then stops, so no lane walks further than max_tip steps whatever the graph holds (the one-lane-per-long-unitig
+ *                         caveat of bfcg_kmers_unitigs does not apply); of an island's two lanes the one the unitigs' spelling rule picks
+ *                         goes on; a lane that removes walks the same steps again and sets one bit per slot in a bitmap; one streaming
+ *                         pass counts the survivors per sub-table, a second upserts them into the new table.  Intermediate tables are
+ *                         freed as soon as the next one stands.  Device memory: one bit per slot, the listing, and the tables of two rounds
  * Their host twins and the text forms use no GPU:
+ *   bfcg_clip_host        bfcg_kmers_clip -- result, stats, refusals -- by the same rule (one piece of code for both) on
+ *                         bfcg_kmer_occ_host, over bfc_ch_export_sorted's slots, into a table made at the same cshift rule
  *   bfcg_kmer_from_str    the inverse of bfcg_kmer_2str; -1 unless s has exactly k bytes of ACGTacgt
  *   bfcg_kmer_occ_host    bfc_ch_kmer_occ on listing-style planes of either strand (the four planes of bfc_kmer_t built from the two)
  *   bfcg_kmers_occ_host   the same for n k-mers
@@ -555,6 +586,10 @@ int   bfcg_kmers_unitigs(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t se
                          uint64_t n_cap, uint64_t n[2]);
 int   bfcg_unitigs_host(const bfc_ch_t *ch, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
                         uint64_t n_cap, uint64_t n[2]);
+enum { BFCG_CLIP_ISLANDS = 1 };
+bfcg_kmers_t *bfcg_kmers_clip(bfcg_kmers_t *t, int min_cnt, int max_tip, int max_mean, int flags, int max_rounds,
+                              uint64_t *stats /* 3 per round: unitigs removed, k-mers removed, keys left */, int *n_rounds);
+bfc_ch_t     *bfcg_clip_host(const bfc_ch_t *ch, int min_cnt, int max_tip, int max_mean, int flags, int max_rounds, uint64_t *stats, int *n_rounds);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);

@@ -2,7 +2,7 @@
 from the attached context, kernels only, against the path it replaces for the spectrum -- bfcg_export_table followed by the host's
 bfc_ch_hist.  Not the headline bench; numbers quoted in profiles/kmers_rate.md.
 
-    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph | --unitigs] [k] [bf_shift] [genome size] [coverage]
+    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph | --unitigs | --clip] [k] [bf_shift] [genome size] [coverage]
 
 --lookup measures the other direction instead (bfcg_lookup.hip): lookup() of every listed k-mer in shuffled order, and profile() over a
 prefix of the reads that built the table, each next to the host's loop over bfc_ch_kmer_occ on the same input (bfcg_kmers_occ_host,
@@ -18,6 +18,9 @@ census next to the route without it -- export the table, bfcg_graph_census_host 
 --unitigs measures the compacted graph (bfcg_unitigs.hip): unitigs() -- the sizing call alone (listing of the path ends, counting walks,
 the pass for the cycles' nodes, scans) and the call that also fills -- kernels only, next to a census of the same table and to the route
 without it: export the table, bfcg_unitigs_host on the CPU (one thread).  The per-kernel split is a kernel trace of this script's run.
+--clip measures the graph cleaning (bfcg_clip.hip): clip() at the default parameters -- tips of at most 2 k k-mers, eight rounds at most --
+and with islands, all the call's kernels, in k-mers of the input per second, beside unitigs() on the same table in the same run (the only
+yardstick there is: nobody measured this before), and the unitigs of the cleaned table beside those of the input.
 """
 import os
 import sys
@@ -45,6 +48,9 @@ if GRAPH:
 UNITIGS = "--unitigs" in sys.argv
 if UNITIGS:
     sys.argv.remove("--unitigs")
+CLIP = "--clip" in sys.argv
+if CLIP:
+    sys.argv.remove("--clip")
 arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
 k, b, G, cov = arg(1, 31), arg(2, 33), arg(3, 4_600_000), arg(4, 100)
 rs = gen.ReadSet(seed=2, G=G, cov=cov)
@@ -312,6 +318,45 @@ def unitig_rates(min_cnt=1):
     print("the host's sorted unitigs equal the device's")
     t.close()
 
+
+def clip_rates(min_cnt=1):
+    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
+    print("build %s" % bfc_amd._lib.build_id())
+
+    def shape(t):
+        seq_u, off_u, nk, cs, ends = t.unitigs(min_cnt)
+        lens = np.sort(np.diff(off_u).astype(np.int64))[::-1]
+        n50 = int(lens[np.searchsorted(np.cumsum(lens), (int(lens.sum()) + 1) // 2)]) if len(lens) else 0
+        return "%d unitigs over %d nodes, N50 %d bases" % (len(nk), int(nk.sum()), n50), int(nk.sum()), t.last_ms()
+
+    ums = []
+    for rep in range(3):
+        text, nodes, ms = shape(km)
+        ums.append(ms)
+    print("unitigs (min_cnt %d), the call that writes, 3 runs (ms): %s; %s" % (min_cnt, f(ums), text))
+    for islands in (False, True):
+        cms, wall = [], []
+        for rep in range(3):
+            t0 = time.perf_counter()
+            res, stats = km.clip(min_cnt=min_cnt, islands=islands)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            cms.append(res.last_ms())
+            if rep < 2:
+                res.close()
+        best = min(cms)
+        print("clip (min_cnt %d, max_tip %d, max_mean 255, islands %d, at most 8 rounds), all kernels, 3 runs (ms): %s; wall: %s"
+              % (min_cnt, 2 * km.k, islands, f(cms), " ".join("%.1f" % v for v in wall)))
+        print("clip rounds (unitigs removed, k-mers removed, keys left): %s" % " ".join("(%d, %d, %d)" % tuple(int(v) for v in r) for r in stats))
+        print("clip best: %.3f ms = %.2f G k-mers of the input per second = %.2f x unitigs (%.3f ms); result 2^%d sub-tables of 2^%d slots; %s"
+              % (best, nodes / best / 1e6, best / min(ums), min(ums), res.l_pre, res.cshift, shape(res)[0]))
+        res.close()
+
+
+if CLIP:
+    clip_rates()
+    km.close()
+    g.close()
+    sys.exit(0)
 
 if UNITIGS:
     unitig_rates()
