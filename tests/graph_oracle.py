@@ -137,6 +137,18 @@ def census_of_nb(nb):
     return deg
 
 
+def cells_of_nb(nb):
+    """the degree cell 5 * o + i of every entry of an array of neighbour bits"""
+    nb = np.asarray(nb, dtype=np.uint8)
+    pop = np.array([bin(i).count("1") for i in range(16)], dtype=np.int64)
+    return 5 * pop[nb & 15] + pop[nb >> 4]
+
+
+def in_mask(nb, cell_mask):
+    """which entries of an array of neighbour bits have their degree cell set in cell_mask (list_graph's predicate)"""
+    return ((int(cell_mask) >> cells_of_nb(nb)) & 1).astype(bool)
+
+
 def paths(bases, length):
     """the rows of extend()'s bases as bytes, each checked to be zero beyond its length"""
     out = []

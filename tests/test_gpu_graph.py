@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from graph_oracle import census_of_nb, fixture, paths, planes_of_strs, revcomp
+from graph_oracle import census_of_nb, fixture, in_mask, paths, planes_of_strs, revcomp
 from test_gpu_kmers import _count, _g1
 from test_gpu_tabcmp import FORMS
 from test_lookup_host import stream_kmers
@@ -60,11 +60,6 @@ def _host_nb(gpu_lib, which, k, form, min_cnt):
     sizes, slots = c.host.export_sorted()
     y, nb = c.host.graph_nb(min_cnt)
     return np.repeat(np.arange(len(sizes), dtype=np.uint64), sizes), y, (slots & U(0x3fff)).astype(np.uint16), nb
-
-
-def _cells(nb):
-    pop = np.array([bin(i).count("1") for i in range(16)], dtype=np.int64)
-    return 5 * pop[nb & 15] + pop[nb >> 4]
 
 
 def _rows(sub, y, ch, nb):
@@ -185,7 +180,7 @@ def test_list_graph_equals_host_twin(gpu_lib, which, k):
         node = (hch & 0xff) >= min_cnt
         for name in NAMED:
             mask = gpu_lib.GRAPH_MASKS[name]
-            keep = node & ((mask >> _cells(hnb)) & 1).astype(bool)
+            keep = node & in_mask(hnb, mask)
             y, cnt, high, nb = (c.att if name != "simple" else c.up).list_graph(min_cnt, mask)
             assert len(cnt) == int(keep.sum()) and (which == "g1" or name == "all" or 0 < len(cnt) < node.sum())
             want = _rows(sub[keep], hy[keep], hch[keep], hnb[keep])
