@@ -38,13 +38,16 @@ using namespace bfcg;
 // contended bit, competitors, look-ups, all by divergent probe loops on LDS compare-and-swaps -- took 28 ps per k-mer for the launch into the
 // empty filter and 13 for the next against 6.7 once the filter is warm (profiles/round4_k_bloom.md, section 3).  A k-mer touches ONE 64-byte
 // block (bbf.c:27-31), so the reference's order only matters inside a block, and a region has 2^R of them with a handful of listed k-mers each:
-// the list is ordered by (block, file index) -- one LDS counter per block, a scan of 2^R counters, a scatter, ranks by comparing a block's few
-// indices -- and ONE LANE PER BLOCK walks its k-mers in file order doing literally what bfc_bf_insert does (bbf.c:33-44): test the four bits,
-// seen iff all are set, set them.  The lane owns the block: plain LDS reads, fire-and-forget ORs, no table, no probing, no retries, and the
-// result is the sequential one by construction.  A list entry is 12 bytes (file index, packed address + clear mask, record index, position in
-// block order); with no first-setter table beside it the list holds 2 879 entries where the protocol's held 2 021.
-#define B3_SEEN 0x40000000u /* COLD: list word: the walk found every bit of this k-mer set */
+// the list is ordered by (block, file index) IN PLACE -- one LDS counter per block, a scan of 2^R counters, the entries moved to their blocks
+// through registers, ranks by comparing a block's few indices where they lie side by side, the entries moved to their ranks -- and ONE LANE PER
+// BLOCK walks its k-mers in file order doing literally what bfc_bf_insert does (bbf.c:33-44): test the four bits, seen iff all are set, set them
+// (one returning OR per bit, as bbf.c:39-40 has it).  The lane owns the block: no table, no probing, no retries, no decision between two
+// k-mers' ORs, and the result is the sequential one by construction.  A list entry is 12 bytes (file index; packed address + clear mask, once
+// ordered three of the four bit positions; record index; once ordered the fourth position and the walk's verdict); with no first-setter table
+// beside it the list holds 2 879 entries where the protocol's held 2 021.  (profiles/bloom3_cold_order.md: the sub-steps' clocks, what was tried.)
+#define B3_SEEN16 0x8000u    /* COLD: the flag beside an ordered entry's fourth position (16-bit word) */
 #define B3_COLD_NR 8       /* COLD: list positions per thread in the rank pass (8 x 512 = 4096 >= the cold list's capacity) */
+#define B3_WALK_U 4        /* COLD: entries of a block whose ORs the walk issues back to back */
 template <int BT, int PF, bool COLD>
 __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, BloomArgs A)
 {
@@ -78,7 +81,7 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 	unsigned int *la = reinterpret_cast<unsigned int *>(sp); sp += (size_t)P.list_cap * 4;   // file-order index
 	unsigned int *lb = reinterpret_cast<unsigned int *>(sp); sp += (size_t)P.list_cap * 4;   // block | h1 << 8 | h2 << 17 | clear-bit mask << 26 (| B3_UND)
 	unsigned short *lc = reinterpret_cast<unsigned short *>(sp); sp += (size_t)P.list_cap * 2; // record index inside the region's slab
-	unsigned short *ord = reinterpret_cast<unsigned short *>(sp);                            // COLD: the list's entries in (block, file index) order
+	unsigned short *ord = reinterpret_cast<unsigned short *>(sp);                            // COLD, once the list is ordered: an entry's fourth bit position (| B3_SEEN16); lb then holds the other three
 	const uint32_t fs_mask = P.fs_cap - 1;
 	const uint32_t *recs = A.recs + (uint64_t)rs * 3;
 	unsigned int *g_region = reinterpret_cast<unsigned int *>(A.bloom) + (uint64_t)f * region_dw;
@@ -89,7 +92,11 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 #ifdef BFCG_MEASURE
 	const bool timing = BFCG_ABL(P, 64) && tid == 0;
 	long long tq[7] = {0, 0, 0, 0, 0, 0, 0};
+	long long tc[7] = {0, 0, 0, 0, 0, 0, 0}; // COLD, BFCG_ABLATE & 128: the ordering's sub-steps (scan, scatter, rank, reorder, walk, emit)
 	if (timing) tq[0] = clock64();
+#define B3_TC(i) do { if (timing) tc[i] = clock64(); } while (0)
+#else
+#define B3_TC(i) do { } while (0)
 #endif
 	// block (8 bits at R = 8) | h1 << 8 | h2 << 17 of a record (decode_fast3, packed)
 	auto addr3 = [&](uint32_t d0, uint32_t d1) -> uint32_t {
@@ -189,10 +196,11 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 	if (timing) tq[2] = clock64();
 #endif
 	const uint32_t ln = s_list_n;
-	const bool ovf_list = ln > P.list_cap || ln > (COLD ? (uint32_t)(B3_COLD_NR * BT) : 8191u) || n > 65535u; // (13-bit list index in a first-setter entry, 16-bit record index in the list; COLD: 16 positions per thread in the rank pass)
+	const bool ovf_list = ln > P.list_cap || ln > (COLD ? (uint32_t)(B3_COLD_NR * BT) : 8191u) || n > 65535u; // (13-bit list index in a first-setter entry, 16-bit record index in the list; COLD: B3_COLD_NR positions per thread in the ordering passes)
 	bool dirty = true;
 	if constexpr (COLD) {
 		if (!ovf_list) {
+			B3_TC(0);
 			// ---- block offsets: exclusive scan of the 2^R counters by the first wave (2^R <= 256: four blocks per lane)
 			if (tid < 64) {
 				const uint32_t per = (nblk + 63u) >> 6, b0 = (uint32_t)tid * per;
@@ -208,69 +216,132 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 				if (tid == 63) boff[nblk] = inc;
 			}
 			__syncthreads();
-			// ---- scatter: the list's entries grouped by block (any order inside a block)
-			for (uint32_t li = tid; li < ln; li += BT) ord[atomicAdd(&bcnt[lb[li] & 255u], 1u)] = (unsigned short)li;
+			B3_TC(1);
+			// ---- group the list by block IN PLACE (any order inside a block): every thread takes its up to B3_COLD_NR entries into registers and draws
+			// each one's place from its block's cursor; behind the barrier -- every entry is read before any is overwritten -- it writes them there.
+			// Block b's entries then are la / lb / lc[boff[b] .. boff[b + 1]): the passes below read them at addresses no loaded value decides.
+			uint32_t ex[B3_COLD_NR], ew[B3_COLD_NR], ep[B3_COLD_NR]; // file index; packed address + mask; place | record index << 16
+#pragma unroll
+			for (int t = 0; t < B3_COLD_NR; ++t) {
+				const uint32_t li = (uint32_t)tid + (uint32_t)t * BT;
+				ex[t] = 0; ew[t] = 0; ep[t] = 0;
+				if (li < ln) {
+					ex[t] = la[li]; ew[t] = lb[li];
+					ep[t] = ((uint32_t)lc[li] << 16) | __hip_atomic_fetch_add(&bcnt[ew[t] & 255u], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+				}
+			}
 			__syncthreads();
-			// ---- ranks: an entry's place among its block's entries = how many of them come earlier in the file (a block holds a handful).  Every
-			// position is read before any is rewritten: the new places wait in registers across the barrier.
-			uint32_t mv[B3_COLD_NR]; // place << 16 | entry, per position this thread owns (B3_COLD_NR x BT >= the cold list's capacity)
+#pragma unroll
+			for (int t = 0; t < B3_COLD_NR; ++t) {
+				if ((uint32_t)tid + (uint32_t)t * BT < ln) { const uint32_t p = ep[t] & 0xffffu; la[p] = ex[t]; lb[p] = ew[t]; lc[p] = (unsigned short)(ep[t] >> 16); }
+			}
+			__syncthreads();
+			B3_TC(2);
+			// ---- ranks: an entry's place in its block's file order = how many of the block's entries come earlier in the file.  A thread ranks
+			// the entries AT its positions of the grouped list: neighbouring lanes hold the same block or the next one, so a wave's loop is as long
+			// as the longest of the few blocks it covers and its lanes read the same few words (no bank conflicts).  The block's file indices lie
+			// side by side: four reads at a time, clamped to the block's last entry and masked out beyond it, at addresses no loaded value
+			// decides.  A block of hundreds of entries (one read repeated thousands of times) only makes the loop longer.
+			// The entry then moves to its place (again through registers and a barrier): the list itself is in (block, file index) order and needs
+			// no index beside it.  What moves is what the walk wants: the four bit positions, worked out here by every thread for its few entries
+			// and not by the one lane in four that walks -- three of them in the list word, the fourth in the 16-bit word beside it (ord).
+			uint32_t sx[B3_COLD_NR], sw[B3_COLD_NR], sq[B3_COLD_NR]; // file index; h1 | h2 << 9 | place << 18 (a place has 12 bits); record index
 #pragma unroll
 			for (int t = 0; t < B3_COLD_NR; ++t) {
 				const uint32_t pos = (uint32_t)tid + (uint32_t)t * BT;
-				mv[t] = 0;
+				sx[t] = 0; sw[t] = 0; sq[t] = 0;
 				if (pos < ln) {
-					const uint32_t li = ord[pos], x = la[li], bl = lb[li] & 255u, s0 = boff[bl], s1 = boff[bl + 1];
-					uint32_t r = 0;
-					for (uint32_t j = s0; j < s1; ++j) r += (uint32_t)(la[ord[j]] < x);
-					mv[t] = ((s0 + r) << 16) | li;
+					const uint32_t x = la[pos], w = lb[pos], bl = w & 255u, s0 = boff[bl], s1 = boff[bl + 1], last = s1 - 1u; // (s1 > s0: the entry itself is one of them)
+					uint32_t r = s0;
+					for (uint32_t j = s0; j < s1; j += 4) {
+						const uint32_t y0 = la[j], y1 = la[min(j + 1u, last)], y2 = la[min(j + 2u, last)], y3 = la[min(j + 3u, last)];
+						r += (uint32_t)(y0 < x) + (uint32_t)(j + 1u < s1 && y1 < x) + (uint32_t)(j + 2u < s1 && y2 < x) + (uint32_t)(j + 3u < s1 && y3 < x);
+					}
+					sx[t] = x; sw[t] = ((w >> 8) & 0x3ffffu) | (r << 18); sq[t] = lc[pos];
 				}
 			}
 			__syncthreads();
+			B3_TC(3);
 #pragma unroll
-			for (int t = 0; t < B3_COLD_NR; ++t) { const uint32_t pos = (uint32_t)tid + (uint32_t)t * BT; if (pos < ln) ord[mv[t] >> 16] = (unsigned short)mv[t]; }
+			for (int t = 0; t < B3_COLD_NR; ++t) {
+				if ((uint32_t)tid + (uint32_t)t * BT < ln) {
+					const uint32_t r = sw[t] >> 18;
+					const B3Pos b = b3_positions(sw[t] & 511u, (sw[t] >> 9) & 511u);
+					la[r] = sx[t]; lb[r] = b.b0 | (b.b1 << 9) | (b.b2 << 18); ord[r] = (unsigned short)b.b3; lc[r] = (unsigned short)sq[t];
+				}
+			}
 			__syncthreads();
+			B3_TC(4);
 			// ---- the walk: lane b takes block b's k-mers in file order -- bbf.c:33-44 as it stands: seen iff every bit is set, then set them
+			// Test and set are ONE returning OR per position, as the reference's loop has them (bbf.c:39-40), issued for B3_WALK_U entries back to
+			// back: the LDS takes a wave's operations in order, so entry j + 1 meets the bits entry j set without the lane waiting for entry j's
+			// answer -- nothing a lane decides lies between two entries' ORs (a slot beyond the block's end ORs nothing into the last entry's words).
+			// The next B3_WALK_U entries are on their way meanwhile.
 			if ((uint32_t)tid < nblk) {
-				const uint32_t bl = (uint32_t)tid, bl64 = bl << 6, s0 = boff[bl], s1 = boff[bl + 1];
-				uint32_t li_n = s0 < s1 ? ord[s0] : 0u, w_n = s0 < s1 ? lb[li_n] : 0u;
-				for (uint32_t j = s0; j < s1; ++j) {
-					const uint32_t li = li_n, w = w_n;
-					if (j + 1 < s1) { li_n = ord[j + 1]; w_n = lb[li_n]; } // (the next entry is on its way while this one is decided)
-					const B3Pos b = b3_positions((w >> 8) & 511u, (w >> 17) & 511u);
-					unsigned int *p0 = b3_wordp(region, bl64, b.b0), *p1 = b3_wordp(region, bl64, b.b1), *p2 = b3_wordp(region, bl64, b.b2), *p3 = b3_wordp(region, bl64, b.b3);
-					const uint32_t w0 = *p0, w1 = *p1, w2 = *p2, w3 = *p3;
-					const uint32_t clr = (b3_bit(w0, b.b0) | (b3_bit(w1, b.b1) << 1) | (b3_bit(w2, b.b2) << 2) | (b3_bit(w3, b.b3) << 3)) ^ 15u; // (bits set before the batch are still set)
-					if (clr == 0) lb[li] = w | B3_SEEN;
-					else { // (two positions may share a word: ORs, not stores; this lane's later reads follow them in order)
-						if (clr & 1u) __hip_atomic_fetch_or(p0, 1u << (b.b0 & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-						if (clr & 2u) __hip_atomic_fetch_or(p1, 1u << (b.b1 & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-						if (clr & 4u) __hip_atomic_fetch_or(p2, 1u << (b.b2 & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-						if (clr & 8u) __hip_atomic_fetch_or(p3, 1u << (b.b3 & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+				const uint32_t bl = (uint32_t)tid, bl64 = bl << 6, s0 = boff[bl], s1 = boff[bl + 1], last = s1 - 1u;
+				uint32_t pw_n[B3_WALK_U] = {0, 0, 0, 0}, p3_n[B3_WALK_U] = {0, 0, 0, 0};
+				if (s0 < s1) {
+#pragma unroll
+					for (int u = 0; u < B3_WALK_U; ++u) { const uint32_t jj = min(s0 + (uint32_t)u, last); pw_n[u] = lb[jj]; p3_n[u] = ord[jj]; }
+				}
+				for (uint32_t j = s0; j < s1; j += B3_WALK_U) {
+					uint32_t pw[B3_WALK_U], p3[B3_WALK_U], sn[B3_WALK_U];
+#pragma unroll
+					for (int u = 0; u < B3_WALK_U; ++u) { pw[u] = pw_n[u]; p3[u] = p3_n[u]; }
+#pragma unroll
+					for (int u = 0; u < B3_WALK_U; ++u) { const uint32_t jj = min(j + (uint32_t)(B3_WALK_U + u), last); pw_n[u] = lb[jj]; p3_n[u] = ord[jj]; }
+#pragma unroll
+					for (int u = 0; u < B3_WALK_U; ++u) {
+						const uint32_t in = (uint32_t)(j + (uint32_t)u < s1);
+						const uint32_t b0 = pw[u] & 511u, b1 = (pw[u] >> 9) & 511u, b2 = (pw[u] >> 18) & 511u, b3 = p3[u] & 511u;
+						const uint32_t o0 = __hip_atomic_fetch_or(b3_wordp(region, bl64, b0), in << (b0 & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+						const uint32_t o1 = __hip_atomic_fetch_or(b3_wordp(region, bl64, b1), in << (b1 & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+						const uint32_t o2 = __hip_atomic_fetch_or(b3_wordp(region, bl64, b2), in << (b2 & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+						const uint32_t o3 = __hip_atomic_fetch_or(b3_wordp(region, bl64, b3), in << (b3 & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+						sn[u] = in & b3_bit(o0, b0) & b3_bit(o1, b1) & b3_bit(o2, b2) & b3_bit(o3, b3);
+					}
+#pragma unroll
+					for (int u = 0; u < B3_WALK_U; ++u) if (sn[u]) ord[j + (uint32_t)u] = (unsigned short)(p3[u] | B3_SEEN16);
+				}
+			}
+			__syncthreads();
+			B3_TC(5);
+			// ---- emit the listed k-mers the walk found seen (record re-read by its index), behind what pass 1 emitted
+			// A wave draws the slots of all its seen k-mers at once and has their records on their way together (B3_COLD_NR positions per thread).
+			{
+				uint32_t sm = 0, tot = 0; // bit t: this thread's t-th position is a seen k-mer
+#pragma unroll
+				for (int t = 0; t < B3_COLD_NR; ++t) {
+					const uint32_t li = (uint32_t)tid + (uint32_t)t * BT;
+					if (li < ln) {
+						const uint32_t seen = (ord[li] & B3_SEEN16) != 0;
+						if (A.seen_out) A.seen_out[la[li]] = seen ? 2 : 1;
+						sm |= seen << t;
 					}
 				}
-			}
-			__syncthreads();
-			// ---- emit the listed k-mers the walk found seen (record re-read by its index), behind what pass 1 emitted
-			for (uint32_t t0 = 0; t0 < ln; t0 += BT) {
-				const uint32_t li = t0 + tid;
-				bool seen = false;
-				if (li < ln) {
-					seen = (lb[li] & B3_SEEN) != 0;
-					if (A.seen_out) A.seen_out[la[li]] = seen ? 2 : 1;
-				}
-				const unsigned long long vote = __ballot(seen);
-				if (vote) {
+#pragma unroll
+				for (int t = 0; t < B3_COLD_NR; ++t) tot += (uint32_t)__popcll(__ballot((sm >> t) & 1u));
+				if (tot) { // (wave-uniform)
 					uint32_t o = 0;
-					if (lane == 0) o = atomicAdd(&s_emit_n, (uint32_t)__popcll(vote));
+					if (lane == 0) o = atomicAdd(&s_emit_n, tot);
 					o = __builtin_amdgcn_readfirstlane(o);
-					if (seen) {
-						const RecW<3> r = rec_load<3>(recs + (uint64_t)lc[li] * 3);
-						ho_base[o + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(vote >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vote, 0u))] = entry3(r.d[0], r.d[1]);
+					RecW<3> r[B3_COLD_NR];
+#pragma unroll
+					for (int t = 0; t < B3_COLD_NR; ++t) {
+						r[t].d[0] = r[t].d[1] = r[t].d[2] = 0;
+						if ((sm >> t) & 1u) r[t] = rec_load<3>(recs + (uint64_t)lc[(uint32_t)tid + (uint32_t)t * BT] * 3);
+					}
+#pragma unroll
+					for (int t = 0; t < B3_COLD_NR; ++t) {
+						const unsigned long long vote = __ballot((sm >> t) & 1u);
+						if ((sm >> t) & 1u) ho_base[o + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(vote >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)vote, 0u))] = entry3(r[t].d[0], r[t].d[1]);
+						o += (uint32_t)__popcll(vote);
 					}
 				}
 			}
 			dirty = ln != 0;
 			__syncthreads();
+			B3_TC(6);
 		}
 	} else
 	if (!ovf_list) {
@@ -480,10 +551,15 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 #ifdef BFCG_MEASURE
 	if (timing) {
 		tq[5] = clock64();
-		for (int t = 0; t < 5; ++t) atomicAdd(&A.stats[10 + t], (unsigned long long)(tq[t + 1] - tq[t]));
-		atomicAdd(&A.stats[15], (unsigned long long)(tq[6] - tq[2])); // pass A alone (part of slot 12)
+		if (BFCG_ABL(P, 128)) { // (the six slots hold the sub-steps of a COLD launch's slot 12 instead; a warm launch and a region on the slow path add nothing)
+			if (COLD) for (int t = 0; t < 6; ++t) atomicAdd(&A.stats[10 + t], (unsigned long long)(tc[t + 1] - tc[t]));
+		} else {
+			for (int t = 0; t < 5; ++t) atomicAdd(&A.stats[10 + t], (unsigned long long)(tq[t + 1] - tq[t]));
+			atomicAdd(&A.stats[15], (unsigned long long)(tq[6] - tq[2])); // pass A alone (part of slot 12)
+		}
 	}
 #endif
+#undef B3_TC
 	(void)s_pad3;
 }
 
@@ -554,7 +630,7 @@ __global__ __launch_bounds__(BT, 6) void k_bloom3fm(KParams P, BloomArgs A)
 	unsigned int *region_hi = reinterpret_cast<unsigned int *>(sp); sp += (size_t)region_dw * 4;
 	unsigned int *bcnt = reinterpret_cast<unsigned int *>(sp), *boff = bcnt + nblk; sp += (size_t)(2 * nblk + 4) * 4;
 	unsigned int *la = reinterpret_cast<unsigned int *>(sp); sp += (size_t)P.list_cap * 4;   // file-order index
-	unsigned int *lb = reinterpret_cast<unsigned int *>(sp); sp += (size_t)P.list_cap * 4;   // block | h1 << 8 | h2 << 17 (| B3_SEEN)
+	unsigned int *lb = reinterpret_cast<unsigned int *>(sp); sp += (size_t)P.list_cap * 4;   // block | h1 << 8 | h2 << 17
 	unsigned short *ord = reinterpret_cast<unsigned short *>(sp);                            // the list's entries in (block, file index) order
 	const uint32_t *recs = A.recs + (uint64_t)rs * 4;
 	unsigned int *g_region = reinterpret_cast<unsigned int *>(A.bloom) + (uint64_t)f * region_dw;
