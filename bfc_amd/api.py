@@ -148,6 +148,15 @@ def _clip(L, fn, obj, k, min_cnt, max_tip, max_mean, islands, max_rounds):
     return p, stats[:n.value].copy()
 
 
+def _pop(L, fn, obj, k, min_cnt, max_arm, max_diff, max_mean, max_rounds):
+    """(pointer to the new table, stats u64 (rounds, 3)) of bfcg_kmers_pop / bfcg_pop_host on `obj`; max_arm None = 2 k"""
+    stats, n = np.zeros((max(0, min(int(max_rounds), 64)), 3), dtype=np.uint64), C.c_int(0)
+    p = fn(obj, int(min_cnt), 2 * k if max_arm is None else int(max_arm), int(max_diff), int(max_mean), int(max_rounds), stats.ctypes.data, C.byref(n))
+    if not p:
+        raise BfcGpuError(L.bfcg_last_error().decode())
+    return p, stats[:n.value].copy()
+
+
 def unitig_rows(seq, off, n_kmers, cnt_sum, ends):
     """The five arrays of unitigs() as a sorted list of (sequence bytes, n_kmers, cnt_sum, left stop, right stop, cycle 0 / 1)."""
     s = np.asarray(seq, dtype=np.uint8).tobytes()
@@ -262,6 +271,11 @@ class HostTable:
     def clip(self, min_cnt=1, max_tip=None, max_mean=255, islands=False, max_rounds=8):
         """(HostTable, stats u64 (rounds, 3)): GpuKmers.clip's host twin (bfcg_clip_host)."""
         p, stats = _clip(self.L, self.L.bfcg_clip_host, self.ptr, self.k, min_cnt, max_tip, max_mean, islands, max_rounds)
+        return HostTable(p), stats
+
+    def pop_bubbles(self, min_cnt=1, max_arm=None, max_diff=0, max_mean=255, max_rounds=8):
+        """(HostTable, stats u64 (rounds, 3)): GpuKmers.pop_bubbles's host twin (bfcg_pop_host)."""
+        p, stats = _pop(self.L, self.L.bfcg_pop_host, self.ptr, self.k, min_cnt, max_arm, max_diff, max_mean, max_rounds)
         return HostTable(p), stats
 
     def insert(self, y0, y1, is_high, forced=1):
@@ -1040,10 +1054,22 @@ class GpuKmers:
         p, stats = _clip(self.L, self.L.bfcg_kmers_clip, self.t, self.k, min_cnt, max_tip, max_mean, islands, max_rounds)
         return GpuKmers._adopt(p, None), stats
 
+    def pop_bubbles(self, min_cnt=1, max_arm=None, max_diff=0, max_mean=255, max_rounds=8):
+        """The simple bubbles of the graph at min_cnt popped (odd k <= 37; include/bfc_gpu.h defines arm, simple bubble, loser and
+        round): (a new GpuKmers that owns its table, stats u64 (rounds, 3)).  A bubble is two unitigs of at most max_arm k-mers each
+        (None: 2 k), their lengths at most max_diff apart, that leave one k-mer with two successors and meet in one k-mer with two
+        predecessors; a round removes of each bubble the arm with the lower mean count (a tie: the one whose spelling starts with the
+        larger k-mer) if that mean is at most max_mean (255: any), and leaves the nodes that survive; rounds repeat until one removes
+        nothing or max_rounds have run.  stats has a row per round that removed something: bubbles popped, k-mers removed, keys left.
+        max_rounds = 0 only drops the k-mers with a count below min_cnt.  This table is not written.  The result's last_ms() is the
+        time of all the call's kernels."""
+        p, stats = _pop(self.L, self.L.bfcg_kmers_pop, self.t, self.k, min_cnt, max_arm, max_diff, max_mean, max_rounds)
+        return GpuKmers._adopt(p, None), stats
+
     def last_ms(self):
         """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces,
         read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces, neighbors() / list_graph() / extend() all their pieces, graph_census() one pass, unitigs() the call that writes; of a union() result,
-        its size passes and fill; of a clip() result, every kernel of the call."""
+        its size passes and fill; of a clip() or pop_bubbles() result, every kernel of the call."""
         return self._ms
 
 

@@ -1,7 +1,8 @@
 // bfcg_glink.h -- the link rule of the compacted graph and what goes with it, for the files that walk the count table's de Bruijn graph from
-// its open ends: bfcg_unitigs.hip (every unitig as bases) and bfcg_clip.hip (tips and islands removed into a new table).  include/bfc_gpu.h
+// its open ends: bfcg_unitigs.hip (every unitig as bases), bfcg_clip.hip (tips and islands removed into a new table) and bfcg_pop.hip (the
+// weaker arm of every simple bubble removed likewise).  include/bfc_gpu.h
 // defines nodes, link(x), paths and the stop codes; the k-mer in registers and the probes are bfcg_gprobe.h's, the listing bfcg_klist.h's.
-//   rc_planes, text_less, succ_planes   oriented k-mers as planes, for the device and the host
+//   rc_planes, text_less, succ_planes, pred_planes   oriented k-mers as planes, for the device and the host
 //   link_rule        the rule that joins two nodes, written once for the kernels and the host twins
 //   EndPred          the listing's predicate: a node is kept if one of its sides is open; the two stop codes are the third column
 //   set_mark         one bit per slot, a plain vector atomicOr that returns nothing
@@ -21,8 +22,8 @@ namespace {
 
 enum { UT_BT = 64 /* a lane walks a start: a workgroup is one wave */ };
 // the object's buffers (bfcg_kmers.d_ut): the marks, the cycles' nodes, counters; per set of starts (paths at +0, cycles at +SET) a
-// record, the winner flag, the length in bases and their scans; the call's five outputs.  bfcg_kmers_clip uses the marks (its KILL
-// bits) and the counters
+// record, the winner flag, the length in bases and their scans; the call's five outputs.  bfcg_kmers_clip and bfcg_kmers_pop use the
+// marks (their KILL bits) and the counters
 enum { B_MARK, B_CAND, B_CTR, B_REC, B_WIN, B_LEN, B_UIDX, B_BOFF, SET = 5, B_SEQ = B_REC + 2 * SET, B_OFF, B_NK, B_SUM, B_ENDS, B_N };
 static_assert(B_N <= BFCG_UT_NBUF, "bfcg_kmers.d_ut is too short");
 
@@ -44,9 +45,13 @@ __host__ __device__ __forceinline__ void succ_planes(int k, uint64_t a, uint64_t
 	const uint64_t m = kdec::mask(k);
 	ya = (a << 1 | (uint64_t)(c & 1)) & m; yb = (b << 1 | (uint64_t)(c >> 1)) & m;
 }
+__host__ __device__ __forceinline__ void pred_planes(int k, uint64_t a, uint64_t b, int c, uint64_t &ya, uint64_t &yb) // a, b masked
+{
+	ya = a >> 1 | (uint64_t)(c & 1) << (k - 1); yb = b >> 1 | (uint64_t)(c >> 1) << (k - 1);
+}
 
-// link(x) of include/bfc_gpu.h for the oriented k-mer (a, b), masked: 0 and y = (ya, yb), or the stop code 1, 2, 3, 6.  `tab` answers
-// present4(a, b, pred, min_cnt) as for extend_rule (bfcg_graph.hip)
+// link(x) of include/bfc_gpu.h for the oriented k-mer (a, b), masked: 0 and y = (ya, yb), or the stop code 1, 2, 3, 6; with 3 and 6
+// (ya, yb) is the single successor all the same.  `tab` answers present4(a, b, pred, min_cnt) as for extend_rule (bfcg_graph.hip)
 template <class T>
 __host__ __device__ __forceinline__ int link_rule(const T &tab, int k, uint64_t a, uint64_t b, int min_cnt, uint64_t &ya, uint64_t &yb)
 {

@@ -1,6 +1,6 @@
 """A `bfc -d` dump read as a de Bruijn graph on the GPU: how many k-mers are dead ends, how many branch, and what lies around a k-mer.
 
-    python -m bfc_amd.kmergraph [-m INT] [-c INT [-a INT] [-i] [-r INT] [-o FILE]] [-t|-b] [-u] [-x FILE] [-l INT] table.dump
+    python -m bfc_amd.kmergraph [-m INT] [-c INT [-i]] [-p INT [-d INT]] [-a INT] [-r INT] [-o FILE] [-t|-b] [-u] [-x FILE] [-l INT] table.dump
 
 The dump is restored with bfc_ch_restore and uploaded.  A k-mer is PRESENT if the table holds it with count >= INT (-m, default 1); a NODE
 is a k-mer of the table with such a count, on the strand the table stores (the one hash2cnt prints); its out-degree o is the number of
@@ -14,6 +14,15 @@ such tool, so the output format is this project's.  Standard output, in this ord
                           islands (both ends dead); it leaves the k-mers with a count of at least -m that survive.  Rounds repeat until
                           one removes nothing or -r INT (default 8) have run.  One line per round that removed something, rounds from 1:
                           the unitigs and k-mers it removed and the keys it left.  -o FILE writes the cleaned table as a dump
+    pop<TAB>round<TAB>bubbles<TAB>kmers<TAB>keys_left
+                          under -p INT, after the clip lines: the simple bubbles of the graph are popped on the GPU (bfcg_kmers_pop; odd
+                          k <= 37) and every line below describes the table that is left.  A bubble is two unitigs of at most INT k-mers
+                          each (0: 2 k), their lengths at most -d INT apart (default 0), between one k-mer with two successors and one
+                          with two predecessors; a round removes of each the arm with the lower mean count if that mean is at most -a
+                          INT.  Rounds and -r, -o as for -c.  One line per round that removed something: the bubbles it popped, the
+                          k-mers it removed, the keys it left.  With -c and -p the tips are clipped first, then the bubbles popped, then
+                          the tips clipped once more with the same parameters (popping makes no tip, but the chain is closed): that
+                          second clipping's lines follow the pop lines, its rounds numbered on from the first's
     deg<TAB>o<TAB>n0<TAB>n1<TAB>n2<TAB>n3<TAB>n4
                           five lines, o = 0..4: the nodes with out-degree o and in-degree 0..4 (bfcg_kmers_graph_census; k <= 37).  A
                           node stored as its reverse complement has the two degrees swapped; the five lines below count classes that are
@@ -49,10 +58,12 @@ USAGE = """Usage: kmergraph [options] <table.dump>
 Options:
   -m INT   a k-mer is present with occ >= INT [1]
   -c INT   clip tips of at most INT k-mers first (0: 2k); all output describes the cleaned table (odd k <= 37)
-  -a INT   clip only unitigs whose mean count is at most INT [255]
-  -i       clip islands too
-  -r INT   at most INT rounds of clipping [8]
-  -o FILE  write the cleaned table as a dump (with -c)
+  -p INT   pop simple bubbles with arms of at most INT k-mers (0: 2k), after -c; all output describes the table left (odd k <= 37)
+  -d INT   the arms of a bubble differ by at most INT k-mers [0] (with -p)
+  -a INT   clip / pop only unitigs whose mean count is at most INT [255]
+  -i       clip islands too (with -c)
+  -r INT   at most INT rounds of clipping, of popping [8]
+  -o FILE  write the cleaned table as a dump (with -c or -p)
   -t       list the tips
   -b       list the branching k-mers
   -u       list the unitigs of the compacted graph (odd k <= 37)
@@ -112,12 +123,13 @@ def _unitig_lines(rows, out):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     try:
-        opts, args = getopt.getopt(argv, "tbuim:x:l:c:a:r:o:")
+        opts, args = getopt.getopt(argv, "tbuim:x:l:c:a:r:o:p:d:")
     except getopt.GetoptError:
         opts, args = [], []
     o = dict(opts)
     modes = [f for f in ("-t", "-b") if f in o]
-    if len(args) != 1 or len(modes) > 1 or ("-c" not in o and any(f in o for f in ("-a", "-i", "-r", "-o"))):
+    cleans = "-c" in o or "-p" in o
+    if len(args) != 1 or len(modes) > 1 or (not cleans and any(f in o for f in ("-a", "-r", "-o"))) or ("-i" in o and "-c" not in o) or ("-d" in o and "-p" not in o):
         sys.stderr.write(USAGE)
         return 1
     from . import api
@@ -129,11 +141,19 @@ def main(argv=None):
     km = api.GpuKmers(t)
     rc = 0
     try:
-        if "-c" in o:   # (refused, like -u, before any output)
-            clean, stats = km.clip(min_cnt, _atoi(o["-c"]) or None, _atoi(o.get("-a", "255")), "-i" in o, _atoi(o.get("-r", "8")))
-            km.close()
-            km = clean
-            out.write(b"".join(b"clip\t%d\t%d\t%d\t%d\n" % (i + 1, r[0], r[1], r[2]) for i, r in enumerate(stats)))
+        if cleans:   # (refused, like -u, before any output)
+            max_mean, max_rounds, clipped = _atoi(o.get("-a", "255")), _atoi(o.get("-r", "8")), 0
+            steps = ["clip", "pop", "clip"] if "-c" in o and "-p" in o else ["clip"] if "-c" in o else ["pop"]
+            for step in steps:
+                if step == "clip":
+                    clean, stats = km.clip(min_cnt, _atoi(o["-c"]) or None, max_mean, "-i" in o, max_rounds)
+                else:
+                    clean, stats = km.pop_bubbles(min_cnt, _atoi(o["-p"]) or None, _atoi(o.get("-d", "0")), max_mean, max_rounds)
+                km.close()
+                km = clean
+                first = clipped if step == "clip" else 0
+                out.write(b"".join(b"%s\t%d\t%d\t%d\t%d\n" % (step.encode(), first + i + 1, r[0], r[1], r[2]) for i, r in enumerate(stats)))
+                clipped += len(stats) if step == "clip" else 0
             if "-o" in o:
                 h = km.to_host()
                 failed = h.dump(o["-o"]) != 0

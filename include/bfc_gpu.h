@@ -517,9 +517,52 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *                         goes on; a lane that removes walks the same steps again and sets one bit per slot in a bitmap; one streaming
  *                         pass counts the survivors per sub-table, a second upserts them into the new table.  Intermediate tables are
  *                         freed as soon as the next one stands.  Device memory: one bit per slot, the listing, and the tables of two rounds
+ * Simple bubbles popped (bfcg_pop.hip): of two parallel unitigs between one k-mer and another -- a substitution error seen twice, a
+ * heterozygous SNP, a short indel -- the weaker one is removed into a new table, on either form of the object.  The domain is
+ * bfcg_kmers_clip's -- odd k <= 37, min_cnt in [1, 255] --, and nodes, link(x), unitigs, stop codes and the spelling emitted are exactly
+ * those defined above.
+ *   ARM         a unitig of the graph at min_cnt that is a path, not a cycle, with stop code 3 on both ends.  Oriented from its first
+ *               oriented k-mer s to its last e: s has exactly one present predecessor p, its ENTRY, and e exactly one present successor
+ *               q, its EXIT (both follow from code 3).  Read from the other end the entry is rc(q) and the exit rc(p)
+ *   SIMPLE BUBBLE  an arm U and a second unitig V such that: p has exactly two present successors, s and s'; q has exactly two present
+ *               predecessors; s' != rc(e), so the sibling is not U read backwards (the inverted case q == rc(p)); V, oriented to
+ *               start at s', is an arm whose exit is the same oriented k-mer q; n_kmers(U) <= max_arm and n_kmers(V) <= max_arm;
+ *               |n_kmers(U) - n_kmers(V)| <= max_diff.  V is unique given U, the relation is symmetric, and U and V share no node
+ *   LOSER       the arm with the lower mean count: cnt_sum(U) * n_kmers(V) < cnt_sum(V) * n_kmers(U), in 64-bit integers; on a tie the
+ *               arm whose emitted spelling's first k-mer is larger as text.  The loser is removed only if cnt_sum <= max_mean *
+ *               n_kmers (max_mean = 255 switches this rule off); if it fails that, neither arm goes
+ *   a ROUND     as bfcg_kmers_clip's: it decides on its input graph only and removes the losers of all simple bubbles at once.  Arms of
+ *               different bubbles are node-disjoint, so the result does not depend on any order.  Its output is the table of the
+ *               surviving nodes at min_cnt; key, count and high count of a survivor are unchanged.  Rounds repeat on the previous
+ *               round's output until one removes nothing or max_rounds rounds have run.  max_rounds = 0 is the threshold filter,
+ *               identical to bfcg_kmers_clip's
+ *   not touched, deliberately: a site with three or more branches; two variants closer than k that come from different reads (their
+ *               arms interlock: beside each lies a path that the other cuts, not an arm); an arm beside a direct edge p -> q (the edge
+ *               is no unitig); the inverted case.  A bubble nested inside another's arm is popped in one round and the outer one in the
+ *               next, once the arm it sat in is one unitig
+ *   bfcg_kmers_pop        a new object that owns its table, word for word as bfcg_kmers_clip's: the input's k and l_pre, cshift by the
+ *                         union's rule on the survivors, the order inside a sub-table unspecified; an empty result is a valid table;
+ *                         the input is never written, and an attached input stays attached and unchanged.  *n_rounds = the rounds
+ *                         that ran and removed something; stats (may be NULL, else room for 3 * max_rounds words) gets three words per
+ *                         such round: bubbles popped, k-mers removed, keys left.  Refused before any launch with a message, the outputs
+ *                         untouched and the object usable: even k and k > 37 (the unitigs' messages), min_cnt outside [1, 255],
+ *                         max_arm outside [1, 65535], max_diff outside [0, 65535], max_mean outside [1, 255], max_rounds outside
+ *                         [0, 64], NULL t or n_rounds.  NULL on refusal or error; bfcg_kmers_last_ms(result) covers every kernel of
+ *                         the call.
+ *                         How, per round: the unitigs' listing pass yields the nodes with an open side; one lane per side with code 3
+ *                         walks its arm for at most max_arm k-mers, summing counts, and goes on only if the far side has code 3 too
+ *                         and its own end is the one that emits, so one lane per arm continues; it checks the entry's two successors
+ *                         and the exit's two predecessors, walks the sibling's unitig for at most max_arm k-mers to the same exit,
+ *                         applies max_diff, the loser rule and max_mean, and if its own arm is to go walks it again and sets one bit
+ *                         per slot.  A lane decides its own arm only, so no two lanes mark the same node, and no lane takes more than
+ *                         3 * max_arm steps whatever the graph holds.  The marks become the new table by bfcg_kmers_clip's two
+ *                         streaming passes (one piece of code for both).  Device memory as for bfcg_kmers_clip
  * Their host twins and the text forms use no GPU:
  *   bfcg_clip_host        bfcg_kmers_clip -- result, stats, refusals -- by the same rule (one piece of code for both) on
  *                         bfcg_kmer_occ_host, over bfc_ch_export_sorted's slots, into a table made at the same cshift rule
+ *   bfcg_pop_host         bfcg_kmers_pop -- result, stats, refusals -- by the same rule (one piece of code for both) on
+ *                         bfcg_kmer_occ_host, over bfc_ch_export_sorted's slots: every side with code 3 decides on its arm, the removed
+ *                         nodes go into a set, and the call fails if the k-mers removed are not the set's size
  *   bfcg_kmer_from_str    the inverse of bfcg_kmer_2str; -1 unless s has exactly k bytes of ACGTacgt
  *   bfcg_kmer_occ_host    bfc_ch_kmer_occ on listing-style planes of either strand (the four planes of bfc_kmer_t built from the two)
  *   bfcg_kmers_occ_host   the same for n k-mers
@@ -590,6 +633,9 @@ enum { BFCG_CLIP_ISLANDS = 1 };
 bfcg_kmers_t *bfcg_kmers_clip(bfcg_kmers_t *t, int min_cnt, int max_tip, int max_mean, int flags, int max_rounds,
                               uint64_t *stats /* 3 per round: unitigs removed, k-mers removed, keys left */, int *n_rounds);
 bfc_ch_t     *bfcg_clip_host(const bfc_ch_t *ch, int min_cnt, int max_tip, int max_mean, int flags, int max_rounds, uint64_t *stats, int *n_rounds);
+bfcg_kmers_t *bfcg_kmers_pop(bfcg_kmers_t *t, int min_cnt, int max_arm, int max_diff, int max_mean, int max_rounds,
+                             uint64_t *stats /* 3 per round: bubbles popped, k-mers removed, keys left */, int *n_rounds);
+bfc_ch_t     *bfcg_pop_host(const bfc_ch_t *ch, int min_cnt, int max_arm, int max_diff, int max_mean, int max_rounds, uint64_t *stats, int *n_rounds);
 
 /* unit-test hooks: K1 only.  out = 3 u64 per position: y0, y1, flags (bit0 k-mer ends here, bit1 high) */
 int bfcg_hash_positions(bfcg_ctx_t *c, const uint8_t *h_seq, const uint8_t *h_qual, uint64_t n_pos, uint64_t *out);

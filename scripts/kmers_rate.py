@@ -2,7 +2,7 @@
 from the attached context, kernels only, against the path it replaces for the spectrum -- bfcg_export_table followed by the host's
 bfc_ch_hist.  Not the headline bench; numbers quoted in profiles/kmers_rate.md.
 
-    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph | --unitigs | --clip] [k] [bf_shift] [genome size] [coverage]
+    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph | --unitigs | --clip | --pop] [k] [bf_shift] [genome size] [coverage]
 
 --lookup measures the other direction instead (bfcg_lookup.hip): lookup() of every listed k-mer in shuffled order, and profile() over a
 prefix of the reads that built the table, each next to the host's loop over bfc_ch_kmer_occ on the same input (bfcg_kmers_occ_host,
@@ -21,6 +21,9 @@ without it: export the table, bfcg_unitigs_host on the CPU (one thread).  The pe
 --clip measures the graph cleaning (bfcg_clip.hip): clip() at the default parameters -- tips of at most 2 k k-mers, eight rounds at most --
 and with islands, all the call's kernels, in k-mers of the input per second, beside unitigs() on the same table in the same run (the only
 yardstick there is: nobody measured this before), and the unitigs of the cleaned table beside those of the input.
+--pop measures the bubble popping (bfcg_pop.hip): pop_bubbles() at the default parameters -- arms of at most 2 k k-mers of equal length,
+eight rounds at most -- and with max_diff 2, all the call's kernels, beside clip() at its defaults on the same table in the same run, the
+unitigs before and after, and the route without it: export the table, bfcg_pop_host on the CPU (one thread).
 """
 import os
 import sys
@@ -51,6 +54,9 @@ if UNITIGS:
 CLIP = "--clip" in sys.argv
 if CLIP:
     sys.argv.remove("--clip")
+POP = "--pop" in sys.argv
+if POP:
+    sys.argv.remove("--pop")
 arg = lambda i, d: int(sys.argv[i]) if len(sys.argv) > i else d  # noqa: E731
 k, b, G, cov = arg(1, 31), arg(2, 33), arg(3, 4_600_000), arg(4, 100)
 rs = gen.ReadSet(seed=2, G=G, cov=cov)
@@ -351,6 +357,62 @@ def clip_rates(min_cnt=1):
               % (best, nodes / best / 1e6, best / min(ums), min(ums), res.l_pre, res.cshift, shape(res)[0]))
         res.close()
 
+
+def pop_rates(min_cnt=1):
+    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
+    print("build %s" % bfc_amd._lib.build_id())
+
+    def shape(t):
+        seq_u, off_u, nk, cs, ends = t.unitigs(min_cnt)
+        lens = np.sort(np.diff(off_u).astype(np.int64))[::-1]
+        n50 = int(lens[np.searchsorted(np.cumsum(lens), (int(lens.sum()) + 1) // 2)]) if len(lens) else 0
+        arms = int(((ends & 63) == (3 | 3 << 3)).sum())
+        return "%d unitigs over %d nodes, N50 %d bases, %d with ends (3, 3)" % (len(nk), int(nk.sum()), n50, arms), int(nk.sum())
+
+    text, nodes = shape(km)
+    print("input (min_cnt %d): %s" % (min_cnt, text))
+    cms = []
+    for rep in range(3):
+        res, stats = km.clip(min_cnt=min_cnt)
+        cms.append(res.last_ms())
+        res.close()
+    print("clip (max_tip %d, max_mean 255, at most 8 rounds), all kernels, 3 runs (ms): %s; %d rounds" % (2 * km.k, f(cms), len(stats)))
+    for max_diff in (0, 2):
+        pms, wall = [], []
+        for rep in range(3):
+            t0 = time.perf_counter()
+            res, stats = km.pop_bubbles(min_cnt=min_cnt, max_diff=max_diff)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            pms.append(res.last_ms())
+            if rep < 2:
+                res.close()
+        best = min(pms)
+        print("pop_bubbles (min_cnt %d, max_arm %d, max_diff %d, max_mean 255, at most 8 rounds), all kernels, 3 runs (ms): %s; wall: %s"
+              % (min_cnt, 2 * km.k, max_diff, f(pms), " ".join("%.1f" % v for v in wall)))
+        print("pop rounds (bubbles popped, k-mers removed, keys left): %s" % " ".join("(%d, %d, %d)" % tuple(int(v) for v in r) for r in stats))
+        print("pop best: %.3f ms = %.2f G k-mers of the input per second = %.2f x clip (%.3f ms); result 2^%d sub-tables of 2^%d slots; %s"
+              % (best, nodes / best / 1e6, best / min(cms), min(cms), res.l_pre, res.cshift, shape(res)[0]))
+        if max_diff == 0:
+            dev_stats, dev_keys = stats, len(res.list(1)[1])
+        res.close()
+    t0 = time.perf_counter()
+    t = g.export_table()
+    t1 = time.perf_counter()
+    print("export: %.1f ms" % ((t1 - t0) * 1e3), flush=True)
+    h, hstats = t.pop_bubbles(min_cnt=min_cnt)
+    t2 = time.perf_counter()
+    print("export + host bfcg_pop_host (defaults), one thread: %.1f ms + %.1f ms = %.1f ms (%.0fx the kernels)" % ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t2 - t0) * 1e3, (t2 - t0) * 1e3 / best))
+    assert np.array_equal(hstats, dev_stats) and h.count() == dev_keys
+    print("the host's rounds and keys equal the device's")
+    h.close()
+    t.close()
+
+
+if POP:
+    pop_rates()
+    km.close()
+    g.close()
+    sys.exit(0)
 
 if CLIP:
     clip_rates()
