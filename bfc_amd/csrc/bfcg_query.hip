@@ -95,7 +95,9 @@ extern "C" bfcg_trim_t *bfcg_trim_create(int k, const bfc_bf_t *bf, int device, 
 		BFCG_CKN(bfcg_trim_destroy(t), hipMalloc(&t->bloom, 1ULL << (bf->n_shift - 3)));
 		BFCG_CKN(bfcg_trim_destroy(t), hipMemcpy(t->bloom, bf->b, 1ULL << (bf->n_shift - 3), hipMemcpyHostToDevice));
 	}
-	BFCG_CKN(bfcg_trim_destroy(t), hipMalloc(&t->d_seq, max_pos)); BFCG_CKN(bfcg_trim_destroy(t), hipMalloc(&t->d_flags, max_pos));
+	// d_flags: one bit per position in whole 64-bit words, and k_streak may read the word behind a read's last
+	const uint64_t flag_bytes = 8 * (max_pos / 64 + 2);
+	BFCG_CKN(bfcg_trim_destroy(t), hipMalloc(&t->d_seq, max_pos)); BFCG_CKN(bfcg_trim_destroy(t), hipMalloc(&t->d_flags, max_pos > flag_bytes ? max_pos : flag_bytes));
 	BFCG_CKN(bfcg_trim_destroy(t), hipMalloc(&t->d_off, (max_reads + 1) * 8));
 	BFCG_CKN(bfcg_trim_destroy(t), hipMalloc(&t->d_start, max_reads * 4)); BFCG_CKN(bfcg_trim_destroy(t), hipMalloc(&t->d_end, max_reads * 4));
 	return t;
