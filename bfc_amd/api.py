@@ -139,22 +139,22 @@ def _unitigs(L, fn, obj, min_cnt):
     return seq, off, nk, cs, ends
 
 
-def _clip(L, fn, obj, k, min_cnt, max_tip, max_mean, islands, max_rounds):
-    """(pointer to the new table, stats u64 (rounds, 3)) of bfcg_kmers_clip / bfcg_clip_host on `obj`; max_tip None = 2 k"""
+def _clean(L, fn, obj, max_rounds, *rule):
+    """(pointer to the new table, stats u64 (rounds, 3)) of a graph-cleaning call on `obj` -- bfcg_kmers_clip / bfcg_clip_host,
+    bfcg_kmers_pop / bfcg_pop_host; `rule` = its arguments between the table and max_rounds"""
     stats, n = np.zeros((max(0, min(int(max_rounds), 64)), 3), dtype=np.uint64), C.c_int(0)
-    p = fn(obj, int(min_cnt), 2 * k if max_tip is None else int(max_tip), int(max_mean), CLIP_ISLANDS if islands else 0, int(max_rounds), stats.ctypes.data, C.byref(n))
+    p = fn(obj, *(int(v) for v in rule), int(max_rounds), stats.ctypes.data, C.byref(n))
     if not p:
         raise BfcGpuError(L.bfcg_last_error().decode())
     return p, stats[:n.value].copy()
 
 
-def _pop(L, fn, obj, k, min_cnt, max_arm, max_diff, max_mean, max_rounds):
-    """(pointer to the new table, stats u64 (rounds, 3)) of bfcg_kmers_pop / bfcg_pop_host on `obj`; max_arm None = 2 k"""
-    stats, n = np.zeros((max(0, min(int(max_rounds), 64)), 3), dtype=np.uint64), C.c_int(0)
-    p = fn(obj, int(min_cnt), 2 * k if max_arm is None else int(max_arm), int(max_diff), int(max_mean), int(max_rounds), stats.ctypes.data, C.byref(n))
-    if not p:
-        raise BfcGpuError(L.bfcg_last_error().decode())
-    return p, stats[:n.value].copy()
+def _listing(parts, *extra):
+    """(y (n, 2) u64, count u8, high u8, a column of each dtype in `extra`) of the pieces that pieces(), pieces_vs() or pieces_graph() yield"""
+    parts = list(parts)
+    y, ch, *more = [np.concatenate([p[i] for p in parts]) if parts else np.zeros((0, 2) if i == 0 else 0, dtype=dt)
+                    for i, dt in enumerate((np.uint64, np.uint16) + extra)]
+    return (y, (ch & 0xff).astype(np.uint8), (ch >> 8).astype(np.uint8), *more)
 
 
 def unitig_rows(seq, off, n_kmers, cnt_sum, ends):
@@ -270,12 +270,12 @@ class HostTable:
 
     def clip(self, min_cnt=1, max_tip=None, max_mean=255, islands=False, max_rounds=8):
         """(HostTable, stats u64 (rounds, 3)): GpuKmers.clip's host twin (bfcg_clip_host)."""
-        p, stats = _clip(self.L, self.L.bfcg_clip_host, self.ptr, self.k, min_cnt, max_tip, max_mean, islands, max_rounds)
+        p, stats = _clean(self.L, self.L.bfcg_clip_host, self.ptr, max_rounds, min_cnt, 2 * self.k if max_tip is None else max_tip, max_mean, CLIP_ISLANDS if islands else 0)
         return HostTable(p), stats
 
     def pop_bubbles(self, min_cnt=1, max_arm=None, max_diff=0, max_mean=255, max_rounds=8):
         """(HostTable, stats u64 (rounds, 3)): GpuKmers.pop_bubbles's host twin (bfcg_pop_host)."""
-        p, stats = _pop(self.L, self.L.bfcg_pop_host, self.ptr, self.k, min_cnt, max_arm, max_diff, max_mean, max_rounds)
+        p, stats = _clean(self.L, self.L.bfcg_pop_host, self.ptr, max_rounds, min_cnt, 2 * self.k if max_arm is None else max_arm, max_diff, max_mean)
         return HostTable(p), stats
 
     def insert(self, y0, y1, is_high, forced=1):
@@ -800,6 +800,12 @@ class GpuKmers:
         sub_hi = (1 << self.l_pre) if sub_hi is None else sub_hi
         if self.k > 37:  # fail before any work, with the library's message
             self.list_raw(min_cnt, min_diff, sub_lo, sub_hi, 0)
+        yield from self._pieces(lambda lo, hi, cap: self.list_raw(min_cnt, min_diff, lo, hi, cap), sub_lo, sub_hi, piece, sizes)
+
+    def _pieces(self, raw, sub_lo, sub_hi, piece, sizes):
+        """The walk of pieces(), pieces_vs() and pieces_graph(): raw(lo, hi, cap) is one of the *_raw calls on sub-tables [lo, hi) ->
+        (rc, n, columns ...); yields the columns' first n rows per piece."""
+        sub_hi = (1 << self.l_pre) if sub_hi is None else sub_hi
         ends = np.cumsum((self.sub_sizes() if sizes is None else sizes)[sub_lo:sub_hi], dtype=np.uint64)
         max_subs = max(1, self.MAX_SLOTS >> self.cshift)
         self._ms, lo, done = 0.0, sub_lo, 0
@@ -807,19 +813,16 @@ class GpuKmers:
             hi = sub_lo + int(np.searchsorted(ends, done + piece, side="right"))
             hi = min(max(hi, lo + 1), lo + max_subs, sub_hi)
             cap = int(ends[hi - 1 - sub_lo]) - done
-            rc, n, y, ch = self.list_raw(min_cnt, min_diff, lo, hi, cap)
+            rc, n, *cols = raw(lo, hi, cap)
             if rc != 0:
                 raise BfcGpuError("sub-tables [%d, %d) hold %d k-mers, their sizes said %d: the table changed under the listing" % (lo, hi, n, cap))
             self._ms += float(self.L.bfcg_kmers_last_ms(self.t))
-            yield y[:n], ch[:n]
+            yield tuple(c[:n] for c in cols)
             lo, done = hi, done + cap
 
     def list(self, min_cnt=0, min_diff=0, sub_lo=0, sub_hi=None, piece=1 << 24):
         """(y (n, 2) u64, count u8, high u8): the k-mers with count >= min_cnt and min(count, 63) - high >= min_diff, sub-tables ascending."""
-        parts = list(self.pieces(min_cnt, min_diff, sub_lo, sub_hi, piece))
-        y = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 2), dtype=np.uint64)
-        ch = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.uint16)
-        return y, (ch & 0xff).astype(np.uint8), (ch >> 8).astype(np.uint8)
+        return _listing(self.pieces(min_cnt, min_diff, sub_lo, sub_hi, piece))
 
     def strings(self, y):
         """The k-mers as a list of str (bfc_kmer_2str, kmer.h:97)."""
@@ -916,31 +919,14 @@ class GpuKmers:
     def pieces_vs(self, other, min_cnt=0, min_diff=0, other_min=0, other_max=255, sub_lo=0, sub_hi=None, piece=1 << 24, sizes=None):
         """pieces() against `other`: yields (y, cnt_high, other i16) per piece of whole sub-tables, each sized from this table's
         sub-table sizes (an upper bound: the filters only drop)."""
-        sub_hi = (1 << self.l_pre) if sub_hi is None else sub_hi
         self.list_vs_raw(other, min_cnt, min_diff, other_min, other_max, sub_lo, sub_lo, 0)  # an empty range: the library's refusals, before any work
-        ends = np.cumsum((self.sub_sizes() if sizes is None else sizes)[sub_lo:sub_hi], dtype=np.uint64)
-        max_subs = max(1, self.MAX_SLOTS >> self.cshift)
-        self._ms, lo, done = 0.0, sub_lo, 0
-        while lo < sub_hi:
-            hi = sub_lo + int(np.searchsorted(ends, done + piece, side="right"))
-            hi = min(max(hi, lo + 1), lo + max_subs, sub_hi)
-            cap = int(ends[hi - 1 - sub_lo]) - done
-            rc, n, y, ch, oth = self.list_vs_raw(other, min_cnt, min_diff, other_min, other_max, lo, hi, cap)
-            if rc != 0:
-                raise BfcGpuError("sub-tables [%d, %d) hold %d k-mers, their sizes said %d: the table changed under the listing" % (lo, hi, n, cap))
-            self._ms += float(self.L.bfcg_kmers_last_ms(self.t))
-            yield y[:n], ch[:n], oth[:n]
-            lo, done = hi, done + cap
+        yield from self._pieces(lambda lo, hi, cap: self.list_vs_raw(other, min_cnt, min_diff, other_min, other_max, lo, hi, cap), sub_lo, sub_hi, piece, sizes)
 
     def list_vs(self, other, min_cnt=0, min_diff=0, other_min=0, other_max=255, sub_lo=0, sub_hi=None, piece=1 << 24):
         """list() with the k-mers' counts in `other`: (y (n, 2) u64, count u8, high u8, other i16).  A k-mer is kept only if its count in
         `other` (0 where absent) lies in [other_min, other_max]: (0, 0) private to this table, (1, 255) shared, (0, 255) everything;
         other[i] is what other.lookup(y[i]) answers, -1 or high << 8 | count."""
-        parts = list(self.pieces_vs(other, min_cnt, min_diff, other_min, other_max, sub_lo, sub_hi, piece))
-        y = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 2), dtype=np.uint64)
-        ch = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.uint16)
-        oth = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, dtype=np.int16)
-        return y, (ch & 0xff).astype(np.uint8), (ch >> 8).astype(np.uint8), oth
+        return _listing(self.pieces_vs(other, min_cnt, min_diff, other_min, other_max, sub_lo, sub_hi, piece), np.int16)
 
     def format_vs(self, y, cnt_high, other):
         """The lines of a piece of list_vs, "kmer count high count_in_other high_in_other", formatted in C: bytes."""
@@ -998,30 +984,13 @@ class GpuKmers:
     def pieces_graph(self, min_cnt=1, cell_mask=GRAPH_MASKS["all"], sub_lo=0, sub_hi=None, piece=1 << 24, sizes=None):
         """pieces() with the graph predicate: yields (y, cnt_high, nb u8) per piece of whole sub-tables, each sized from the sub-table
         sizes (an upper bound: the predicate only drops)."""
-        sub_hi = (1 << self.l_pre) if sub_hi is None else sub_hi
         self.list_graph_raw(min_cnt, cell_mask, sub_lo, sub_lo, 0)  # an empty range: the library's refusals, before any work
-        ends = np.cumsum((self.sub_sizes() if sizes is None else sizes)[sub_lo:sub_hi], dtype=np.uint64)
-        max_subs = max(1, self.MAX_SLOTS >> self.cshift)
-        self._ms, lo, done = 0.0, sub_lo, 0
-        while lo < sub_hi:
-            hi = sub_lo + int(np.searchsorted(ends, done + piece, side="right"))
-            hi = min(max(hi, lo + 1), lo + max_subs, sub_hi)
-            cap = int(ends[hi - 1 - sub_lo]) - done
-            rc, n, y, ch, nb = self.list_graph_raw(min_cnt, cell_mask, lo, hi, cap)
-            if rc != 0:
-                raise BfcGpuError("sub-tables [%d, %d) hold %d k-mers, their sizes said %d: the table changed under the listing" % (lo, hi, n, cap))
-            self._ms += float(self.L.bfcg_kmers_last_ms(self.t))
-            yield y[:n], ch[:n], nb[:n]
-            lo, done = hi, done + cap
+        yield from self._pieces(lambda lo, hi, cap: self.list_graph_raw(min_cnt, cell_mask, lo, hi, cap), sub_lo, sub_hi, piece, sizes)
 
     def list_graph(self, min_cnt=1, cell_mask=GRAPH_MASKS["all"], sub_lo=0, sub_hi=None, piece=1 << 24):
         """(y (n, 2) u64, count u8, high u8, nb u8): the k-mers with count >= min_cnt whose degree cell 5 * o + i is a set bit of cell_mask
         (GRAPH_MASKS names some), sub-tables ascending; nb bit c: succ by base c is present, bit 4 + c: pred by base c."""
-        parts = list(self.pieces_graph(min_cnt, cell_mask, sub_lo, sub_hi, piece))
-        y = np.concatenate([p[0] for p in parts]) if parts else np.zeros((0, 2), dtype=np.uint64)
-        ch = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, dtype=np.uint16)
-        nb = np.concatenate([p[2] for p in parts]) if parts else np.zeros(0, dtype=np.uint8)
-        return y, (ch & 0xff).astype(np.uint8), (ch >> 8).astype(np.uint8), nb
+        return _listing(self.pieces_graph(min_cnt, cell_mask, sub_lo, sub_hi, piece), np.uint8)
 
     def extend(self, y, min_cnt=1, max_len=300):
         """The unambiguous path to the right of every seed y (n, 2) u64: (bases u8 (n, max_len) of 'A' 'C' 'G' 'T', zero beyond the
@@ -1051,7 +1020,7 @@ class GpuKmers:
         the nodes that survive; rounds repeat until one removes nothing or max_rounds have run.  stats has a row per round that removed
         something: unitigs removed, k-mers removed, keys left.  max_rounds = 0 only drops the k-mers with a count below min_cnt.  This
         table is not written.  The result's last_ms() is the time of all the call's kernels."""
-        p, stats = _clip(self.L, self.L.bfcg_kmers_clip, self.t, self.k, min_cnt, max_tip, max_mean, islands, max_rounds)
+        p, stats = _clean(self.L, self.L.bfcg_kmers_clip, self.t, max_rounds, min_cnt, 2 * self.k if max_tip is None else max_tip, max_mean, CLIP_ISLANDS if islands else 0)
         return GpuKmers._adopt(p, None), stats
 
     def pop_bubbles(self, min_cnt=1, max_arm=None, max_diff=0, max_mean=255, max_rounds=8):
@@ -1063,7 +1032,7 @@ class GpuKmers:
         nothing or max_rounds have run.  stats has a row per round that removed something: bubbles popped, k-mers removed, keys left.
         max_rounds = 0 only drops the k-mers with a count below min_cnt.  This table is not written.  The result's last_ms() is the
         time of all the call's kernels."""
-        p, stats = _pop(self.L, self.L.bfcg_kmers_pop, self.t, self.k, min_cnt, max_arm, max_diff, max_mean, max_rounds)
+        p, stats = _clean(self.L, self.L.bfcg_kmers_pop, self.t, max_rounds, min_cnt, 2 * self.k if max_arm is None else max_arm, max_diff, max_mean)
         return GpuKmers._adopt(p, None), stats
 
     def last_ms(self):

@@ -1,10 +1,12 @@
 // bfcg_glink.h -- the link rule of the compacted graph and what goes with it, for the files that walk the count table's de Bruijn graph from
-// its open ends: bfcg_unitigs.hip (every unitig as bases), bfcg_clip.hip (tips and islands removed into a new table) and bfcg_pop.hip (the
-// weaker arm of every simple bubble removed likewise).  include/bfc_gpu.h
+// its open ends: bfcg_unitigs.hip (every unitig as bases) and, through bfcg_gclean.h's round, bfcg_clip.hip (tips and islands removed into
+// a new table) and bfcg_pop.hip (the weaker arm of every simple bubble removed likewise).  include/bfc_gpu.h
 // defines nodes, link(x), paths and the stop codes; the k-mer in registers and the probes are bfcg_gprobe.h's, the listing bfcg_klist.h's.
 //   rc_planes, text_less, succ_planes, pred_planes   oriented k-mers as planes, for the device and the host
 //   link_rule        the rule that joins two nodes, written once for the kernels and the host twins
+//   arm_walk         the unitig from an open side for a bounded number of k-mers: its length, the sum of its counts, its far end's stop code
 //   EndPred          the listing's predicate: a node is kept if one of its sides is open; the two stop codes are the third column
+//   walk_start       start i of such a listing as a side, its stop code and an oriented k-mer, for the kernels with one lane per start
 //   set_mark         one bit per slot, a plain vector atomicOr that returns nothing
 //   B_*, ut_buf ...  the object's buffers for these calls (bfcg_kmers.d_ut), grown on demand
 #pragma once
@@ -22,8 +24,8 @@ namespace {
 
 enum { UT_BT = 64 /* a lane walks a start: a workgroup is one wave */ };
 // the object's buffers (bfcg_kmers.d_ut): the marks, the cycles' nodes, counters; per set of starts (paths at +0, cycles at +SET) a
-// record, the winner flag, the length in bases and their scans; the call's five outputs.  bfcg_kmers_clip and bfcg_kmers_pop use the
-// marks (their KILL bits) and the counters
+// record, the winner flag, the length in bases and their scans; the call's five outputs.  A cleaning round (bfcg_gclean.h) uses the
+// marks (its KILL bits) and the counters
 enum { B_MARK, B_CAND, B_CTR, B_REC, B_WIN, B_LEN, B_UIDX, B_BOFF, SET = 5, B_SEQ = B_REC + 2 * SET, B_OFF, B_NK, B_SUM, B_ENDS, B_N };
 static_assert(B_N <= BFCG_UT_NBUF, "bfcg_kmers.d_ut is too short");
 
@@ -73,6 +75,25 @@ template <class T> __host__ __device__ __forceinline__ int only_succ(const T &ta
 	return o ? __builtin_ctz(o) : 0;
 }
 
+// The unitig from the oriented k-mer (a, b), whose left side is open, for at most max_n k-mers: the stop code of its right end, which
+// (a, b) then is, n its k-mers, sum their counts and (ya, yb) the single successor under codes 3 and 6; 0 if it is longer than max_n;
+// -1 if a k-mer of the walk is not in the table
+template <class T>
+__host__ __device__ __forceinline__ int arm_walk(const T &tab, int k, int min_cnt, int max_n, uint64_t &a, uint64_t &b, uint64_t &ya, uint64_t &yb, int &n, uint64_t &sum)
+{
+	uint64_t slot = 0;
+	int v = tab.value_at(a, b, slot), right;
+	if (v < 0) return -1;
+	n = 1; sum = (uint64_t)(v & 0xff);
+	while ((right = link_rule(tab, k, a, b, min_cnt, ya, yb)) == 0) {
+		if (n >= max_n) return 0; // too long
+		if ((v = tab.value_at(ya, yb, slot)) < 0) return -1;
+		sum += (uint64_t)(v & 0xff); ++n;
+		a = ya; b = yb;
+	}
+	return right;
+}
+
 // ---- the listing's predicate: a node with an open side -----------------------------------------------------------------------------------
 template <typename W> struct EndPred {
 	static constexpr bool probes = true;
@@ -89,6 +110,22 @@ template <typename W> struct EndPred {
 		return o != 0;
 	}
 };
+
+// Start i of a listing with EndPred: side i & 1 of listed node i >> 1 (0: the stored strand x, its left side; 1: rc(x), whose left side is
+// x's right).  code = that side's stop code; if r.starts(code), true and (a, b) = the oriented k-mer whose left side it is
+template <class R>
+__device__ __forceinline__ bool walk_start(int k, const ulonglong2 *__restrict__ node_y, const uint8_t *__restrict__ node_code, uint64_t i, const R &r, int &code, uint64_t &a, uint64_t &b)
+{
+	const int side = (int)(i & 1), both = node_code[i >> 1];
+	code = side ? both >> 3 : both & 7;
+	if (!r.starts(code)) return false;
+	const uint64_t m = kdec::mask(k);
+	const ulonglong2 x = node_y[i >> 1];
+	a = x.x & m; b = x.y & m;
+	if (side) rc_planes(k, x.x & m, x.y & m, a, b);
+	return true;
+}
+struct OpenSide { __device__ __forceinline__ bool starts(int code) const { return code != 0; } }; // every open side starts: a linked one is where a path comes in
 
 __device__ __forceinline__ void set_mark(uint32_t *mark, uint64_t slot) { atomicOr(&mark[slot >> 5], 1u << (slot & 31)); }
 

@@ -1,6 +1,6 @@
 // bfcg_gprobe.h -- a k-mer of the graph view in registers and the probes of its neighbours, for the files that read the count table as a
 // de Bruijn graph: bfcg_graph.hip (neighbours, census, listing by degree, extension), bfcg_unitigs.hip (the compacted graph) and
-// bfcg_clip.hip (the graph cleaned), the last two through bfcg_glink.h.
+// bfcg_clip.hip and bfcg_pop.hip (the graph cleaned), the last three through bfcg_glink.h.
 //
 // A k-mer is the two planes a listing hands out (bit l = the base l from the 3' end); succ(x, c) shifts both planes left and puts base c
 // at the 3' end, pred(x, c) shifts them right and puts c at the 5' end.  The VALUE of a k-mer is what bfcg_kmers_lookup answers for it, on
@@ -8,7 +8,7 @@
 // neighbour's windows are the k-mer's shifted by one with one bit pair replaced, so the bit reversal is done once per k-mer and the
 // eight hashes start from there (kmer_hash_windows, kmer_dev.h).  All home slots of a group of probes are loaded before the first is
 // looked at.  DevGraph answers for planes on the device what HostGraph answers on the host from bfcg_kmer_occ_host: the rules that walk
-// the graph (extend_rule, link_rule, clip_rule) are templates over the two.
+// the graph (extend_rule, link_rule, arm_walk, the cleaning rules' decide) are templates over the two.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -37,7 +37,7 @@ struct Start { uint64_t a, b, sum; uint32_t nk, ends; }; // a winner: the planes
 __host__ __device__ __forceinline__ uint8_t base_at(uint64_t a, uint64_t b, int l) { return (uint8_t)"ACGT"[(b >> l & 1) << 1 | (a >> l & 1)]; }
 
 // ---- the counting walks ----------------------------------------------------------------------------------------------------------------
-// start i in [first, end): side i & 1 of listed node i >> 1 (0: the stored strand x, its left side; 1: rc(x), whose left side is x's right)
+// start i in [first, end): walk_start's (bfcg_glink.h)
 template <typename W>
 __global__ __launch_bounds__(UT_BT) void k_ut_path_count(TabRef T, int min_cnt, const ulonglong2 *__restrict__ node_y, const uint8_t *__restrict__ node_code, uint64_t first,
                                                          uint64_t end, uint64_t max_steps, uint32_t *__restrict__ mark, Start *__restrict__ rec, uint32_t *__restrict__ win,
@@ -45,13 +45,10 @@ __global__ __launch_bounds__(UT_BT) void k_ut_path_count(TabRef T, int min_cnt, 
 {
 	const uint64_t i = first + (uint64_t)blockIdx.x * UT_BT + threadIdx.x;
 	if (i >= end) return;
-	const int side = (int)(i & 1), code = node_code[i >> 1], left = side ? code >> 3 : code & 7;
-	if (left == 0) return; // this side is linked: the path comes in here, it does not start
+	int left;
+	uint64_t sa, sb, slot = 0;
+	if (!walk_start(T.k, node_y, node_code, i, OpenSide(), left, sa, sb)) return; // this side is linked: the path comes in here, it does not start
 	DevGraph<W> g; g.T = T;
-	const uint64_t m = kdec::mask(T.k);
-	const ulonglong2 x = node_y[i >> 1];
-	uint64_t sa = x.x & m, sb = x.y & m, slot = 0;
-	if (side) rc_planes(T.k, x.x & m, x.y & m, sa, sb);
 	int v = g.value_at(sa, sb, slot);
 	if (v < 0) { atomicOr(&ctr[CTR_ERR], 1ULL); return; } // (a listed node is in the table unless the table changed)
 	set_mark(mark, slot);

@@ -325,73 +325,65 @@ def unitig_rates(min_cnt=1):
     t.close()
 
 
+def _ms3(v):
+    return " ".join("%.3f" % x for x in v)
+
+
+def _shape(t, min_cnt, arms=False):
+    """(text, nodes, kernel ms) of unitigs() on table t; with `arms`, the text also counts the unitigs whose two ends have code 3"""
+    seq_u, off_u, nk, cs, ends = t.unitigs(min_cnt)
+    lens = np.sort(np.diff(off_u).astype(np.int64))[::-1]
+    n50 = int(lens[np.searchsorted(np.cumsum(lens), (int(lens.sum()) + 1) // 2)]) if len(lens) else 0
+    text = "%d unitigs over %d nodes, N50 %d bases" % (len(nk), int(nk.sum()), n50)
+    if arms:
+        text += ", %d with ends (3, 3)" % int(((ends & 63) == (3 | 3 << 3)).sum())
+    return text, int(nk.sum()), t.last_ms()
+
+
+def _clean3(call):
+    """call() -> (table, stats), three runs: (kernel ms, wall ms, the last run's table -- the caller closes it --, its stats)"""
+    ms, wall = [], []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        res, stats = call()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        ms.append(res.last_ms())
+        if rep < 2:
+            res.close()
+    return ms, " ".join("%.1f" % v for v in wall), res, stats
+
+
 def clip_rates(min_cnt=1):
-    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
     print("build %s" % bfc_amd._lib.build_id())
-
-    def shape(t):
-        seq_u, off_u, nk, cs, ends = t.unitigs(min_cnt)
-        lens = np.sort(np.diff(off_u).astype(np.int64))[::-1]
-        n50 = int(lens[np.searchsorted(np.cumsum(lens), (int(lens.sum()) + 1) // 2)]) if len(lens) else 0
-        return "%d unitigs over %d nodes, N50 %d bases" % (len(nk), int(nk.sum()), n50), int(nk.sum()), t.last_ms()
-
     ums = []
     for rep in range(3):
-        text, nodes, ms = shape(km)
+        text, nodes, ms = _shape(km, min_cnt)
         ums.append(ms)
-    print("unitigs (min_cnt %d), the call that writes, 3 runs (ms): %s; %s" % (min_cnt, f(ums), text))
+    print("unitigs (min_cnt %d), the call that writes, 3 runs (ms): %s; %s" % (min_cnt, _ms3(ums), text))
     for islands in (False, True):
-        cms, wall = [], []
-        for rep in range(3):
-            t0 = time.perf_counter()
-            res, stats = km.clip(min_cnt=min_cnt, islands=islands)
-            wall.append((time.perf_counter() - t0) * 1e3)
-            cms.append(res.last_ms())
-            if rep < 2:
-                res.close()
+        cms, wall, res, stats = _clean3(lambda: km.clip(min_cnt=min_cnt, islands=islands))
         best = min(cms)
-        print("clip (min_cnt %d, max_tip %d, max_mean 255, islands %d, at most 8 rounds), all kernels, 3 runs (ms): %s; wall: %s"
-              % (min_cnt, 2 * km.k, islands, f(cms), " ".join("%.1f" % v for v in wall)))
+        print("clip (min_cnt %d, max_tip %d, max_mean 255, islands %d, at most 8 rounds), all kernels, 3 runs (ms): %s; wall: %s" % (min_cnt, 2 * km.k, islands, _ms3(cms), wall))
         print("clip rounds (unitigs removed, k-mers removed, keys left): %s" % " ".join("(%d, %d, %d)" % tuple(int(v) for v in r) for r in stats))
         print("clip best: %.3f ms = %.2f G k-mers of the input per second = %.2f x unitigs (%.3f ms); result 2^%d sub-tables of 2^%d slots; %s"
-              % (best, nodes / best / 1e6, best / min(ums), min(ums), res.l_pre, res.cshift, shape(res)[0]))
+              % (best, nodes / best / 1e6, best / min(ums), min(ums), res.l_pre, res.cshift, _shape(res, min_cnt)[0]))
         res.close()
 
 
 def pop_rates(min_cnt=1):
-    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
     print("build %s" % bfc_amd._lib.build_id())
-
-    def shape(t):
-        seq_u, off_u, nk, cs, ends = t.unitigs(min_cnt)
-        lens = np.sort(np.diff(off_u).astype(np.int64))[::-1]
-        n50 = int(lens[np.searchsorted(np.cumsum(lens), (int(lens.sum()) + 1) // 2)]) if len(lens) else 0
-        arms = int(((ends & 63) == (3 | 3 << 3)).sum())
-        return "%d unitigs over %d nodes, N50 %d bases, %d with ends (3, 3)" % (len(nk), int(nk.sum()), n50, arms), int(nk.sum())
-
-    text, nodes = shape(km)
+    text, nodes, _ = _shape(km, min_cnt, True)
     print("input (min_cnt %d): %s" % (min_cnt, text))
-    cms = []
-    for rep in range(3):
-        res, stats = km.clip(min_cnt=min_cnt)
-        cms.append(res.last_ms())
-        res.close()
-    print("clip (max_tip %d, max_mean 255, at most 8 rounds), all kernels, 3 runs (ms): %s; %d rounds" % (2 * km.k, f(cms), len(stats)))
+    cms, _, res, stats = _clean3(lambda: km.clip(min_cnt=min_cnt))
+    res.close()
+    print("clip (max_tip %d, max_mean 255, at most 8 rounds), all kernels, 3 runs (ms): %s; %d rounds" % (2 * km.k, _ms3(cms), len(stats)))
     for max_diff in (0, 2):
-        pms, wall = [], []
-        for rep in range(3):
-            t0 = time.perf_counter()
-            res, stats = km.pop_bubbles(min_cnt=min_cnt, max_diff=max_diff)
-            wall.append((time.perf_counter() - t0) * 1e3)
-            pms.append(res.last_ms())
-            if rep < 2:
-                res.close()
+        pms, wall, res, stats = _clean3(lambda: km.pop_bubbles(min_cnt=min_cnt, max_diff=max_diff))
         best = min(pms)
-        print("pop_bubbles (min_cnt %d, max_arm %d, max_diff %d, max_mean 255, at most 8 rounds), all kernels, 3 runs (ms): %s; wall: %s"
-              % (min_cnt, 2 * km.k, max_diff, f(pms), " ".join("%.1f" % v for v in wall)))
+        print("pop_bubbles (min_cnt %d, max_arm %d, max_diff %d, max_mean 255, at most 8 rounds), all kernels, 3 runs (ms): %s; wall: %s" % (min_cnt, 2 * km.k, max_diff, _ms3(pms), wall))
         print("pop rounds (bubbles popped, k-mers removed, keys left): %s" % " ".join("(%d, %d, %d)" % tuple(int(v) for v in r) for r in stats))
         print("pop best: %.3f ms = %.2f G k-mers of the input per second = %.2f x clip (%.3f ms); result 2^%d sub-tables of 2^%d slots; %s"
-              % (best, nodes / best / 1e6, best / min(cms), min(cms), res.l_pre, res.cshift, shape(res)[0]))
+              % (best, nodes / best / 1e6, best / min(cms), min(cms), res.l_pre, res.cshift, _shape(res, min_cnt, True)[0]))
         if max_diff == 0:
             dev_stats, dev_keys = stats, len(res.list(1)[1])
         res.close()
