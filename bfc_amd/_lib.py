@@ -192,6 +192,14 @@ SYMBOLS = {
     "bfcg_seen_flags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
 }
 
+# csrc/bfc_host.h, internal: the host table's slots as they lie (HostTable.from_slots / raw)
+HOST_SYMBOLS = {
+    "bfc_ch_alloc_raw": (C.c_void_p, [C.c_int, C.c_int, C.c_int]),
+    "bfc_ch_raw_slots": (u64p, [C.c_void_p]),
+    "bfc_ch_raw_cshift": (C.c_int, [C.c_void_p]),
+    "bfc_ch_raw_recount": (None, [C.c_void_p]),
+}
+
 _lib = None
 
 
@@ -202,7 +210,7 @@ def load():
         if not os.path.exists(SO):
             raise OSError("libbfc_gpu.so is not built (run `python -m bfc_amd.build`); there is no fallback path")
         L = C.CDLL(SO)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(HOST_SYMBOLS.items()):
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args

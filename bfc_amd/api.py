@@ -305,6 +305,29 @@ class HostTable:
         return HostTable(_lib.load().bfc_ch_init(k, l_pre))
 
     @staticmethod
+    def from_slots(k, l_pre, cshift, slots):
+        """A table whose slots the caller wrote: `slots` u64 of 2^(l_pre + cshift) entries, sub-table s in [s << cshift, (s + 1) << cshift),
+        copied in as they lie and then counted.  Nothing is checked beyond the length: a key that linear probing from its home slot
+        does not reach is simply not found.  cshift >= 1: nothing in the library makes a table of one slot per sub-table."""
+        k, l_pre, cshift = int(k), int(l_pre), int(cshift)
+        slots = np.ascontiguousarray(slots, dtype=np.uint64).reshape(-1)
+        if not 1 <= k <= 63 or l_pre < 0 or cshift < 1 or l_pre + cshift > 40:
+            raise BfcGpuError("from_slots: k=%d l_pre=%d cshift=%d is no table geometry (k in [1, 63], cshift >= 1)" % (k, l_pre, cshift))
+        if len(slots) != 1 << (l_pre + cshift):
+            raise BfcGpuError("from_slots: %d slots given, l_pre=%d and cshift=%d make %d" % (len(slots), l_pre, cshift, 1 << (l_pre + cshift)))
+        L = _lib.load()
+        t = HostTable(L.bfc_ch_alloc_raw(k, l_pre, cshift))
+        C.memmove(L.bfc_ch_raw_slots(t.ptr), slots.ctypes.data, slots.nbytes)
+        L.bfc_ch_raw_recount(t.ptr)
+        return t
+
+    def raw(self):
+        """(cshift, a copy of the 2^(l_pre + cshift) slots as they lie)."""
+        cshift = self.L.bfc_ch_raw_cshift(self.ptr)
+        n = 1 << (self.l_pre + cshift)
+        return cshift, np.ctypeslib.as_array(self.L.bfc_ch_raw_slots(self.ptr), shape=(n,)).copy()
+
+    @staticmethod
     def restore(fn):
         p = _lib.load().bfc_ch_restore(fn.encode())
         return HostTable(p) if p else None
