@@ -119,6 +119,9 @@ SYMBOLS = {
     "bfcg_stats": (C.c_int, [C.c_void_p, u64p]),
     "bfcg_progress": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.c_int]),
     "bfcg_partition_info": (C.c_int, [C.c_void_p, u64p]),
+    "bfcg_seg_place": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p]),
+    "bfcg_commit_info": (C.c_int, [C.c_void_p, u64p]),
+    "bfcg_seg_id_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
     "bfcg_s1wc_launches": (C.c_uint64, []),
     "bfcg_table_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "bfcg_last_batch_ms": (C.c_int, [C.c_void_p, f32p]),

@@ -510,6 +510,25 @@ class GpuCounter:
         self.L.bfcg_table_info(self.ctx, out)
         return dict(segments=bool(out[0]), seg_shift=out[1], tab_cshift=out[2], seg_growths=out[3])
 
+    def seg_place(self, y0, y1):
+        """Where this context's geometry puts the k-mer with table hash (y0, y1): (region, identity in the region, home, block)."""
+        out = (C.c_uint64 * 4)()
+        self.L.bfcg_seg_place(self.ctx, int(y0), int(y1), out)
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def commit_info(self):
+        """What the table's write path has done since the context was created; complete after sync()."""
+        out = (C.c_uint64 * 8)()
+        self.L.bfcg_commit_info(self.ctx, out)
+        return dict(seg_replayed=int(out[0]), table_replayed=int(out[1]), commits=int(out[2]), max_commit_pages=int(out[3]), to_host_layout=int(out[4]))
+
+    def progress(self, n=63):
+        """(calls made, last call known complete, [distinct keys after call final, final - 1, ...]) without draining the pipeline."""
+        calls, final = C.c_uint64(), C.c_uint64()
+        keys = (C.c_uint64 * 63)()
+        self.L.bfcg_progress(self.ctx, C.byref(calls), C.byref(final), keys, min(n, 63))
+        return int(calls.value), int(final.value), [int(keys[i]) for i in range(min(n, 63, int(final.value)))]
+
     def partition_info(self):
         out = (C.c_uint64 * 2)()
         self.L.bfcg_partition_info(self.ctx, out)

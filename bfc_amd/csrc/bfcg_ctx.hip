@@ -14,6 +14,7 @@
 #include "bfc_gpu.h"
 #include "bfcg_internal.h"
 #include "bfc_host.h"
+#include "kmer_dev.h" // (seg_id, seg_home on the host: bfcg_seg_place)
 
 using namespace bfcg;
 
@@ -86,7 +87,7 @@ struct bfcg_ctx {
 	uint32_t *h_rows[2]; int rows_slot; // a group's slab mode without the host's wait: the host's copy of a stage A's rows (mg_scatter_slabs_async), the slot of the last one
 	uint32_t op_cap; uint64_t op_min_pos;
 	uint32_t *cnt2; uint32_t cap2; uint64_t recs2_n; // one-pass level 2 (region slabs); records recs2 / stream_out hold
-	struct opq_t { const uint8_t *seq, *qual; uint64_t n_pos; int slot; const void *recv; int mg; } opq[4]; int n_opq; // batches enqueued one-pass and not yet known to be clean
+	struct opq_t { const uint8_t *seq, *qual; uint64_t n_pos; int slot; const void *recv; int mg; uint64_t call; } opq[4]; int n_opq; // batches enqueued one-pass and not yet known to be clean
 	int mg_op2_ok, mg_op2, mg_op2_allowed; uint32_t *mg_seg[4];  // a rank of a multi-GPU run: level 2 (its own stage B) in one pass; copies of the queued batches' segment sizes
 	int mg_slab_ok; int mg_seg_slab[4]; // ... level 1 in one pass into per-destination slabs (mg_scatter_slabs); which queued copies are slab fills
 	uint64_t n_replayed;
@@ -103,6 +104,8 @@ struct bfcg_ctx {
 	uint64_t keys_known;                // distinct keys after the last absorbed commit
 	int commit_absorbed;                // a commit's key counts have arrived since the last growth forecast
 	uint64_t keys_per_batch; int n_commits, ho_window; // most keys one batch created in the last absorbed commit; commits absorbed since the reset; pages the current window takes
+	uint64_t n_seg_replayed, n_tab_replayed; // parked k-mers handed to k_seg_replay / k_table_replay since creation (bfcg_commit_info)
+	uint64_t n_log_commits, max_commit_pages, n_to_legacy; // commits of the hand-over log absorbed, the pages of the largest one, conversions to the host's layout
 	unsigned long long *seg_spare; int seg_spare_shift; // the buffer the last growth left behind (kept up to 16 GiB): growth rehashes from one into the other,
 	                             // so a context that counts one data set after the other stops calling hipMalloc / hipFree (tens of ms per multi-GiB call)
 };
@@ -635,7 +638,11 @@ static int drain(bfcg_ctx_t *c)
 	c->final_call = c->call_no; c->call_keys[c->call_no & 63] = c->h_stats[ST_KEYS];
 	c->pos_final += c->slot_pos[0] + c->slot_pos[1]; c->slot_pos[0] = c->slot_pos[1] = 0;
 	note_growth(c);
-	return check_health(c);
+	if (check_health(c) != 0) return -1;
+	// a replay of parked k-mers (seg_maintain / table_maintain, seg_to_legacy) creates keys that no page of the log counted: they belong to the call
+	// drained at, and the next window's pages count on from the table's state, not from the figure taken before the replay
+	if (c->h_stats[ST_KEYS] != c->keys_known) { c->keys_known = c->h_stats[ST_KEYS]; c->call_keys[c->call_no & 63] = c->h_stats[ST_KEYS]; }
+	return 0;
 }
 
 extern "C" int bfcg_sync(bfcg_ctx_t *c) { return drain(c); }
@@ -658,6 +665,7 @@ static int replay_poisoned(bfcg_ctx_t *c)
 	if (fetch_stats(c) != 0) return -1;
 	c->n_batches -= (uint64_t)n; // the batches keep their places in the count (order stamps carry the batch number)
 	std::vector<uint32_t> seg;
+	const uint64_t calls = c->call_no; // (a single GPU's replayed batches take their own calls' numbers again, below)
 	for (int i = 0; i < n; ++i) if (q[i].mg) --c->call_no; // (mg_process numbers its calls itself)
 	for (int i = 0; i < n; ++i) {
 		if (q[i].mg) { // a rank's stage B: what it received is still in its receive buffer (the exchange of the next batch has not begun: this thread starts it)
@@ -665,10 +673,14 @@ static int replay_poisoned(bfcg_ctx_t *c)
 			const size_t w = (size_t)c->n_ranks * (size_t)((1 << c->P.F1) >> c->log2n) * (slab ? 8 : 1);
 			seg.assign(c->mg_seg[q[i].mg - 1], c->mg_seg[q[i].mg - 1] + w);
 			if (mg_process(c, q[i].recv, seg.data(), slab ? c->op_cap : 0u, 0, 0) != 0) return -1;
-		} else if (enqueue_batch(c, q[i].seq, q[i].qual, q[i].n_pos, 0, 1) != 0) return -1;
+		} else {
+			c->call_no = q[i].call; // the batch belongs to the call that brought it, not to the one that found it poisoned: its keys are that call's (bfcg_progress)
+			if (enqueue_batch(c, q[i].seq, q[i].qual, q[i].n_pos, 0, 1) != 0) return -1;
+		}
 		if (drain(c) != 0) return -1;
 		++c->n_replayed;
 	}
+	if (c->call_no < calls) c->call_no = calls;
 	return 0;
 }
 
@@ -748,6 +760,7 @@ static int table_maintain(bfcg_ctx_t *c)
 			BFCG_CK(hipMemcpyAsync(tmp, B.tab_ovf, ovf * 40, hipMemcpyDeviceToDevice, c->st));
 			BFCG_CK(hipMemsetAsync(&B.stats[(size_t)ST_SLOTS * ST_N], 0, 8, c->st));
 			run_table_replay(P, B.table, tmp, ovf, B.stats, B.tab_ovf, B.tab_ovf_cap, B.tab_first, B.sub_last, c->st);
+			c->n_tab_replayed += ovf;
 			if (fetch_stats(c) != 0) return -1;
 			BFCG_CK(hipFree(tmp));
 		} else c->h_stats[ST_TAB_OVF] = 0;
@@ -829,6 +842,7 @@ static int seg_maintain(bfcg_ctx_t *c)
 			BFCG_CK(hipMemcpyAsync(tmp, B.tab_ovf, ovf * 40, hipMemcpyDeviceToDevice, c->st));
 			BFCG_CK(hipMemsetAsync(&B.stats[(size_t)ST_SLOTS * ST_N], 0, 8, c->st));
 			run_seg_replay(P, B.seg_tab, tmp, ovf, B.stats, B.tab_ovf, B.tab_ovf_cap, c->st);
+			c->n_seg_replayed += ovf;
 			if (fetch_stats(c) != 0) return -1;
 			BFCG_CK(hipFree(tmp));
 		} else c->h_stats[ST_TAB_OVF] = 0;
@@ -868,7 +882,7 @@ static int seg_to_legacy(bfcg_ctx_t *c, int for_export)
 	BFCG_CK(hipGetLastError());
 	BFCG_CK(hipFree(B.seg_tab));
 	B.seg_tab = 0;
-	P.seg = 0; P.b3 = 0; c->seg_escaped = 1;
+	P.seg = 0; P.b3 = 0; c->seg_escaped = 1; ++c->n_to_legacy;
 	BFCG_CK(set_bloom_lds_attr(P)); // the aggregation table is back in the bloom kernel's LDS footprint
 	if (fetch_stats(c) != 0) return -1;
 	c->keys_last = c->h_stats[ST_KEYS];
@@ -882,6 +896,43 @@ extern "C" int bfcg_partition_info(bfcg_ctx_t *c, uint64_t out[2]) { out[0] = (u
 // A rank's stage B may partition what it received in one pass only if the caller keeps every receive buffer unchanged until the call after the
 // next has returned (a slab overflow is found one call later and replayed from the buffer): bfcg_group_* alternates its buffers and says so here.
 extern "C" void bfcg_mg_allow_onepass(bfcg_ctx_t *c, int on) { c->mg_op2_allowed = on != 0; }
+
+// Where the context's own geometry puts the k-mer with table hash (y0, y1): out[0] its bloom region (fine_id, bfcg_kernels.hip, on the host),
+// out[1] its identity inside the region (seg_id), out[2] seg_home of that, out[3] the block of a segment of the current size that holds it
+// (0 in the host's layout).  The home slot inside the block is out[2] & (2^seg_blk - 1).  Read-only; for tests that place k-mers.
+extern "C" int bfcg_seg_place(bfcg_ctx_t *c, uint64_t y0, uint64_t y1, uint64_t out[4])
+{
+	const KParams &P = c->P;
+	const uint64_t m = P.k >= 64 ? ~0ULL : (1ULL << P.k) - 1;
+	const uint64_t h0 = (y0 - y1) & m, hash = ((h0 ^ y1) << P.k) | y0; // bloom_hash (kmer_dev.h)
+	SegGeom G; G.k = P.k; G.lo = P.seg_lo; G.hi = P.seg_hi;
+	out[0] = (hash & ((1ULL << (P.bf_shift - 9)) - 1)) >> P.R;
+	out[1] = seg_id(G, y0 & m, y1 & m);
+	out[2] = seg_home(out[1]);
+	out[3] = P.seg ? (out[2] >> P.seg_blk) & ((1ULL << (P.seg_shift - P.seg_blk)) - 1) : 0;
+	return 0;
+}
+
+// seg_id / seg_home / seg_unpack (kmer_dev.h) as the host compiles them, without a context: out[0] the identity of (y0, y1) for the implied bit
+// field [lo, hi) of y0, out[1] its home, out[2], out[3] the hash that seg_unpack makes of region and identity again
+extern "C" int bfcg_seg_id_host(int k, int lo, int hi, uint64_t region, uint64_t y0, uint64_t y1, uint64_t out[4])
+{
+	if (k < 1 || k > 63 || lo < 0 || hi < lo || hi > k) return -1;
+	SegGeom G; G.k = k; G.lo = lo; G.hi = hi;
+	out[0] = seg_id(G, y0, y1); out[1] = seg_home(out[0]);
+	seg_unpack(G, region, out[0], out[2], out[3]);
+	return 0;
+}
+
+// What the write path of the count table has done since the context was created (no reset clears these): out[0] parked k-mers replayed into
+// segments, out[1] parked k-mers replayed into the host's layout, out[2] commits of the hand-over log, out[3] the pages of the largest of
+// them, out[4] conversions of the segments to the host's layout; out[5..7] are zero.  Complete once the pipeline is drained (bfcg_sync).
+extern "C" int bfcg_commit_info(bfcg_ctx_t *c, uint64_t out[8])
+{
+	memset(out, 0, 8 * sizeof(uint64_t));
+	out[0] = c->n_seg_replayed; out[1] = c->n_tab_replayed; out[2] = c->n_log_commits; out[3] = c->max_commit_pages; out[4] = c->n_to_legacy;
+	return 0;
+}
 
 extern "C" int bfcg_table_info(bfcg_ctx_t *c, int out[4])
 {
@@ -944,7 +995,7 @@ static int opq_push(bfcg_ctx_t *c, int b, const StageB &w)
 		if (w.sizes) memcpy(c->mg_seg[mg], w.sizes, sizeof(uint32_t) * words); else memset(c->mg_seg[mg], 0, sizeof(uint32_t) * words);
 		c->mg_seg_slab[mg++] = w.sizes_slab;
 	}
-	c->opq[c->n_opq++] = bfcg_ctx::opq_t{w.seq, w.qual, w.pos, b, w.recv, mg};
+	c->opq[c->n_opq++] = bfcg_ctx::opq_t{w.seq, w.qual, w.pos, b, w.recv, mg, w.call};
 	return 0;
 }
 
@@ -1324,6 +1375,7 @@ static void absorb_pages(bfcg_ctx_t *c, int b)
 		c->call_keys[c->slot_page_call[b][j] & 63] = run;
 	}
 	c->keys_per_batch = most; ++c->n_commits;
+	++c->n_log_commits; if ((uint64_t)J > c->max_commit_pages) c->max_commit_pages = (uint64_t)J;
 	c->final_call = c->slot_page_call[b][J - 1];
 	c->keys_known = run;
 	c->slot_commit[b] = 0;
@@ -1601,8 +1653,9 @@ extern "C" int bfcg_d2h(bfcg_ctx_t *c, void *dst, const void *src, uint64_t byte
 { BFCG_CK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stC)); BFCG_CK(hipStreamSynchronize(c->stC)); return 0; }
 
 // Progress WITHOUT draining the pipeline: calls = bfcg_count_batch_* calls made so far (numbered from 1 after a reset), final = the last
-// call all of whose batches are known to be complete, keys_of[final - i], i < n: distinct keys after call final - i (exact: stage B alone
-// creates keys, and its counters are copied out right behind it).  bfc_count prints the reference's progress lines from this.
+// call all of whose batches are known to be complete, keys_of[final - i], i < n: distinct keys after call final - i (stage B alone creates
+// keys, and its counters are copied out right behind it: exact while nothing is parked; keys that a replay of parked k-mers creates count
+// at the call drained at, see drain()).  bfc_count prints the reference's progress lines from this.
 extern "C" int bfcg_progress(bfcg_ctx_t *c, uint64_t *calls, uint64_t *final, uint64_t *keys_of, int n)
 {
 	// a call is complete when a batch of a LATER call has been finalised, or when nothing is in flight

@@ -212,12 +212,25 @@ void  bfcg_host_free(void *p);
 
 int bfcg_stats(bfcg_ctx_t *c, uint64_t out[BFCG_ST_N]);   /* drains the pipeline first */
 /* progress without draining: *calls = bfcg_count_batch_* calls since the last reset, *final = the last of them whose batches are all
- * complete, keys_of[i] (i < n) = distinct keys in the table after call *final - i.  Exact, because the table's counters are copied out
- * right behind every batch's table stage (count.c:113 prints the count after every chunk; bfc_count prints it from here). */
+ * complete, keys_of[i] (i < n) = distinct keys in the table after call *final - i: the table's counters are copied out right behind every
+ * batch's table stage (count.c:113 prints the count after every chunk; bfc_count prints it from here).  Exact as long as no k-mer is
+ * parked (a full segment or sub-table).  The keys that the replay of parked k-mers creates are counted at the call the context drains at:
+ * a call whose k-mers parked and the calls up to that one lack them, the calls from that one on are exact again. */
 int bfcg_progress(bfcg_ctx_t *c, uint64_t *calls, uint64_t *final, uint64_t *keys_of, int n);
 /* how the count table is held right now: out[0] 1 = region-owned segments, 0 = the host's layout; out[1] log2 slots per segment;
  * out[2] log2 slots per sub-table; out[3] segment growths so far */
 int bfcg_table_info(bfcg_ctx_t *c, int out[4]);
+/* where the context's geometry puts the k-mer with table hash (y0, y1), computed on the host by the functions the kernels use: out[0] its
+ * bloom region, out[1] its identity inside the region, out[2] the 26-bit home of that identity (the home slot is its low bits), out[3] the
+ * block of a segment of the current size that holds it (0 in the host's layout).  Read-only; for tests that place k-mers. */
+int bfcg_seg_place(bfcg_ctx_t *c, uint64_t y0, uint64_t y1, uint64_t out[4]);
+/* the same functions without a context (no GPU needed): out[0] the identity of (y0, y1) inside its region for the implied bit field [lo, hi) of
+ * y0, out[1] its home, out[2], out[3] the hash rebuilt from (region, identity); -1 for a geometry that cannot be */
+int bfcg_seg_id_host(int k, int lo, int hi, uint64_t region, uint64_t y0, uint64_t y1, uint64_t out[4]);
+/* what the table's write path has done since the context was created (a reset clears nothing): out[0] parked k-mers replayed into segments,
+ * out[1] parked k-mers replayed into the host's layout, out[2] commits of the hand-over log, out[3] pages of the largest of them,
+ * out[4] conversions of the segments to the host's layout, out[5..7] zero.  Complete once the pipeline is drained (bfcg_sync). */
+int bfcg_commit_info(bfcg_ctx_t *c, uint64_t out[8]);
 /* how the k-mers are partitioned: out[0] bit 0 = the one-pass level-1 partition (the k-mer hash is computed once per batch, no histogram pass) is in
  * use, bit 1 = level 2 runs in one pass too (a slab per bloom region, no k_hist2); out[1] batches that had to be replayed through the two-pass
  * partition so far (input with few, often repeated k-mers overflows a one-pass slab) */
