@@ -55,14 +55,50 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 	__shared__ uint32_t s_list_n, s_ovf, s_pool_off, s_emit_n, s_fs_used, s_wb_n, s_pad3[2];
 	const uint32_t f = blockIdx.x;
 	const bool ho_log = A.ho_stride != 0;
-	if (batch_poisoned(A)) { if (ho_log && threadIdx.x == 0) A.ho_mark[f] = A.ho_cur[f]; return; } // (an empty page: the batch will be replayed)
+#ifdef BFCG_MEASURE
+	const long long t_start = clock64();
+#endif
+	// EAGER (A.eager, wave-uniform; bfcg_ctx.hip: enqueue_stage_b sets it where empty regions are rare): everything the workgroup will wait for is
+	// requested by its first instructions, with no branch on a loaded value in between -- the region's slice into registers (its address depends on
+	// blockIdx.x alone; 2^R <= 256 blocks: at most two 16-byte pieces per thread), the five words the exits below test (sticky, flags[0], flags[2],
+	// the region's count, its log cursor; an absent one is read from the counters' block, which always exists, and ignored), and from a one-pass slab
+	// (cap2 != 0: rs = f * cap2 needs no load) the first round of records, bounded by the slab's capacity instead of the count.  Without it these
+	// were a chain of dependent round trips to memory -- the count comes from memory-side atomics -- before a single bulk byte was on its way.
+	// Every such address lies inside its allocation by construction; nothing is stored before the exits, so an exit only drops the loads.
+	const bool eager = A.eager != 0, spec = eager && A.cap2 != 0;
+	constexpr int B3_SL = 1024 / BT; // 16-byte pieces of the largest slice (R = 8: 16 KiB) per thread
+	uint4 sl[B3_SL];
+	uint32_t e_st = 0, e_f0 = 0, e_f2 = 0, e_c = 0, e_s = 0, e_h = 0;
+	RecW<3> cur[PF], nxt[PF];
+#pragma unroll
+	for (int u = 0; u < PF; ++u) { cur[u].d[0] = cur[u].d[1] = cur[u].d[2] = 0; nxt[u] = cur[u]; }
+#pragma unroll
+	for (int j = 0; j < B3_SL; ++j) sl[j] = make_uint4(0, 0, 0, 0);
+	if (eager) {
+		const uint4 *src = reinterpret_cast<const uint4 *>(reinterpret_cast<const unsigned int *>(A.bloom) + (uint64_t)f * (16u << P.R));
+#pragma unroll
+		for (int j = 0; j < B3_SL; ++j) if ((uint32_t)(threadIdx.x + j * BT) < (4u << P.R)) sl[j] = src[threadIdx.x + j * BT];
+		const uint32_t *const any = reinterpret_cast<const uint32_t *>(A.stats);
+		const uint32_t *const p_st = A.sticky ? A.sticky : any, *const p_fl = A.flags ? A.flags : any;
+		const uint32_t *const p_c = A.cnt2 ? A.cnt2 + f : A.start + f + 1, *const p_s = A.cap2 ? any : A.start + f, *const p_h = ho_log ? A.ho_cur + f : any;
+		e_st = *p_st; e_f0 = p_fl[0]; e_f2 = p_fl[2]; e_c = *p_c; e_s = *p_s; e_h = *p_h;
+		if (spec) {
+			const uint32_t *r0 = A.recs + (uint64_t)(f * A.cap2) * 3;
+#pragma unroll
+			for (int u = 0; u < PF; ++u) { const uint32_t i = threadIdx.x + u * BT; if (i < A.cap2) cur[u] = rec_load<3>(r0 + (uint64_t)i * 3); }
+		}
+	}
+	const bool poisoned = eager ? (((A.sticky ? e_st : 0u) | (A.flags ? e_f0 | e_f2 : 0u)) != 0u) : batch_poisoned(A);
+	if (poisoned) { if (ho_log && threadIdx.x == 0) A.ho_mark[f] = A.ho_cur[f]; return; } // (an empty page: the batch will be replayed)
 	uint32_t rs, n;
-	region_list(A, f, rs, n);
+	if (!eager) region_list(A, f, rs, n);
+	else if (A.cap2) { rs = f * A.cap2; n = e_c < A.cap2 ? e_c : A.cap2; } // (region_list on the words already here)
+	else { rs = e_s; n = A.cnt2 ? e_c : e_c - e_s; }
 	if (n == 0) { if (threadIdx.x == 0) { if (ho_log) A.ho_mark[f] = A.ho_cur[f]; else if (A.agg_cnt) A.agg_cnt[f] = 0; } return; }
 	uint32_t ho_cur0 = 0;
 	unsigned long long *ho_base;
 	if (ho_log) {
-		ho_cur0 = A.ho_cur[f];
+		ho_cur0 = eager ? e_h : A.ho_cur[f];
 		if (ho_cur0 + n > A.ho_stride) { // (the host commits before a log can fill up: a bug if it ever happens -- loudly, not silently)
 			if (threadIdx.x == 0) { atomicAdd(&A.stats[(size_t)(f & (ST_SLOTS - 1)) * ST_N + ST_ERR_POOL], 1ULL); A.ho_mark[f] = ho_cur0; }
 			return;
@@ -93,7 +129,7 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 	const bool timing = BFCG_ABL(P, 64) && tid == 0;
 	long long tq[7] = {0, 0, 0, 0, 0, 0, 0};
 	long long tc[7] = {0, 0, 0, 0, 0, 0, 0}; // COLD, BFCG_ABLATE & 128: the ordering's sub-steps (scan, scatter, rank, reorder, walk, emit)
-	if (timing) tq[0] = clock64();
+	if (timing) tq[0] = t_start; // (`stage` runs from the workgroup's first instruction: the counters' round trips are part of it)
 #define B3_TC(i) do { if (timing) tc[i] = clock64(); } while (0)
 #else
 #define B3_TC(i) do { } while (0)
@@ -115,18 +151,23 @@ __global__ __launch_bounds__(BT, PF <= 2 ? 8 : 6) void k_bloom3(KParams P, Bloom
 		const unsigned long long id = (unsigned long long)((y0d & D.rmask) | ((y0d >> D.up) << D.R)) | (y1 << D.sh_y1);
 		return (id << 1) | (unsigned long long)((d1 >> D.sh_flag) & 1u);
 	};
-	RecW<3> cur[PF], nxt[PF];
 #pragma unroll
-	for (int u = 0; u < PF; ++u) {
+	for (int u = 0; u < PF; ++u) { // (lanes beyond the region's records compute on zeros)
 		const uint32_t i = tid + u * BT;
-		cur[u].d[0] = cur[u].d[1] = cur[u].d[2] = 0; nxt[u] = cur[u]; // (lanes beyond the region's records compute on zeros)
-		if (i < n) cur[u] = rec_load<3>(recs + (uint64_t)i * 3);
+		if (!spec && i < n) cur[u] = rec_load<3>(recs + (uint64_t)i * 3);
 		if (i + BT * PF < n) nxt[u] = rec_load<3>(recs + (uint64_t)(i + BT * PF) * 3);
+	}
+	if (spec) { // ... also where the first round was requested before the count was known: what lies beyond the region's records is dropped
+#pragma unroll
+		for (int u = 0; u < PF; ++u) if ((uint32_t)(tid + u * BT) >= n) cur[u].d[0] = cur[u].d[1] = cur[u].d[2] = 0;
 	}
 	{ // stage the region (16-byte loads), clear the first-setter table
 		const uint4 *src = reinterpret_cast<const uint4 *>(g_region);
 		uint4 *dst = reinterpret_cast<uint4 *>(region);
-		for (uint32_t i = tid; i < region_dw / 4; i += BT) dst[i] = src[i];
+		if (eager) {
+#pragma unroll
+			for (int j = 0; j < B3_SL; ++j) if ((uint32_t)(tid + j * BT) < region_dw / 4) dst[tid + j * BT] = sl[j];
+		} else for (uint32_t i = tid; i < region_dw / 4; i += BT) dst[i] = src[i];
 		if constexpr (COLD) { for (uint32_t i = tid; i < 2 * nblk + 4; i += BT) bcnt[i] = 0; }
 		else {
 			uint4 *f4 = reinterpret_cast<uint4 *>(fs);

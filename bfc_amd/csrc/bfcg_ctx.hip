@@ -86,6 +86,7 @@ struct bfcg_ctx {
 	int unfinished, unfinished_mg;     // mg_process_slabs_dev has enqueued a stage B that mg_process_finish has not seen yet (and its entry in the replay queue)
 	uint32_t *h_rows[2]; int rows_slot; // a group's slab mode without the host's wait: the host's copy of a stage A's rows (mg_scatter_slabs_async), the slot of the last one
 	uint32_t op_cap; uint64_t op_min_pos;
+	int eager;                   // k_bloom3's eager prologue (BloomArgs.eager): -1 by the batch's size (enqueue_stage_b), 0 / 1: what BFCG_EAGER says (tests, A/B)
 	uint32_t *cnt2; uint32_t cap2; uint64_t recs2_n; // one-pass level 2 (region slabs); records recs2 / stream_out hold
 	struct opq_t { const uint8_t *seq, *qual; uint64_t n_pos; int slot; const void *recv; int mg; uint64_t call; } opq[4]; int n_opq; // batches enqueued one-pass and not yet known to be clean
 	int mg_op2_ok, mg_op2, mg_op2_allowed; uint32_t *mg_seg[4];  // a rank of a multi-GPU run: level 2 (its own stage B) in one pass; copies of the queued batches' segment sizes
@@ -289,6 +290,7 @@ extern "C" bfcg_ctx_t *bfcg_create(const bfcg_params_t *prm)
 	// the table streamed through LDS (k_commit_seg) it is neither (265.9 vs 269.0 ms): batches of half a billion positions keep the chip busy on
 	// their own, and under rocprofv3 the overlapped kernels stretch.  So: two streams for batches up to 2^28 positions.  BFCG_PIPELINE=0/1 overrides.
 	{ const char *e = getenv("BFCG_PIPELINE"); c->pipeline = e ? atoi(e) != 0 : prm->max_batch_pos <= (1ULL << 28); }
+	{ const char *e = getenv("BFCG_EAGER"); c->eager = e ? atoi(e) != 0 : -1; }
 
 	if (n_ranks > 1 && log2n > P.F1) { fail("multi-GPU needs a two-level partition with 2^F1=%d >= n_ranks (bf_shift=%d is too small)", 1 << P.F1, P.bf_shift); bfcg_destroy(c); return NULL; }
 	P.idx_rank = n_ranks > 1 ? (uint32_t)prm->rank << (32 - log2n) : 0u;
@@ -1005,6 +1007,15 @@ static int opq_push(bfcg_ctx_t *c, int b, const StageB &w)
 static int enqueue_stage_b(bfcg_ctx_t *c, int b, BatchBufs &Bt, const KParams &Pt, const StageB &w)
 {
 	if (handover_begin(c, Bt, b, w.slabs, w.call) != 0) return -1;
+	// k_bloom3's eager prologue requests a region's filter slice (and, from a one-pass slab, a round of records) before it knows that the region
+	// has records at all: an empty region then costs 16 KiB instead of one counter.  It is taken where empty regions are rare: with >= 16
+	// positions per region a region expects >= 12 records (a stream holds ~0.8 k-mers per position), so -- Poisson -- fewer than e^-12 < 10^-5
+	// of the regions are empty and the wasted bytes are below 10^-5 of the launch's.  A small batch in a context of 2^20 regions keeps the old
+	// order (eagerly it would sweep 16 GiB of filter for nothing).  BFCG_EAGER=0/1 (read at creation) overrides the rule.
+	// (A rank's w.pos is its rec_bound -- RECORDS it may have received, an upper bound and in slab mode the slabs' capacity, not positions: the
+	// same figure that decides its one-pass level 2 (mg_stage_b).  16 records per region is the stricter test where the bound is tight; where it
+	// lies far above the batch, a sparse batch may run eagerly: that costs the bytes argued above, never a result -- the flag changes no answer.)
+	Bt.eager = c->eager >= 0 ? c->eager : w.pos >= (uint64_t)16 * nfine(c);
 	run_stage_b(Pt, Bt, w.in1, w.seg_beg, w.seg_end, w.n_seg, w.segs_per_bucket, w.row_base, w.bucket_start, w.rec_bound, c->st, c->evt[b]);
 	if (handover_end(c, Bt, b) != 0) return -1;
 	if (w.queued) { // behind k_seal: is the run poisoned up to and including this batch?  (read with the batch's snapshot; an overflow is replayed: replay_poisoned)

@@ -98,6 +98,7 @@ struct BloomArgs {
 	unsigned long long *ho_keys;        // k_commit_seg: keys created by page j, slotted: ho_keys[j * ST_SLOTS + (f & (ST_SLOTS - 1))]
 	const uint32_t *flags;         // one-pass partition, this batch's slot: [0] a level-1 slab overflowed, [2] a region's slab (NULL: two-pass batch)
 	const uint32_t *sticky;        // an earlier batch of the run overflowed (written by k_seal on stage B's stream only)
+	uint32_t eager;                // k_bloom3: the region's slice, the counters and (cap2 != 0) a first round of records are requested together, before anything is decided
 };
 
 // where region f's records are

@@ -114,6 +114,7 @@ struct BatchBufs {
 	uint32_t *op_cursor, *op_flags, *op_sticky, *op_seg; uint32_t op_cap;
 	uint32_t op_own_lo, op_own_n, op_own_delta; // a rank of a multi-GPU group: the slabs of its OWN buckets lie op_own_delta records further on (bfcg_kernels.hip: OnePass)
 	uint32_t *cnt2; uint32_t cap2;            // one-pass level 2: a slab of cap2 records per bloom region in recs2 and its cursor (0: two passes, start2 says where)
+	int eager;                                // k_bloom3 requests a region's bulk inputs before its counters (BloomArgs.eager; bfcg_ctx.hip: enqueue_stage_b decides)
 	uint32_t *cnt_live;                       // two-pass level 2: the regions' record counts (k_scan2) -- start2 alone does not say them when the level-1 slabs hold dead records
 	// hand-over log of the region-owned table (bfcg_kernels.hip: BloomArgs): arena, entries per region (0: this batch's entries go to stream_out at
 	// its records' offsets and are applied at once), cursors, marks [pages][ho_mark_stride], the page this batch fills, whether stage B ends with

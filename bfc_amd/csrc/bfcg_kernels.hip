@@ -2320,6 +2320,7 @@ static BloomArgs run_bloom_t(const KParams &P, const BatchBufs &B, const uint32_
 	A.cnt2 = nullptr; A.cap2 = 0; A.flags = B.op_flags; A.sticky = B.op_sticky; // (op_flags: NULL unless this batch went through the one-pass partition)
 	if (P.F2 > 0 && B.cap2) { A.cnt2 = B.cnt2; A.cap2 = B.cap2; }
 	else if (P.F2 > 0 && B.cnt_live) A.cnt2 = B.cnt_live; // two passes: the regions' counts beside their starts (region_list)
+	A.eager = B.eager != 0;
 	const bool h4 = P.n_hashes == 4;
 	if (P.filter_mode && B.bloom_hi) { // both filters' slices in LDS, nothing to hand over
 		if (RW == 4 && P.b3fm) run_bloom3fm(P, A, nfine, (size_t)bloom_lds_bytes(P), st); // (bfcg_bloom3.hip)
