@@ -139,6 +139,23 @@ def _unitigs(L, fn, obj, min_cnt):
     return seq, off, nk, cs, ends
 
 
+def _unitig_graph(L, fn, obj, min_cnt):
+    """(seq, off, n_kmers, cnt_sum, ends as _unitigs gives them, links i64 (n, 2, 4)) of bfcg_kmers_unitig_graph / bfcg_unitig_graph_host
+    on `obj`: the sizing call with caps of 0, then the call that writes; the edges it counted are those it wrote"""
+    n = (C.c_uint64 * 3)()
+    rc = fn(obj, int(min_cnt), None, 0, None, None, None, None, None, 0, n)
+    if rc < 0:
+        raise BfcGpuError(L.bfcg_last_error().decode())
+    seq, off = np.zeros(n[1], dtype=np.uint8), np.zeros(n[0] + 1, dtype=np.uint64)
+    nk, cs, ends = np.zeros(n[0], dtype=np.uint32), np.zeros(n[0], dtype=np.uint64), np.zeros(n[0], dtype=np.uint8)
+    links = np.full((n[0], 2, 4), -1, dtype=np.int64)
+    if rc == 1 and fn(obj, int(min_cnt), seq.ctypes.data, len(seq), off.ctypes.data, nk.ctypes.data, cs.ctypes.data, ends.ctypes.data, links.ctypes.data, len(nk), n) != 0:
+        raise BfcGpuError(L.bfcg_last_error().decode() or "the table changed between the sizing call and the call that writes")
+    if rc == 1 and int(n[2]) != int((links >= 0).sum()):
+        raise BfcGpuError("the call counted %d links and wrote %d" % (n[2], (links >= 0).sum()))
+    return seq, off, nk, cs, ends, links
+
+
 def _clean(L, fn, obj, max_rounds, *rule):
     """(pointer to the new table, stats u64 (rounds, 3)) of a graph-cleaning call on `obj` -- bfcg_kmers_clip / bfcg_clip_host,
     bfcg_kmers_pop / bfcg_pop_host; `rule` = its arguments between the table and max_rounds"""
@@ -162,6 +179,15 @@ def unitig_rows(seq, off, n_kmers, cnt_sum, ends):
     s = np.asarray(seq, dtype=np.uint8).tobytes()
     return sorted((s[int(off[i]):int(off[i + 1])], int(n_kmers[i]), int(cnt_sum[i]), int(ends[i]) & 7, int(ends[i]) >> 3 & 7, int(ends[i]) >> 6 & 1)
                   for i in range(len(n_kmers)))
+
+
+def unitig_link_rows(seq, off, links):
+    """The links of unitig_graph() as a sorted list of (spelling of u, o, c, spelling of v, p): an edge from oriented unitig (u, o) -- o = 1
+    is the reverse complement of the emitted spelling -- by base c (A C G T = 0..3) to (v, p).  The spellings are the emitted ones."""
+    s = np.asarray(seq, dtype=np.uint8).tobytes()
+    name = [s[int(off[i]):int(off[i + 1])] for i in range(len(off) - 1)]
+    links = np.asarray(links, dtype=np.int64).reshape(-1, 2, 4)
+    return sorted((name[u], int(o), int(c), name[int(links[u, o, c]) >> 1], int(links[u, o, c]) & 1) for u, o, c in zip(*np.nonzero(links >= 0)))
 
 
 class HostTable:
@@ -267,6 +293,10 @@ class HostTable:
     def unitigs(self, min_cnt=1):
         """(seq u8, off u64 (n + 1), n_kmers u32, cnt_sum u64, ends u8): GpuKmers.unitigs's host twin (bfcg_unitigs_host)."""
         return _unitigs(self.L, self.L.bfcg_unitigs_host, self.ptr, min_cnt)
+
+    def unitig_graph(self, min_cnt=1):
+        """(seq, off, n_kmers, cnt_sum, ends, links i64 (n, 2, 4)): GpuKmers.unitig_graph's host twin (bfcg_unitig_graph_host)."""
+        return _unitig_graph(self.L, self.L.bfcg_unitig_graph_host, self.ptr, min_cnt)
 
     def clip(self, min_cnt=1, max_tip=None, max_mean=255, islands=False, max_rounds=8):
         """(HostTable, stats u64 (rounds, 3)): GpuKmers.clip's host twin (bfcg_clip_host)."""
@@ -1055,6 +1085,16 @@ class GpuKmers:
         self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
         return out
 
+    def unitig_graph(self, min_cnt=1):
+        """The compacted graph with its edges, out of one call (bfcg_kmers_unitig_graph; include/bfc_gpu.h defines oriented unitig and
+        edge): unitigs()'s five arrays and links i64 (n, 2, 4) -- links[u, o, c] = v << 1 | p for the edge from (u, o) by base c
+        (A C G T = 0..3) to (v, p), -1 where there is none; o, p = 1 mean the reverse complement of the emitted spelling; u and v index
+        these arrays (the order differs from call to call: unitig_link_rows() names the ends by their spellings and sorts).  The last
+        k - 1 bases of (u, o) are the first k - 1 of (v, p).  last_ms() is the writing call's, the edges' kernels included."""
+        out = _unitig_graph(self.L, self.L.bfcg_kmers_unitig_graph, self.t, min_cnt)
+        self._ms = float(self.L.bfcg_kmers_last_ms(self.t))
+        return out
+
     def clip(self, min_cnt=1, max_tip=None, max_mean=255, islands=False, max_rounds=8):
         """The graph at min_cnt cleaned (odd k <= 37; include/bfc_gpu.h defines tip, island and round): (a new GpuKmers that owns its
         table, stats u64 (rounds, 3)).  A round removes every unitig of at most max_tip k-mers (None: 2 k) and a mean count of at most
@@ -1079,7 +1119,7 @@ class GpuKmers:
 
     def last_ms(self):
         """GPU time of the last call's kernels: hist() / sub_sizes() / hist_sizes() / profile() one pass, list() and lookup() all their pieces,
-        read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces, neighbors() / list_graph() / extend() all their pieces, graph_census() one pass, unitigs() the call that writes; of a union() result,
+        read_stats() its two kernels, joint_hist() its two launches, list_vs() all its pieces, neighbors() / list_graph() / extend() all their pieces, graph_census() one pass, unitigs() and unitig_graph() the call that writes; of a union() result,
         its size passes and fill; of a clip() or pop_bubbles() result, every kernel of the call."""
         return self._ms
 

@@ -25,8 +25,10 @@ namespace {
 enum { UT_BT = 64 /* a lane walks a start: a workgroup is one wave */ };
 // the object's buffers (bfcg_kmers.d_ut): the marks, the cycles' nodes, counters; per set of starts (paths at +0, cycles at +SET) a
 // record, the winner flag, the length in bases and their scans; the call's five outputs.  A cleaning round (bfcg_gclean.h) uses the
-// marks (its KILL bits) and the counters
-enum { B_MARK, B_CAND, B_CTR, B_REC, B_WIN, B_LEN, B_UIDX, B_BOFF, SET = 5, B_SEQ = B_REC + 2 * SET, B_OFF, B_NK, B_SUM, B_ENDS, B_N };
+// marks (its KILL bits) and the counters.  bfcg_kmers_unitig_graph adds the end map (slot << 32 | unitig), the planes of every unitig's
+// first and last k-mer, the eight links of every unitig and its own two counters
+enum { B_MARK, B_CAND, B_CTR, B_REC, B_WIN, B_LEN, B_UIDX, B_BOFF, SET = 5, B_SEQ = B_REC + 2 * SET, B_OFF, B_NK, B_SUM, B_ENDS,
+       B_MAP, B_FIRST, B_LAST, B_LINKS, B_LCTR, B_N };
 static_assert(B_N <= BFCG_UT_NBUF, "bfcg_kmers.d_ut is too short");
 
 // ---- oriented k-mers as planes, for the device and the host ----------------------------------------------------------------------------

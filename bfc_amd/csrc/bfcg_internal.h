@@ -32,7 +32,7 @@ extern "C" int bfcg_resident_register(const void *bf, void *dev, int device, int
 
 /* the table read-out's object (include/bfc_gpu.h: bfcg_kmers_t): made and destroyed in bfcg_kmers.hip, which lists the table; bfcg_lookup.hip probes it,
    bfcg_readstats.hip reduces a profile per read */
-#define BFCG_UT_NBUF 20
+#define BFCG_UT_NBUF 24
 struct bfcg_kmers {
 	int k, l_pre, cshift, device, owns_table;
 	hipStream_t st;
@@ -52,6 +52,7 @@ struct bfcg_kmers {
 	int32_t *d_gls; uint64_t gls_cap;   // length and stop code per seed of bfcg_kmers_extend (bfcg_graph.hip; grown on demand, in bytes)
 	void *d_ut[BFCG_UT_NBUF]; uint64_t ut_bytes[BFCG_UT_NBUF]; // bfcg_kmers_unitigs's and bfcg_kmers_clip's buffers, named in bfcg_glink.h (grown on demand, in bytes)
 	uint64_t ut_cap;                    // starts a walk kernel of bfcg_kmers_unitigs / bfcg_kmers_clip takes per launch (BFCG_UNITIG_CAP at creation)
+	int link_map_min;                   // bfcg_kmers_unitig_graph's end map at its smallest capacity (BFCG_LINK_MAP_MIN=1 at creation; for tests)
 	uint64_t n_keys; int has_keys;     // the keys of a table this object built and owns (bfcg_kmers_union and bfcg_kmers_clip count them on the device)
 	float last_ms;
 };
@@ -202,6 +203,8 @@ BFCG_LOCAL ::bfcg_kmers *kmers_new(int k, int l_pre, int cshift, int device);
 BFCG_LOCAL uint64_t lookup_cap();
 // starts a walk kernel of bfcg_kmers_unitigs takes per launch (bfcg_unitigs.hip): 2^22, or what BFCG_UNITIG_CAP says
 BFCG_LOCAL uint64_t unitig_cap();
+// 1 if BFCG_LINK_MAP_MIN=1: the end map of bfcg_kmers_unitig_graph gets the smallest power of two above its entries (bfcg_unitigs.hip)
+BFCG_LOCAL int link_map_min();
 // a lookup's staging buffers d_qy / d_qout of q_cap k-mers, allocated by the first call that needs them (bfcg_lookup.hip; bfcg_graph.hip stages its k-mers in d_qy)
 BFCG_LOCAL int lookup_stage(::bfcg_kmers *t);
 // a profile's first half (bfcg_lookup.hip): the stream staged in d_pseq if it is the host's, d_pout grown, t->e0 recorded and k_profile launched

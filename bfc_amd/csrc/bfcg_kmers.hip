@@ -94,7 +94,7 @@ bfcg_kmers_t *bfcg::kmers_new(int k, int l_pre, int cshift, int device)
 	bfcg_kmers_t *t = (bfcg_kmers_t *)calloc(1, sizeof(bfcg_kmers_t));
 	if (!t) { bfcg::fail("out of host memory"); return NULL; }
 	t->k = k; t->l_pre = l_pre; t->cshift = cshift; t->device = device;
-	t->q_cap = bfcg::lookup_cap(); t->ut_cap = bfcg::unitig_cap();
+	t->q_cap = bfcg::lookup_cap(); t->ut_cap = bfcg::unitig_cap(); t->link_map_min = bfcg::link_map_min();
 	BFCG_CKN(bfcg_kmers_destroy(t), hipStreamCreate(&t->st));
 	BFCG_CKN(bfcg_kmers_destroy(t), hipEventCreate(&t->e0)); BFCG_CKN(bfcg_kmers_destroy(t), hipEventCreate(&t->e1));
 	BFCG_CKN(bfcg_kmers_destroy(t), hipMalloc(&t->d_hist, HIST_BINS * 8));

@@ -11,6 +11,12 @@
 //                    than that; only the cycle's smallest oriented k-mer completes the lap, and it emits
 //   k_list_scan      (bfcg_klist.h) the winners' flags and lengths into unitig indices and base offsets
 //   k_ut_fill        one lane per winner walks again and writes the bases at its offset
+// bfcg_kmers_unitig_graph is the same run with the edges between the oriented unitigs found after the fill:
+//   k_ut_fill<W, true>  also writes the planes of the unitig's first and last k-mer and enters the slots of a path's two end nodes
+//                    into the end map, an open-addressing table of slot << 32 | unitig with linear probing, twice as large as its
+//                    entries at least (BFCG_LINK_MAP_MIN=1 when the object is made: the smallest power of two above them)
+//   k_ut_links       one lane per (unitig, side): one present4 on the side's last oriented k-mer, and per present successor its slot,
+//                    the map's unitig for that slot and the orientation in which the successor is that unitig's first k-mer
 // The walk kernels run workgroups of one wave: the walks of a wave end when its longest ends, and a long one then holds back 63 lanes and
 // no other wave; the bitmap's atomics return nothing and are executed at the memory side, one dword each, so a lane does not wait for
 // them.  A launch takes at most `ut_cap` starts (BFCG_UNITIG_CAP when the object is made).
@@ -31,6 +37,8 @@ namespace {
 enum { UT_CAP = 1 << 22, UT_GRID_MAX = 2048 }; // UT_BT, the buffers B_*, link_rule, EndPred, set_mark: bfcg_glink.h
 enum { STOP_CYCLE = 64 };
 enum { CTR_CAND = 0, CTR_ERR = 1, CTR_N = 2 };
+enum { LC_EDGES = 0, LC_ERR = 1, LC_N = 2 }; // d_ut[B_LCTR]: the links written, and what went wrong on the way to them
+#define MAP_EMPTY (~0ULL) // (a slot index has 31 bits at most: no entry is all ones)
 
 struct Start { uint64_t a, b, sum; uint32_t nk, ends; }; // a winner: the planes of its first oriented k-mer, the sum of the counts, the k-mers, the ends byte
 
@@ -114,11 +122,39 @@ __global__ __launch_bounds__(UT_BT) void k_ut_cycle_count(TabRef T, int min_cnt,
 	rec[j] = r; win[j] = 1; len[j] = (uint32_t)(T.k + n - 1);
 }
 
+// ---- the end map: from the table slot of a path's end node to its unitig -----------------------------------------------------------------
+// `mask` + 1 words, a power of two above the number of entries, so a probe always meets an empty word; a probe gives up after one round
+// all the same
+struct EndMap { unsigned long long *w; uint64_t mask; };
+struct FillLinks { EndMap map; ulonglong2 *first, *last; unsigned long long *lctr; }; // what k_ut_fill<W, true> writes besides the unitig
+
+__device__ __forceinline__ uint64_t map_home(const EndMap &M, uint64_t slot) { return (slot * 0x9E3779B97F4A7C15ULL >> 32) & M.mask; }
+__device__ __forceinline__ bool map_put(const EndMap &M, uint64_t slot, uint64_t u) // a compare-and-swap on an empty word, as bfcg_upsert.h's
+{
+	uint64_t pos = map_home(M, slot);
+	for (uint64_t probe = 0; probe <= M.mask; ++probe, pos = (pos + 1) & M.mask)
+		if (atomicCAS(&M.w[pos], MAP_EMPTY, (unsigned long long)(slot << 32 | u)) == MAP_EMPTY) return true;
+	return false;
+}
+__device__ __forceinline__ int64_t map_get(const EndMap &M, uint64_t slot) // the unitig, or -1
+{
+	uint64_t pos = map_home(M, slot);
+	for (uint64_t probe = 0; probe <= M.mask; ++probe, pos = (pos + 1) & M.mask) {
+		const unsigned long long e = M.w[pos];
+		if (e == MAP_EMPTY) return -1;
+		if (e >> 32 == slot) return (int64_t)(e & 0xffffffffULL);
+	}
+	return -1;
+}
+
 // ---- the fill walk: winner i of a set writes unitig u0 + uidx[i] at base b0 + boff[i] ------------------------------------------------------
-template <typename W>
+// With LINKS it leaves first[u] and last[u] as well, and a path enters the slots of its two end nodes (one entry if they are one node)
+// into the end map; a cycle enters nothing: no edge leads into it from outside
+template <typename W, bool LINKS>
 __global__ __launch_bounds__(UT_BT) void k_ut_fill(TabRef T, int min_cnt, const Start *__restrict__ rec, const uint32_t *__restrict__ win, const unsigned long long *__restrict__ uidx,
                                                    const unsigned long long *__restrict__ boff, uint64_t first, uint64_t end, uint64_t u0, uint64_t b0, uint8_t *__restrict__ seq,
-                                                   unsigned long long *__restrict__ off, uint32_t *__restrict__ n_kmers, unsigned long long *__restrict__ cnt_sum, uint8_t *__restrict__ ends)
+                                                   unsigned long long *__restrict__ off, uint32_t *__restrict__ n_kmers, unsigned long long *__restrict__ cnt_sum, uint8_t *__restrict__ ends,
+                                                   FillLinks K)
 {
 	const uint64_t i = first + (uint64_t)blockIdx.x * UT_BT + threadIdx.x;
 	if (i >= end || !win[i]) return;
@@ -132,11 +168,76 @@ __global__ __launch_bounds__(UT_BT) void k_ut_fill(TabRef T, int min_cnt, const 
 		succ_planes(T.k, a, b, only_succ(g, a, b, min_cnt), a, b);
 		seq[p++] = base_at(a, b, 0);
 	}
+	if constexpr (LINKS) {
+		K.first[u] = make_ulonglong2(r.a, r.b); K.last[u] = make_ulonglong2(a, b);
+		if (r.ends & STOP_CYCLE) return;
+		uint64_t s_first = 0, s_last = 0;
+		bool ok = g.value_at(r.a, r.b, s_first) >= 0 && map_put(K.map, s_first, u);
+		if (ok && r.nk > 1) ok = g.value_at(a, b, s_last) >= 0 && map_put(K.map, s_last, u);
+		if (!ok) atomicOr(&K.lctr[LC_ERR], 1ULL);
+	}
 }
 
-int check_unitig_bufs(const char *who, const uint8_t *seq, uint64_t seq_cap, const void *off, const void *n_kmers, const void *cnt_sum, const void *ends, uint64_t n_cap)
+// ---- the edges: lane i in [lo, end) is side i & 1 of unitig i >> 1 -----------------------------------------------------------------------
+// x = the last oriented k-mer of (u, side): last[u], or rc(first[u]).  links[8 u + 4 side + c] = v << 1 | p if succ(x, c) is present and
+// is the first oriented k-mer of (v, p) -- first[v] for p = 0, rc(last[v]) for p = 1 --, else -1.  The left side of such a successor is
+// open (the symmetry of link, include/bfc_gpu.h), so its node is the end of a path and in the map; a miss means the table changed.
+// A cycle's one successor per side is its own first k-mer in that orientation
+template <typename W>
+__global__ __launch_bounds__(UT_BT) void k_ut_links(TabRef T, int min_cnt, EndMap M, const ulonglong2 *__restrict__ first_km, const ulonglong2 *__restrict__ last_km,
+                                                    const uint8_t *__restrict__ ends, uint64_t lo, uint64_t end, longlong2 *__restrict__ links, unsigned long long *__restrict__ lctr)
 {
-	if ((seq_cap && !seq) || (n_cap && (!off || !n_kmers || !cnt_sum || !ends))) return bfcg::fail("%s needs output buffers for seq_cap=%llu, n_cap=%llu", who, (unsigned long long)seq_cap, (unsigned long long)n_cap);
+	const uint64_t i = lo + (uint64_t)blockIdx.x * UT_BT + threadIdx.x;
+	uint32_t n_e = 0;
+	if (i < end) {
+		const uint64_t u = i >> 1;
+		const int side = (int)(i & 1);
+		const ulonglong2 f = first_km[u], l = last_km[u];
+		long long out[4] = { -1, -1, -1, -1 };
+		uint64_t xa = l.x, xb = l.y, ya, yb, ra, rb;
+		if (side) rc_planes(T.k, f.x, f.y, xa, xb);
+		if (ends[u] & STOP_CYCLE) {
+			ya = f.x; yb = f.y;
+			if (side) rc_planes(T.k, l.x, l.y, ya, yb);
+			const int c = (int)((yb & 1) << 1 | (ya & 1));
+#pragma unroll
+			for (int j = 0; j < 4; ++j) if (j == c) out[j] = (long long)(u << 1 | (uint64_t)side);
+			n_e = 1;
+		} else {
+			DevGraph<W> g; g.T = T;
+			const int o = g.present4(xa, xb, 0, min_cnt);
+			bool bad = false;
+#pragma unroll
+			for (int c = 0; c < 4; ++c) {
+				if (!(o >> c & 1)) continue;
+				uint64_t slot = 0;
+				succ_planes(T.k, xa, xb, c, ya, yb);
+				const int64_t v = g.value_at(ya, yb, slot) >= 0 ? map_get(M, slot) : -1;
+				if (v < 0) { bad = true; continue; }
+				const ulonglong2 vf = first_km[v], vl = last_km[v];
+				rc_planes(T.k, vl.x, vl.y, ra, rb);
+				if (ya == vf.x && yb == vf.y) out[c] = (long long)(v << 1);
+				else if (ya == ra && yb == rb) out[c] = (long long)(v << 1 | 1);
+				else { bad = true; continue; }
+				++n_e;
+			}
+			if (bad) atomicOr(&lctr[LC_ERR], 2ULL);
+		}
+		links[2 * i] = make_longlong2(out[0], out[1]); links[2 * i + 1] = make_longlong2(out[2], out[3]);
+	}
+#pragma unroll
+	for (int d = 32; d; d >>= 1) n_e += __shfl_down(n_e, d, 64);
+	if (lane_id() == 0 && n_e) atomicAdd(&lctr[LC_EDGES], (unsigned long long)n_e);
+}
+
+// where a call's edges go: a call without edges (bfcg_kmers_unitigs, bfcg_unitigs_host) passes no LinksOut at all, so that one argument
+// says both whether edges are wanted and where they are written (NULL there is the sizing call's, like the other buffers)
+struct LinksOut { int64_t *links; };
+
+int check_unitig_bufs(const char *who, const uint8_t *seq, uint64_t seq_cap, const void *off, const void *n_kmers, const void *cnt_sum, const void *ends, uint64_t n_cap,
+                      const LinksOut *lo)
+{
+	if ((seq_cap && !seq) || (n_cap && (!off || !n_kmers || !cnt_sum || !ends || (lo && !lo->links)))) return bfcg::fail("%s needs output buffers for seq_cap=%llu, n_cap=%llu", who, (unsigned long long)seq_cap, (unsigned long long)n_cap);
 	return 0;
 }
 
@@ -166,20 +267,32 @@ int set_scan(bfcg_kmers_t *t, int set, uint64_t n, uint64_t n_pad, unsigned long
 	BFCG_CK(hipMemcpyAsync(&tot[1], ut_buf<unsigned long long>(t, set + B_BOFF) + n_pad, 8, hipMemcpyDeviceToHost, t->st));
 	return 0;
 }
-template <typename W> int set_fill(bfcg_kmers_t *t, const TabRef &T, int min_cnt, int set, uint64_t n, uint64_t u0, uint64_t b0)
+template <typename W, bool LINKS> int set_fill(bfcg_kmers_t *t, const TabRef &T, int min_cnt, int set, uint64_t n, uint64_t u0, uint64_t b0, const FillLinks &K)
 {
 	for (uint64_t first = 0; first < n; first += t->ut_cap) {
 		const uint64_t end = n - first < t->ut_cap ? n : first + t->ut_cap;
-		hipLaunchKernelGGL((k_ut_fill<W>), dim3((unsigned)((end - first + UT_BT - 1) / UT_BT)), dim3(UT_BT), 0, t->st, T, min_cnt, ut_buf<Start>(t, set + B_REC),
+		hipLaunchKernelGGL((k_ut_fill<W, LINKS>), dim3((unsigned)((end - first + UT_BT - 1) / UT_BT)), dim3(UT_BT), 0, t->st, T, min_cnt, ut_buf<Start>(t, set + B_REC),
 		                   ut_buf<uint32_t>(t, set + B_WIN), ut_buf<unsigned long long>(t, set + B_UIDX), ut_buf<unsigned long long>(t, set + B_BOFF), first, end, u0, b0,
-		                   ut_buf<uint8_t>(t, B_SEQ), ut_buf<unsigned long long>(t, B_OFF), ut_buf<uint32_t>(t, B_NK), ut_buf<unsigned long long>(t, B_SUM), ut_buf<uint8_t>(t, B_ENDS));
+		                   ut_buf<uint8_t>(t, B_SEQ), ut_buf<unsigned long long>(t, B_OFF), ut_buf<uint32_t>(t, B_NK), ut_buf<unsigned long long>(t, B_SUM), ut_buf<uint8_t>(t, B_ENDS), K);
 	}
 	BFCG_CK(hipGetLastError());
 	return 0;
 }
+// the end map's words for `paths` paths, two entries each at most: the smallest power of two >= twice the entries, or, for tests, the
+// smallest one above them
+uint64_t map_words(uint64_t paths, int smallest)
+{
+	const uint64_t entries = 2 * paths, need = smallest ? entries + 1 : 2 * entries;
+	uint64_t w = 1;
+	while (w < need) w <<= 1;
+	return w;
+}
 
+// `who` = bfcg_kmers_unitigs (lo is NULL) or bfcg_kmers_unitig_graph, which after the fill finds the edges, writes them to lo->links and
+// sets n[2]
 template <typename W>
-int unitigs_run(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends, uint64_t n_cap, uint64_t n[2])
+int unitigs_run(bfcg_kmers_t *t, const char *who, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
+                const LinksOut *lo, uint64_t n_cap, uint64_t *n)
 {
 	const TabRef T = tab_ref(t);
 	const uint64_t n_slots = 1ULL << (t->l_pre + t->cshift), n_pairs = n_slots >> 1;
@@ -187,7 +300,7 @@ int unitigs_run(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t seq_cap, ui
 	// the path ends: the listing's two passes, the rows left on the device (planes in d_y, the two stop codes in d_oth)
 	EndPred<W> P; P.T = T; P.min_cnt = min_cnt;
 	uint64_t n_ends = 0;
-	if (list_dev(t, "bfcg_kmers_unitigs", P, min_cnt, -64, 0, 1u << t->l_pre, true, ~0ULL, &n_ends) != 0) return -1;
+	if (list_dev(t, who, P, min_cnt, -64, 0, 1u << t->l_pre, true, ~0ULL, &n_ends) != 0) return -1;
 	ms = t->last_ms; t->last_ms = 0;
 	// the counting walks of the paths, then the nodes they left unmarked
 	const uint64_t n_a = 2 * n_ends;
@@ -213,7 +326,7 @@ int unitigs_run(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t seq_cap, ui
 		BFCG_CK(hipGetLastError());
 		BFCG_CK(hipMemcpyAsync(ctr, t->d_ut[B_CTR], sizeof(ctr), hipMemcpyDeviceToHost, t->st));
 		if (ut_lap(t, &ms) != 0) return -1;
-		if (ctr[CTR_ERR]) return bfcg::fail("bfcg_kmers_unitigs: a walk left the graph it started in (code %llu): the table changed under the call", ctr[CTR_ERR]);
+		if (ctr[CTR_ERR]) return bfcg::fail("%s: a walk left the graph it started in (code %llu): the table changed under the call", who, ctr[CTR_ERR]);
 		if (ctr[CTR_CAND] <= cap) break;
 		if (ut_grow(t, B_CAND, ctr[CTR_CAND] * 8, "the nodes of the cycles") != 0) return -1;
 		BFCG_CK(hipEventRecord(t->e0, t->st));
@@ -234,24 +347,52 @@ int unitigs_run(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t seq_cap, ui
 	BFCG_CK(hipGetLastError());
 	BFCG_CK(hipMemcpyAsync(ctr, t->d_ut[B_CTR], sizeof(ctr), hipMemcpyDeviceToHost, t->st));
 	if (ut_lap(t, &ms) != 0) return -1;
-	if (ctr[CTR_ERR]) return bfcg::fail("bfcg_kmers_unitigs: a walk left the graph it started in (code %llu): the table changed under the call", ctr[CTR_ERR]);
+	if (ctr[CTR_ERR]) return bfcg::fail("%s: a walk left the graph it started in (code %llu): the table changed under the call", who, ctr[CTR_ERR]);
 	t->last_ms = ms;
 	n[0] = tot_a[0] + tot_b[0]; n[1] = tot_a[1] + tot_b[1];
 	if (n[0] > n_cap || n[1] > seq_cap) return 1; // nothing is written: the caller comes back with room for n[]
-	if (n[0] == 0) { if (off) off[0] = 0; return 0; }
+	if (n[0] == 0) { if (off) off[0] = 0; if (lo) n[2] = 0; return 0; }
 	// the fill walks and the copies
+	FillLinks K = { { NULL, 0 }, NULL, NULL, NULL };
+	if (lo) {
+		const uint64_t words = map_words(tot_a[0], t->link_map_min);
+		if (ut_grow(t, B_MAP, words * 8, "the unitigs' end map") != 0 || ut_grow(t, B_FIRST, n[0] * 16, "the unitigs' end k-mers") != 0 || ut_grow(t, B_LAST, n[0] * 16, "the unitigs' end k-mers") != 0 ||
+		    ut_grow(t, B_LINKS, n[0] * 64, "the unitigs' links") != 0 || ut_grow(t, B_LCTR, LC_N * 8, "the counters of the unitigs' links") != 0) return -1;
+		K.map.w = ut_buf<unsigned long long>(t, B_MAP); K.map.mask = words - 1;
+		K.first = ut_buf<ulonglong2>(t, B_FIRST); K.last = ut_buf<ulonglong2>(t, B_LAST); K.lctr = ut_buf<unsigned long long>(t, B_LCTR);
+	}
 	if (ut_grow(t, B_SEQ, n[1], "the unitigs' bases") != 0 || ut_grow(t, B_OFF, n[0] * 8, "the unitigs' offsets") != 0 || ut_grow(t, B_NK, n[0] * 4, "the unitigs' sizes") != 0 ||
 	    ut_grow(t, B_SUM, n[0] * 8, "the unitigs' sums") != 0 || ut_grow(t, B_ENDS, n[0], "the unitigs' ends") != 0) return -1;
+	unsigned long long lctr[LC_N] = { 0, 0 };
 	BFCG_CK(hipEventRecord(t->e0, t->st));
-	if (set_fill<W>(t, T, min_cnt, 0, n_a, 0, 0) != 0 || set_fill<W>(t, T, min_cnt, SET, n_b, tot_a[0], tot_a[1]) != 0) return -1;
-	BFCG_CK(hipEventRecord(t->e1, t->st));
+	if (lo) {
+		BFCG_CK(hipMemsetAsync(t->d_ut[B_MAP], 0xff, (K.map.mask + 1) * 8, t->st));
+		BFCG_CK(hipMemsetAsync(t->d_ut[B_LCTR], 0, LC_N * 8, t->st));
+		if (set_fill<W, true>(t, T, min_cnt, 0, n_a, 0, 0, K) != 0 || set_fill<W, true>(t, T, min_cnt, SET, n_b, tot_a[0], tot_a[1], K) != 0) return -1;
+		for (uint64_t first = 0; first < 2 * n[0]; first += t->ut_cap) { // the map is complete: the fills came before on this stream
+			const uint64_t end = 2 * n[0] - first < t->ut_cap ? 2 * n[0] : first + t->ut_cap;
+			hipLaunchKernelGGL((k_ut_links<W>), dim3((unsigned)((end - first + UT_BT - 1) / UT_BT)), dim3(UT_BT), 0, t->st, T, min_cnt, K.map, (const ulonglong2 *)K.first,
+			                   (const ulonglong2 *)K.last, (const uint8_t *)ut_buf<uint8_t>(t, B_ENDS), first, end, ut_buf<longlong2>(t, B_LINKS), K.lctr);
+		}
+		BFCG_CK(hipGetLastError());
+		BFCG_CK(hipEventRecord(t->e1, t->st));
+		BFCG_CK(hipMemcpyAsync(lctr, t->d_ut[B_LCTR], sizeof(lctr), hipMemcpyDeviceToHost, t->st));
+		if (ut_lap(t, &ms) != 0) return -1;
+		if (lctr[LC_ERR]) return bfcg::fail("%s: an end of a unitig leads to no unitig (code %llu): the table changed under the call", who, lctr[LC_ERR]);
+		BFCG_CK(hipMemcpyAsync(lo->links, t->d_ut[B_LINKS], n[0] * 64, hipMemcpyDeviceToHost, t->st));
+	} else {
+		if (set_fill<W, false>(t, T, min_cnt, 0, n_a, 0, 0, K) != 0 || set_fill<W, false>(t, T, min_cnt, SET, n_b, tot_a[0], tot_a[1], K) != 0) return -1;
+		BFCG_CK(hipEventRecord(t->e1, t->st));
+	}
 	BFCG_CK(hipMemcpyAsync(seq, t->d_ut[B_SEQ], n[1], hipMemcpyDeviceToHost, t->st));
 	BFCG_CK(hipMemcpyAsync(off, t->d_ut[B_OFF], n[0] * 8, hipMemcpyDeviceToHost, t->st));
 	BFCG_CK(hipMemcpyAsync(n_kmers, t->d_ut[B_NK], n[0] * 4, hipMemcpyDeviceToHost, t->st));
 	BFCG_CK(hipMemcpyAsync(cnt_sum, t->d_ut[B_SUM], n[0] * 8, hipMemcpyDeviceToHost, t->st));
 	BFCG_CK(hipMemcpyAsync(ends, t->d_ut[B_ENDS], n[0], hipMemcpyDeviceToHost, t->st));
-	if (ut_lap(t, &ms) != 0) return -1;
+	if (lo) BFCG_CK(hipStreamSynchronize(t->st)); // (the kernels' time is in ms already)
+	else if (ut_lap(t, &ms) != 0) return -1;
 	off[n[0]] = n[1];
+	if (lo) n[2] = lctr[LC_EDGES];
 	t->last_ms = ms;
 	return 0;
 }
@@ -264,18 +405,38 @@ uint64_t bfcg::unitig_cap()
 	const unsigned long long v = s ? strtoull(s, NULL, 10) : 0;
 	return v ? v : UT_CAP;
 }
+int bfcg::link_map_min()
+{
+	const char *s = getenv("BFCG_LINK_MAP_MIN");
+	return s && strtoull(s, NULL, 10) == 1;
+}
 
 extern "C" int bfcg_kmers_unitigs(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
                                   uint64_t n_cap, uint64_t n[2])
 {
 	if (!t || !n) return bfcg::fail("bad arguments to bfcg_kmers_unitigs");
 	if (check_min_cnt("bfcg_kmers_unitigs", min_cnt) != 0 || check_unitig_k("bfcg_kmers_unitigs", t->k) != 0) return -1;
-	if (check_unitig_bufs("bfcg_kmers_unitigs", seq, seq_cap, off, n_kmers, cnt_sum, ends, n_cap) != 0) return -1;
+	if (check_unitig_bufs("bfcg_kmers_unitigs", seq, seq_cap, off, n_kmers, cnt_sum, ends, n_cap, NULL) != 0) return -1;
 	if (t->l_pre + t->cshift > 31) return bfcg::fail("bfcg_kmers_unitigs: a table of 2^%d slots is too large: a unitig's k-mers and bases are counted in 32 bits", t->l_pre + t->cshift);
 	t->last_ms = 0;
 	BFCG_CK(hipSetDevice(t->device));
-	return t->k <= 32 ? unitigs_run<uint32_t>(t, min_cnt, seq, seq_cap, off, n_kmers, cnt_sum, ends, n_cap, n)
-	                  : unitigs_run<uint64_t>(t, min_cnt, seq, seq_cap, off, n_kmers, cnt_sum, ends, n_cap, n);
+	return t->k <= 32 ? unitigs_run<uint32_t>(t, "bfcg_kmers_unitigs", min_cnt, seq, seq_cap, off, n_kmers, cnt_sum, ends, NULL, n_cap, n)
+	                  : unitigs_run<uint64_t>(t, "bfcg_kmers_unitigs", min_cnt, seq, seq_cap, off, n_kmers, cnt_sum, ends, NULL, n_cap, n);
+}
+
+extern "C" int bfcg_kmers_unitig_graph(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
+                                       int64_t *links, uint64_t n_cap, uint64_t n[3])
+{
+	static const char who[] = "bfcg_kmers_unitig_graph";
+	if (!t || !n) return bfcg::fail("bad arguments to %s", who);
+	if (check_min_cnt(who, min_cnt) != 0 || check_unitig_k(who, t->k) != 0) return -1;
+	const LinksOut lo = { links };
+	if (check_unitig_bufs(who, seq, seq_cap, off, n_kmers, cnt_sum, ends, n_cap, &lo) != 0) return -1;
+	if (t->l_pre + t->cshift > 31) return bfcg::fail("%s: a table of 2^%d slots is too large: a unitig's k-mers and bases are counted in 32 bits", who, t->l_pre + t->cshift);
+	t->last_ms = 0;
+	BFCG_CK(hipSetDevice(t->device));
+	return t->k <= 32 ? unitigs_run<uint32_t>(t, who, min_cnt, seq, seq_cap, off, n_kmers, cnt_sum, ends, &lo, n_cap, n)
+	                  : unitigs_run<uint64_t>(t, who, min_cnt, seq, seq_cap, off, n_kmers, cnt_sum, ends, &lo, n_cap, n);
 }
 
 // ---- the host twin: no GPU -----------------------------------------------------------------------------------------------------------------
@@ -284,6 +445,7 @@ extern "C" int bfcg_kmers_unitigs(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, ui
 // their smaller strands) and emits the spelling that starts at the smaller of the two ends.  Then every node still unmarked: it lies on
 // a cycle, one lap from it marks the cycle and finds its smallest oriented k-mer, from which it is spelled.
 
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -360,30 +522,85 @@ struct HostUnitigs {
 	}
 };
 
+// bfcg_unitigs_host and bfcg_unitig_graph_host: the cap protocol, then the spellings; with `lo` the edges between them, by another
+// route than the device's -- a hash map from the first oriented k-mer of every oriented unitig (first[u] for (u, 0), rc(last[u]) for
+// (u, 1), cycles included) to u << 1 | o, asked for every present successor of every oriented unitig's last k-mer
+int host_unitigs(const char *who, const bfc_ch_t *ch, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
+                 const LinksOut *lo, uint64_t n_cap, uint64_t *n)
+{
+	if (!ch || !n) return bfcg::fail("bad arguments to %s", who);
+	if (check_min_cnt(who, min_cnt) != 0 || check_unitig_k(who, bfc_ch_get_k(ch)) != 0) return -1;
+	if (check_unitig_bufs(who, seq, seq_cap, off, n_kmers, cnt_sum, ends, n_cap, lo) != 0) return -1;
+	HostUnitigs h;
+	h.g.ch = ch; h.g.k = bfc_ch_get_k(ch); h.min_cnt = min_cnt;
+	if (h.run() != 0) return -1;
+	const uint64_t n0 = h.out.size(), n1 = h.bases;
+	if (n0 > n_cap || n1 > seq_cap) { n[0] = n0; n[1] = n1; return 1; }
+	// everything is made here first and copied out at the end: a failure on the way writes nothing
+	const int k = h.g.k;
+	std::vector<uint8_t> bases(n1);
+	std::vector<uint64_t> at(n0 + 1);
+	std::vector<Planes> last(n0);
+	uint64_t p = 0;
+	for (uint64_t u = 0; u < n0; ++u) {
+		const Start &r = h.out[u];
+		uint64_t a = r.a, b = r.b;
+		at[u] = p;
+		for (int l = k - 1; l >= 0; --l) bases[p++] = base_at(a, b, l);
+		for (uint32_t j = 1; j < r.nk; ++j) {
+			succ_planes(k, a, b, only_succ(h.g, a, b, min_cnt), a, b);
+			bases[p++] = base_at(a, b, 0);
+		}
+		last[u] = Planes{ a, b };
+	}
+	at[n0] = p;
+	std::vector<int64_t> found(lo ? 8 * n0 : 0, -1);
+	uint64_t edges = 0;
+	if (lo) {
+		std::unordered_map<Planes, int64_t, PlanesHash> head;
+		uint64_t ra, rb, ya, yb;
+		for (uint64_t u = 0; u < n0; ++u) {
+			rc_planes(k, last[u].a, last[u].b, ra, rb);
+			const bool fresh0 = head.emplace(Planes{ h.out[u].a, h.out[u].b }, (int64_t)(u << 1)).second, fresh1 = head.emplace(Planes{ ra, rb }, (int64_t)(u << 1 | 1)).second;
+			if (!fresh0 || !fresh1) return bfcg::fail("%s: two oriented unitigs start with one k-mer: the table changed under the call", who);
+		}
+		for (uint64_t u = 0; u < n0; ++u)
+			for (int o = 0; o < 2; ++o) {
+				uint64_t xa = last[u].a, xb = last[u].b;
+				if (o) rc_planes(k, h.out[u].a, h.out[u].b, xa, xb);
+				const int succ = h.g.present4(xa, xb, 0, min_cnt);
+				for (int c = 0; c < 4; ++c) {
+					if (!(succ >> c & 1)) continue;
+					succ_planes(k, xa, xb, c, ya, yb);
+					const auto it = head.find(Planes{ ya, yb });
+					if (it == head.end()) return bfcg::fail("%s: an end of a unitig leads to no unitig: the table changed under the call", who);
+					found[8 * u + 4 * o + c] = it->second;
+					++edges;
+				}
+			}
+	}
+	n[0] = n0; n[1] = n1;
+	if (n1) memcpy(seq, bases.data(), n1);
+	if (off) memcpy(off, at.data(), 8 * (n0 + 1));
+	for (uint64_t u = 0; u < n0; ++u) { n_kmers[u] = h.out[u].nk; cnt_sum[u] = h.out[u].sum; ends[u] = (uint8_t)h.out[u].ends; }
+	if (lo) {
+		if (n0) memcpy(lo->links, found.data(), 64 * n0);
+		n[2] = edges;
+	}
+	return 0;
+}
+
 } // namespace
 
 extern "C" int bfcg_unitigs_host(const bfc_ch_t *ch, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
                                  uint64_t n_cap, uint64_t n[2])
 {
-	if (!ch || !n) return bfcg::fail("bad arguments to bfcg_unitigs_host");
-	if (check_min_cnt("bfcg_unitigs_host", min_cnt) != 0 || check_unitig_k("bfcg_unitigs_host", bfc_ch_get_k(ch)) != 0) return -1;
-	if (check_unitig_bufs("bfcg_unitigs_host", seq, seq_cap, off, n_kmers, cnt_sum, ends, n_cap) != 0) return -1;
-	HostUnitigs h;
-	h.g.ch = ch; h.g.k = bfc_ch_get_k(ch); h.min_cnt = min_cnt;
-	if (h.run() != 0) return -1;
-	n[0] = h.out.size(); n[1] = h.bases;
-	if (n[0] > n_cap || n[1] > seq_cap) return 1;
-	uint64_t p = 0;
-	for (uint64_t u = 0; u < n[0]; ++u) {
-		const Start &r = h.out[u];
-		uint64_t a = r.a, b = r.b;
-		off[u] = p; n_kmers[u] = r.nk; cnt_sum[u] = r.sum; ends[u] = (uint8_t)r.ends;
-		for (int l = h.g.k - 1; l >= 0; --l) seq[p++] = base_at(a, b, l);
-		for (uint32_t j = 1; j < r.nk; ++j) {
-			succ_planes(h.g.k, a, b, only_succ(h.g, a, b, min_cnt), a, b);
-			seq[p++] = base_at(a, b, 0);
-		}
-	}
-	if (off) off[n[0]] = p;
-	return 0;
+	return host_unitigs("bfcg_unitigs_host", ch, min_cnt, seq, seq_cap, off, n_kmers, cnt_sum, ends, NULL, n_cap, n);
+}
+
+extern "C" int bfcg_unitig_graph_host(const bfc_ch_t *ch, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
+                                      int64_t *links, uint64_t n_cap, uint64_t n[3])
+{
+	const LinksOut lo = { links };
+	return host_unitigs("bfcg_unitig_graph_host", ch, min_cnt, seq, seq_cap, off, n_kmers, cnt_sum, ends, &lo, n_cap, n);
 }

@@ -1,6 +1,6 @@
 """A `bfc -d` dump read as a de Bruijn graph on the GPU: how many k-mers are dead ends, how many branch, and what lies around a k-mer.
 
-    python -m bfc_amd.kmergraph [-m INT] [-c INT [-i]] [-p INT [-d INT]] [-a INT] [-r INT] [-o FILE] [-t|-b] [-u] [-x FILE] [-l INT] table.dump
+    python -m bfc_amd.kmergraph [-m INT] [-c INT [-i]] [-p INT [-d INT]] [-a INT] [-r INT] [-o FILE] [-t|-b] [-u] [-g FILE] [-x FILE] [-l INT] table.dump
 
 The dump is restored with bfc_ch_restore and uploaded.  A k-mer is PRESENT if the table holds it with count >= INT (-m, default 1); a NODE
 is a k-mer of the table with such a count, on the strand the table stores (the one hash2cnt prints); its out-degree o is the number of
@@ -47,6 +47,19 @@ such tool, so the output format is this project's.  Standard output, in this ord
                           mean_count with two decimals; the stop codes of the two ends are 1, 2, 3 as above and 6, the only way on
                           leads back into the node itself (its own k-mer or its reverse complement); a cycle has 0 0 1 and repeats its
                           first k - 1 bases at the end
+    links<TAB>N
+                          under -g FILE (odd k <= 37), after the n50 line -- the three lines unitigs, cycles, n50 are printed under -g
+                          also without -u, the unitig lines only under -u: the edges of the compacted graph (bfcg_kmers_unitig_graph,
+                          the unitigs and their edges out of one call), which FILE then holds as GFA 1:
+                              H<TAB>VN:Z:1.0
+                              S<TAB>id<TAB>seq<TAB>LN:i:bases<TAB>KC:i:cnt_sum<TAB>km:f:mean_count
+                              L<TAB>id<TAB>+|-<TAB>id<TAB>+|-<TAB>(k-1)M
+                          The segments are named 1..n in the order of the unitig lines (sorted by sequence); a cycle's segment keeps
+                          its k + n - 1 bases.  One L line per edge, sorted by (id, strand, id, strand), + before -: from the last
+                          k-mer of the first segment read on that strand to the first k-mer of the second, which overlap in k - 1
+                          bases.  Every edge is there with its mirror (a - b + for a + b -), a hairpin's, which is its own, once; a
+                          cycle links to itself on both strands.  With -c / -p the file describes the cleaned table.  A FILE that
+                          cannot be written is an error, exit status 1
 """
 import ctypes as C
 import getopt
@@ -67,6 +80,7 @@ Options:
   -t       list the tips
   -b       list the branching k-mers
   -u       list the unitigs of the compacted graph (odd k <= 37)
+  -g FILE  write the compacted graph with its edges as GFA 1 (odd k <= 37)
   -x FILE  extend the k-mers of FILE both ways and print the unitig around each
   -l INT   at most INT bases each way [10000]
 """
@@ -115,15 +129,32 @@ def n50(lengths):
     return 0
 
 
-def _unitig_lines(rows, out):
+def gfa(k, seq, off, n_kmers, cnt_sum, links):
+    """(the GFA 1 text, the number of L lines) of unitig_graph()'s arrays: segments 1..n in unitig_rows()'s order"""
+    s = np.asarray(seq, dtype=np.uint8).tobytes()
+    name = [s[int(off[u]):int(off[u + 1])] for u in range(len(n_kmers))]
+    sid = [0] * len(name)
+    for rank, u in enumerate(sorted(range(len(name)), key=name.__getitem__)):
+        sid[u] = rank + 1
+    segs = sorted((sid[u], name[u], int(cnt_sum[u]), int(cnt_sum[u]) / int(n_kmers[u])) for u in range(len(name)))
+    links = np.asarray(links, dtype=np.int64).reshape(-1, 2, 4)
+    edges = sorted((sid[u], int(o), sid[int(links[u, o, c]) >> 1], int(links[u, o, c]) & 1) for u, o, c in zip(*np.nonzero(links >= 0)))
+    text = b"H\tVN:Z:1.0\n" + b"".join(b"S\t%d\t%s\tLN:i:%d\tKC:i:%d\tkm:f:%.2f\n" % (i, q, len(q), cs, mean) for i, q, cs, mean in segs)
+    return text + b"".join(b"L\t%d\t%s\t%d\t%s\t%dM\n" % (u, b"+-"[o:o + 1], v, b"+-"[p:p + 1], k - 1) for u, o, v, p in edges), len(edges)
+
+
+def _unitig_lines(rows, out, n_links=None, listed=True):
     out.write(b"unitigs\t%d\ncycles\t%d\nn50\t%d\n" % (len(rows), sum(r[5] for r in rows), n50([len(r[0]) for r in rows])))
-    out.write(b"".join(b"unitig\t%s\t%d\t%.2f\t%d\t%d\t%d\n" % (s, nk, cs / nk, left, right, cyc) for s, nk, cs, left, right, cyc in rows))
+    if n_links is not None:
+        out.write(b"links\t%d\n" % n_links)
+    if listed:
+        out.write(b"".join(b"unitig\t%s\t%d\t%.2f\t%d\t%d\t%d\n" % (s, nk, cs / nk, left, right, cyc) for s, nk, cs, left, right, cyc in rows))
 
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     try:
-        opts, args = getopt.getopt(argv, "tbuim:x:l:c:a:r:o:p:d:")
+        opts, args = getopt.getopt(argv, "tbuim:x:l:c:a:r:o:p:d:g:")
     except getopt.GetoptError:
         opts, args = [], []
     o = dict(opts)
@@ -160,13 +191,24 @@ def main(argv=None):
                 h.close()
                 if failed:
                     raise api.BfcGpuError("cannot write %s" % o["-o"])
-        rows = api.unitig_rows(*km.unitigs(min_cnt)) if "-u" in o else None   # (an even k or k > 37 is refused here, before any output)
+        rows = n_links = None
+        if "-g" in o:   # (the unitigs and their edges out of one call: a second call need not number the unitigs alike)
+            g = km.unitig_graph(min_cnt)
+            rows = api.unitig_rows(*g[:5])
+            text, n_links = gfa(t.k, g[0], g[1], g[2], g[3], g[5])
+            try:
+                with open(o["-g"], "wb") as fh:
+                    fh.write(text)
+            except OSError:
+                raise api.BfcGpuError("cannot write %s" % o["-g"])
+        elif "-u" in o:
+            rows = api.unitig_rows(*km.unitigs(min_cnt))   # (an even k or k > 37 is refused here, before any output)
         if t.k <= 37 or "-x" not in o:   # (k > 37 with -x alone: the walks need no decode)
             deg = km.graph_census(min_cnt)
             out.write("".join("deg\t%d\t%s\n" % (i, "\t".join(str(int(v)) for v in deg[i])) for i in range(5)).encode())
             out.write(b"nodes\t%d\nisolated\t%d\ntips\t%d\nsimple\t%d\nbranching\t%d\n" % summary(deg))
         if rows is not None:
-            _unitig_lines(rows, out)
+            _unitig_lines(rows, out, n_links, "-u" in o)
         if modes:
             mask = api.GRAPH_MASKS["tips" if modes[0] == "-t" else "branching"]
             for y, ch, nb in km.pieces_graph(min_cnt, mask):

@@ -501,6 +501,40 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *                         lane's sequential probes: expected work is near-linear on ordinary sequence (a cycle node gives up after about
  *                         ln n steps on average), but one unitig of millions of k-mers -- a path, or a cycle's leader on its lap -- runs
  *                         at the pace of one lane, the caveat bfcg_kmers_read_stats makes for a megabase contig
+ * The unitigs linked (bfcg_unitigs.hip): the compacted graph with its edges, out of one call -- the order of the unitigs is unspecified
+ * and the cycles are placed by an atomic counter, so a second call need not number them alike.  The domain is that of bfcg_kmers_unitigs
+ * -- odd k <= 37, min_cnt in [1, 255], l_pre + cshift <= 31 --, and nodes, link(x), unitigs, stop codes and the spelling emitted are
+ * exactly those defined above.
+ *   ORIENTED UNITIG  (u, 0) is unitig u as emitted, (u, 1) its reverse complement.  Its first and last oriented k-mers are the first
+ *               and last k bases of that spelling; for a cycle the spelling is the emitted k + n - 1 bases, so its last k-mer is the
+ *               lap's last node
+ *   EDGE        (u, o) -> (v, p) by base c exists when succ(x, c) is present at min_cnt, x being the last oriented k-mer of (u, o);
+ *               (v, p) is the oriented unitig whose first oriented k-mer succ(x, c) is.  That is well defined: the left side of
+ *               succ(x, c) is always open, by the symmetry of link stated under UNITIGS (if x has several successors, each of them
+ *               has code 3 or 2 to its left; if the single one has several predecessors, it has code 2 to its left; under code 6 it is
+ *               x or rc(x), whose side this is).  The last k - 1 bases of (u, o) are the first k - 1 of (v, p)
+ *   PER END     a side with code 1 has no edge, with code 2 two to four, with code 3 exactly one; with code 6 exactly one, whose target
+ *               is u itself -- (u, o) for a self-loop such as the A-run, (u, 1 - o) for a hairpin; a cycle has exactly one per side, to
+ *               (u, o) itself, by the base at position k - 1 of that spelling
+ *   MIRROR      if (u, o) -> (v, p) is an edge, so is (v, 1 - p) -> (u, 1 - o).  Both appear; an edge that is its own mirror (the
+ *               hairpin's) appears once
+ *   bfcg_kmers_unitig_graph  the first five outputs, the cap protocol (0 / 1 / -1), the refusals and their messages are
+ *                         bfcg_kmers_unitigs's.  links has 8 entries per unitig: links[8 u + 4 o + c] = v << 1 | p for the edge from
+ *                         (u, o) by base c (A C G T = 0..3), -1 if there is none; u and v index this call's own outputs.  links ==
+ *                         NULL with n_cap > 0 is refused like the other buffers.  n[2] = the entries >= 0, set only on return 0 (the
+ *                         sizing call leaves it alone: the edges are found after the fill); on return 1 or -1 links is untouched.
+ *                         The set {(spelling of u, o, c, spelling of v, p)} does not depend on the table's layout.  The input is never
+ *                         written.  bfcg_kmers_last_ms covers every kernel of the call.
+ *                         How: bfcg_kmers_unitigs's passes, whose fill walk also leaves the planes of each unitig's first and last
+ *                         k-mer (32 bytes per unitig) and enters the table slots of a path's two end nodes into an end map -- open
+ *                         addressing with linear probing over 64-bit words slot << 32 | u, inserted by a compare-and-swap on an empty
+ *                         word, the smallest power of two >= 4 x the paths, so never more than half full (BFCG_LINK_MAP_MIN=1 in the
+ *                         environment when the object is made: the smallest power of two above 2 x the paths, for tests); cycles enter
+ *                         nothing, no edge leads into one from outside.  Then one lane per (unitig, side), at most BFCG_UNITIG_CAP a
+ *                         launch: the four successors of the side's last k-mer probed at once, and per present one its slot, the
+ *                         map's unitig for it, and p = 0 if it is that unitig's first k-mer, 1 if the reverse complement of its last.
+ *                         A miss, or a successor that is neither, fails the call: the table changed under the call.  Device memory
+ *                         on top of bfcg_kmers_unitigs's: the map, and 96 bytes per unitig
  * The graph cleaned (bfcg_clip.hip): tips and islands clipped into a new table, on either form of the object.  The domain is that of
  * bfcg_kmers_unitigs -- odd k <= 37, min_cnt in [1, 255] --, and nodes, link(x), unitigs and stop codes are exactly those defined above.
  *   DEAD, ATTACHED  stop codes 1 and 6 are DEAD (nothing lies beyond but the node itself), 2 and 3 are ATTACHED
@@ -595,7 +629,11 @@ int   bfcg_ec_parse_stats(const char *comment, uint32_t *aux, uint32_t *aux2);
  *                         with count < min_cnt; returns the number of slots (with both NULL nothing else), -1 refused (k > 37, min_cnt)
  *   bfcg_extend_host      bfcg_kmers_extend by the same rule (one piece of code for both) on bfcg_kmer_occ_host
  *   bfcg_unitigs_host     bfcg_kmers_unitigs -- outputs, cap protocol, refusals -- by the same link rule (one piece of code for both) on
- *                         bfcg_kmer_occ_host, over bfc_ch_export_sorted's slots: every node walks, no bitmap */
+ *                         bfcg_kmer_occ_host, over bfc_ch_export_sorted's slots: every node walks, no bitmap
+ *   bfcg_unitig_graph_host  bfcg_kmers_unitig_graph -- outputs, cap protocol, refusals -- on bfcg_unitigs_host's unitigs: a hash map from
+ *                         the first oriented k-mer of every oriented unitig to (u, o), asked for each present successor of every
+ *                         oriented unitig's last k-mer; cycles go the same way, there is no end map and no slot.  Everything is made before
+ *                         anything is copied out: a return of -1 has written nothing, n[] included */
 typedef struct bfcg_kmers bfcg_kmers_t;
 bfcg_kmers_t *bfcg_kmers_create(const bfc_ch_t *ch, int device);
 bfcg_kmers_t *bfcg_kmers_attach(bfcg_ctx_t *ctx);
@@ -642,6 +680,10 @@ int   bfcg_kmers_unitigs(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t se
                          uint64_t n_cap, uint64_t n[2]);
 int   bfcg_unitigs_host(const bfc_ch_t *ch, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
                         uint64_t n_cap, uint64_t n[2]);
+int   bfcg_kmers_unitig_graph(bfcg_kmers_t *t, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
+                              int64_t *links, uint64_t n_cap, uint64_t n[3]);
+int   bfcg_unitig_graph_host(const bfc_ch_t *ch, int min_cnt, uint8_t *seq, uint64_t seq_cap, uint64_t *off, uint32_t *n_kmers, uint64_t *cnt_sum, uint8_t *ends,
+                             int64_t *links, uint64_t n_cap, uint64_t n[3]);
 enum { BFCG_CLIP_ISLANDS = 1 };
 bfcg_kmers_t *bfcg_kmers_clip(bfcg_kmers_t *t, int min_cnt, int max_tip, int max_mean, int flags, int max_rounds,
                               uint64_t *stats /* 3 per round: unitigs removed, k-mers removed, keys left */, int *n_rounds);

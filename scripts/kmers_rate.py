@@ -2,7 +2,7 @@
 from the attached context, kernels only, against the path it replaces for the spectrum -- bfcg_export_table followed by the host's
 bfc_ch_hist.  Not the headline bench; numbers quoted in profiles/kmers_rate.md.
 
-    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph | --unitigs | --clip | --pop] [k] [bf_shift] [genome size] [coverage]
+    python scripts/kmers_rate.py [--lookup | --readstats | --compare | --graph | --unitigs | --links | --clip | --pop] [k] [bf_shift] [genome size] [coverage]
 
 --lookup measures the other direction instead (bfcg_lookup.hip): lookup() of every listed k-mer in shuffled order, and profile() over a
 prefix of the reads that built the table, each next to the host's loop over bfc_ch_kmer_occ on the same input (bfcg_kmers_occ_host,
@@ -18,6 +18,8 @@ census next to the route without it -- export the table, bfcg_graph_census_host 
 --unitigs measures the compacted graph (bfcg_unitigs.hip): unitigs() -- the sizing call alone (listing of the path ends, counting walks,
 the pass for the cycles' nodes, scans) and the call that also fills -- kernels only, next to a census of the same table and to the route
 without it: export the table, bfcg_unitigs_host on the CPU (one thread).  The per-kernel split is a kernel trace of this script's run.
+--links measures what the edges cost on top of the walks (bfcg_kmers_unitig_graph): unitigs() and unitig_graph(), each the call that writes,
+kernels only, on the same table in the same run, and the edges by the kind of end they leave.  No host route: the twin walks for a minute.
 --clip measures the graph cleaning (bfcg_clip.hip): clip() at the default parameters -- tips of at most 2 k k-mers, eight rounds at most --
 and with islands, all the call's kernels, in k-mers of the input per second, beside unitigs() on the same table in the same run (the only
 yardstick there is: nobody measured this before), and the unitigs of the cleaned table beside those of the input.
@@ -51,6 +53,9 @@ if GRAPH:
 UNITIGS = "--unitigs" in sys.argv
 if UNITIGS:
     sys.argv.remove("--unitigs")
+LINKS = "--links" in sys.argv
+if LINKS:
+    sys.argv.remove("--links")
 CLIP = "--clip" in sys.argv
 if CLIP:
     sys.argv.remove("--clip")
@@ -325,6 +330,34 @@ def unitig_rates(min_cnt=1):
     t.close()
 
 
+def link_rates(min_cnt=1):
+    f = lambda v: " ".join("%.3f" % x for x in v)  # noqa: E731
+    print("build %s" % bfc_amd._lib.build_id())
+    ums, gms, wall = [], [], []
+    for rep in range(3):
+        seq_u, off_u, nk, cs, ends = km.unitigs(min_cnt)
+        ums.append(km.last_ms())
+    print("unitigs (min_cnt %d), the call that writes, 3 runs (ms): %s; %d unitigs" % (min_cnt, f(ums), len(nk)))
+    for rep in range(3):
+        t0 = time.perf_counter()
+        seq_g, off_g, nk_g, cs_g, ends_g, links = km.unitig_graph(min_cnt)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        gms.append(km.last_ms())
+    print("unitig_graph, the call that writes (the same, the end map and the edges), 3 runs (ms): %s; wall of sizing + writing call with the copies: %s"
+          % (f(gms), " ".join("%.1f" % v for v in wall)))
+    assert bfc_amd.unitig_rows(seq_g, off_g, nk_g, cs_g, ends_g) == bfc_amd.unitig_rows(seq_u, off_u, nk, cs, ends)
+    n_out = (links >= 0).sum(axis=2)                                                            # (n, 2): the edges that leave each side
+    code = np.stack([ends_g >> 3 & 7, ends_g & 7], axis=1)                                      # (n, 2): the stop code of the side they leave
+    print("%d edges from %d sides; by stop code of the side 2 / 3 / 6 / cycle: %s; sides with 2 / 3 / 4 edges: %s"
+          % (int(n_out.sum()), 2 * len(nk_g), " / ".join(str(int(n_out[code == c].sum())) for c in (2, 3, 6, 0)), " / ".join(str(int((n_out == v).sum())) for v in (2, 3, 4))))
+    back = links[links >= 0]
+    u, o, c = np.nonzero(links >= 0)
+    pairs = set(zip((u * 2 + o).tolist(), back.tolist()))
+    assert all(((v ^ 1), (s ^ 1)) in pairs for s, v in pairs)
+    print("every edge has its mirror")
+    print("unitig_graph best: %.3f ms = %.2f x unitigs (%.3f ms): the edges cost %.3f ms = %.2f ns per side" % (min(gms), min(gms) / min(ums), min(ums), min(gms) - min(ums), (min(gms) - min(ums)) * 1e6 / (2 * len(nk_g))))
+
+
 def _ms3(v):
     return " ".join("%.3f" % x for x in v)
 
@@ -408,6 +441,12 @@ if POP:
 
 if CLIP:
     clip_rates()
+    km.close()
+    g.close()
+    sys.exit(0)
+
+if LINKS:
+    link_rates()
     km.close()
     g.close()
     sys.exit(0)
